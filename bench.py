@@ -21,6 +21,15 @@ Rank 0 prints ONE JSON line.  Extra objects:
                 full train step leg at batch 16 (Hungarian matching + losses + backward + AdamW), run AFTER the timed
                 forward region and the CPU sample -- ms per step, images/sec and the K1 / K2 / K3 launch times.
                 `value` / `metric` stay configs[1].
+
+--dump-outputs DIR (rank 0): right after the timed region, what the last timed step returned is written as
+DIR/<name>.npy -- every tensor of the output object (`auxiliary_logits.3.masks_queries_logits` for nested ones), in
+--mode train also `loss_dict.*`, `matched_indices.*` and `parameters` (all parameters after the step's AdamW update,
+concatenated in `model.parameters()` order).  Floating tensors are stored as float32 (float64 stays float64), integer
+ones as float64.  DUMP_BYTES bounds the whole dump: an array above its share is replaced by a sample of its flattened
+values at sorted indices drawn from numpy's default_rng(0) for its size, so two runs with the same arguments compare
+element for element.  Inputs and weights are seeded; the outputs are not bitwise reproducible from process to process
+(the backbone's output already differs in its last bits), so compare them within a floating-point tolerance.
 """
 from __future__ import annotations
 
@@ -40,6 +49,7 @@ MFMA_F32_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: fp32 matrix peak (spec)
 # HBM bytes per K1 launch from the PMC counters of a separate rocprofv3 run over this same command (tools/pmc_bench.sh;
 # counters cannot be collected inside the driver's own run): the newest committed measurement
 K1_TRAFFIC_PROFILE = "r03_pmc_k1_traffic.json"
+DUMP_BYTES = 60 * 2 ** 20  # --dump-outputs: payload bound of the whole dump (under 64 MB with the .npy headers)
 
 
 def build_model(seed=0, num_labels=3, num_queries=100):
@@ -119,6 +129,48 @@ def train_leg(dev, batch=16, size=1024, warmup=2, steps=3, amp=True, seed=0):
             "kernels_us": {k: {"launches_per_step": n // steps, "avg_us": round(us, 1)} for k, (n, us) in sorted(ks.items())}}
 
 
+def _named_tensors(obj, name, acc):
+    if torch.is_tensor(obj):
+        acc[name] = obj
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            _named_tensors(v, f"{name}.{k}", acc)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            _named_tensors(v, f"{name}.{i}", acc)
+
+
+def dump_outputs(out, outdir, model=None):
+    """--dump-outputs: the tensors of the output object `out` (and, for a train step, its loss terms, matched indices
+    and the updated parameters of `model`) as outdir/<name>.npy, DUMP_BYTES in all.  Returns (arrays, bytes)."""
+    import numpy as np
+    arrays = {}
+    for f in out.keys():
+        _named_tensors(getattr(out, f), f, arrays)
+    if model is not None:
+        _named_tensors(out.loss_dict, "loss_dict", arrays)
+        _named_tensors(list(out.matched_indices), "matched_indices", arrays)  # per image (rows, cols); may be a lazy view
+        arrays["parameters"] = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+    itemsize = {k: 8 if t.dtype == torch.float64 or not t.is_floating_point() else 4 for k, t in arrays.items()}
+    # the smallest arrays are written whole, the rest share what is left equally
+    cap, left, n = {}, DUMP_BYTES, len(arrays)
+    for k in sorted(arrays, key=lambda k: arrays[k].numel() * itemsize[k]):
+        cap[k] = min(arrays[k].numel(), left // n // itemsize[k])
+        left -= cap[k] * itemsize[k]
+        n -= 1
+    os.makedirs(outdir, exist_ok=True)
+    total = 0
+    for k, t in arrays.items():
+        t = t.detach()
+        if cap[k] < t.numel():
+            idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), cap[k]))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = (t.double() if itemsize[k] == 8 else t.float()).cpu().numpy()
+        np.save(os.path.join(outdir, k + ".npy"), a)
+        total += a.nbytes
+    return len(arrays), total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -131,7 +183,11 @@ def main():
     ap.add_argument("--train-leg", type=int, default=1, help="1: after the default run also time a short configs[2] train leg (0 = skip)")
     ap.add_argument("--amp", choices=["off", "bf16"], default="off",
                     help="bf16: run the step under torch.autocast(bfloat16) (BASELINE configs 2-4)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (see the module docstring)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -165,11 +221,14 @@ def main():
         model.train()
         ml, cl = synthetic_labels(B, S, S, seed=rank, device=dev)
         engine = DataParallelEngine(model, lr=5e-5)
+        last = {}  # --dump-outputs: the output object of the latest step
 
         def step():
             with torch.autocast("cuda", dtype=torch.bfloat16, enabled=a.amp == "bf16"):
                 out = model(pixel_values=x, mask_labels=ml, class_labels=cl)
             engine.backward_and_step(out.loss)
+            if a.dump_outputs:
+                last["out"] = out
             return out.loss.detach()
 
     for _ in range(a.warmup):
@@ -193,6 +252,10 @@ def main():
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    dumped = None
+    if a.dump_outputs and rank == 0:  # before anything else runs the model again
+        dumped = (dump_outputs(out, a.dump_outputs) if a.mode == "fwd"
+                  else dump_outputs(last["out"], a.dump_outputs, model))
 
     if rank == 0:
         ksum = timer.summary()
@@ -244,6 +307,8 @@ def main():
                                    "frac": round(ach / MFMA_F32_PEAK_TFLOPS, 4), "traffic": None,
                                    "algorithmic_flop_per_launch": flop, "launches": n, "avg_us": round(us, 2)}
         line["kernels_us"] = {k: {"launches": n, "avg_us": round(us, 2)} for k, (n, us) in sorted(ksum.items())}
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": a.dump_outputs, "arrays": dumped[0], "bytes": dumped[1]}
         if world == 1 and a.cpu_images > 0:
             cb, res, xc = cpu_baseline(model, S, a.cpu_images)
             # the same sample through the HIP path, as a last parity check beside the timing
