@@ -33,6 +33,8 @@ extern "C" {
 
 #define WM2F_F32 0
 #define WM2F_BF16 1
+#define WM2F_I32 2 /* integer maps of the mAP entry points */
+#define WM2F_U8 3
 
 #define WM2F_OK 0
 #define WM2F_EINVAL (-1)      /* bad argument / unsupported shape */
@@ -462,6 +464,45 @@ int wm2f_instance_maps(const void* image_logits, const int32_t* kept_q, int n, v
  *   index removed); masks (T, n_pixels) uint8: masks[t][i] = (label_map[i] == ids[t]). */
 int wm2f_labelmap_to_masks(const int32_t* label_map, const int32_t* ids, uint8_t* masks, int64_t n_pixels, int T,
                            void* stream);
+
+/* ---- segmentation mAP on device ----------------------------------------------------
+ * The hot part of torchmetrics MeanAveragePrecision(iou_type="segm") -- pycocotools COCOeval.evaluate on binary
+ * masks -- as the reference's models/metrics.py::test_with_metrics and show_worst_predictions.py use it.  The host
+ * keeps COCOeval.accumulate / summarize (weed_instance_segmentation_amd/metrics.py).
+ * wm2f_labelmap_pair_counts: hist (B, P+1, G+1) int32 = joint histogram of, per image, the prediction id map
+ *                         pred_map (B, n_pixels) -- WM2F_F32 (ids as floats, -1 background: the post-processor's output)
+ *                         or WM2F_I32 -- and the GT raw-id map gt_map (B, n_pixels), WM2F_U8 or WM2F_I32.  Row r > 0 is
+ *                         prediction id r-1 (ids outside [0, P) count as row 0); column c > 0 is the GT raw id
+ *                         gt_ids[b][c-1] -- gt_ids (B, G) int32, ascending, n_ids (B) int32 of them valid per image --
+ *                         any other raw id is column 0.  Inner bins are intersections, row / column sums are areas.
+ *                         The histogram is overwritten (cleared on the stream first).  G <= 4096, else WM2F_EUNSUPPORTED.
+ *                         An LDS histogram per block while (P+1)(G+1) <= 12288, global atomics above.
+ * wm2f_mask_pair_counts:   det_masks (D, n_pixels), gt_masks (G, n_pixels) uint8 (any nonzero byte is set, masks may
+ *                         overlap) -> inter (D, G), det_area (D), gt_area (G) int32, all overwritten.  workspace of
+ *                         wm2f_mask_pair_counts_workspace(D, G, n_pixels) bytes (the bit-packed stacks).  n_pixels < 2^31.
+ * wm2f_coco_match:         greedy COCO matching (COCOeval.evaluateImg) of B images at once, one 64-lane workgroup per
+ *                         image, one lane per (area range, IoU threshold), IoU = inter / union in fp64.
+ *                         inter (B, D, G), det_area / det_label / det_order (B, D), gt_area / gt_label (B, G),
+ *                         n_det / n_gt (B) int32.  det_order: the image's detection indices by descending score, stable
+ *                         (padding after the n_det real ones).  A GT labelled INT32_MIN does not exist.
+ *                         iou_thresholds (T) and area_ranges (A, 2) fp64 (inclusive [lo, hi]), A * T <= 64.
+ *                         Out: det_rank (B, D) = rank of the detection among its image's detections of its category in
+ *                         score order (-1 for padding); det_matched / det_ignored (B, A, T, D) uint8 (0 for ranks >=
+ *                         max_det); gt_ignored (B, A, G) uint8.  Only the first max_det detections per (image, category)
+ *                         are matched.  LDS holds the image's detections (16 B each), its GT (20 B each), and a flag
+ *                         per (lane, GT): D <= 1024 and G <= 512 per image (46 KiB at both bounds and A * T = 40), else
+ *                         WM2F_EUNSUPPORTED. */
+int wm2f_labelmap_pair_counts(const void* pred_map, int pred_dtype, const void* gt_map, int gt_dtype,
+                              const int32_t* gt_ids, const int32_t* n_ids, int32_t* hist, int B, int64_t n_pixels, int P,
+                              int G, void* stream);
+int64_t wm2f_mask_pair_counts_workspace(int D, int G, int64_t n_pixels);
+int wm2f_mask_pair_counts(const uint8_t* det_masks, const uint8_t* gt_masks, int32_t* inter, int32_t* det_area,
+                          int32_t* gt_area, void* workspace, int D, int G, int64_t n_pixels, void* stream);
+int wm2f_coco_match(const int32_t* inter, const int32_t* det_area, const int32_t* gt_area, const int32_t* det_label,
+                    const int32_t* gt_label, const int32_t* det_order, const int32_t* n_det, const int32_t* n_gt,
+                    const double* iou_thresholds, const double* area_ranges, int32_t* det_rank, uint8_t* det_matched,
+                    uint8_t* det_ignored, uint8_t* gt_ignored, int B, int D, int G, int T, int A, int max_det,
+                    void* stream);
 
 #ifdef __cplusplus
 }

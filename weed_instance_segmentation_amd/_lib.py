@@ -16,6 +16,8 @@ if os.environ.get("WM2F_PROF_LIB"):  # tools only: another profiling build (comp
 
 WM2F_F32 = 0
 WM2F_BF16 = 1
+WM2F_I32 = 2
+WM2F_U8 = 3
 # return codes of include/wm2f.h
 WM2F_OK, WM2F_EINVAL, WM2F_EUNSUPPORTED, WM2F_ELAUNCH = 0, -1, -2, -3
 
@@ -87,6 +89,10 @@ SIGNATURES = {
     "wm2f_group_norm_act": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, c_float, _I, _P]),
     "wm2f_point_sample_fwd": (c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     "wm2f_point_sample_bwd": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "wm2f_labelmap_pair_counts": (c_int, [_P, _I, _P, _I, _P, _P, _P, _I, c_int64, _I, _I, _P]),
+    "wm2f_mask_pair_counts_workspace": (c_int64, [_I, _I, c_int64]),
+    "wm2f_mask_pair_counts": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, c_int64, _P]),
+    "wm2f_coco_match": (c_int, [_P] * 14 + [_I, _I, _I, _I, _I, _I, _P]),
 }
 
 # additions of the profiling library (include/wm2f_prof.h)

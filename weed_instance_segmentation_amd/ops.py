@@ -1269,3 +1269,83 @@ def labelmap_to_masks(label_map: torch.Tensor, ids: torch.Tensor) -> torch.Tenso
         check(load().wm2f_labelmap_to_masks(_p(label_map), _p(ids), _p(out), H * W, T, _stream(label_map)),
               "wm2f_labelmap_to_masks")
     return out
+
+
+# ------------------------------------------------------------------------------ segmentation mAP
+def labelmap_pair_counts(pred_maps: torch.Tensor, gt_maps: torch.Tensor, gt_ids: torch.Tensor, n_ids: torch.Tensor,
+                         P: int) -> torch.Tensor:
+    """(B, H, W) prediction id maps (fp32 with -1 background, or int32), (B, H, W) GT raw-id maps (uint8 or int32),
+    (B, G) ascending accepted GT ids with n_ids (B) valid -> (B, P+1, G+1) int32 joint histogram (row 0: no prediction,
+    column 0: no accepted GT id)."""
+    if not isinstance(pred_maps, torch.Tensor) or not isinstance(gt_maps, torch.Tensor):
+        raise TypeError("labelmap_pair_counts: expected tensors")
+    pred_maps = _req(pred_maps, "pred_maps", pred_maps.dtype)
+    gt_maps = _req(gt_maps, "gt_maps", gt_maps.dtype)
+    gt_ids, n_ids = _req(gt_ids, "gt_ids", torch.int32), _req(n_ids, "n_ids", torch.int32)
+    pdt = {torch.float32: _lib.WM2F_F32, torch.int32: _lib.WM2F_I32}.get(pred_maps.dtype)
+    gdt = {torch.uint8: _lib.WM2F_U8, torch.int32: _lib.WM2F_I32}.get(gt_maps.dtype)
+    if pdt is None or gdt is None:
+        raise TypeError(f"labelmap_pair_counts: prediction maps fp32 / int32 and GT maps uint8 / int32, got "
+                        f"{pred_maps.dtype} / {gt_maps.dtype}")
+    B = pred_maps.shape[0]
+    if gt_maps.shape != pred_maps.shape or gt_ids.dim() != 2 or gt_ids.shape[0] != B or n_ids.shape != (B,):
+        raise ValueError("labelmap_pair_counts: shapes disagree")
+    n = pred_maps[0].numel()
+    G = int(gt_ids.shape[1])
+    hist = torch.empty(B, P + 1, G + 1, device=pred_maps.device, dtype=torch.int32)
+    with torch.cuda.device(pred_maps.device):
+        check(_timed("labelmap_pair_counts", pred_maps, lambda: load().wm2f_labelmap_pair_counts(
+            _p(pred_maps), pdt, _p(gt_maps), gdt, _p(gt_ids), _p(n_ids), _p(hist), B, n, P, G, _stream(pred_maps))),
+            "wm2f_labelmap_pair_counts")
+    return hist
+
+
+def mask_pair_counts(det_masks: torch.Tensor, gt_masks: torch.Tensor):
+    """(D, H, W) and (G, H, W) bool / uint8 mask stacks (may overlap) -> inter (D, G), det_area (D), gt_area (G) int32."""
+    det_masks = _req(det_masks, "det_masks", det_masks.dtype if det_masks.dtype in (torch.bool, torch.uint8) else torch.uint8)
+    gt_masks = _req(gt_masks, "gt_masks", gt_masks.dtype if gt_masks.dtype in (torch.bool, torch.uint8) else torch.uint8)
+    if det_masks.shape[1:] != gt_masks.shape[1:]:
+        raise ValueError(f"mask_pair_counts: mask sizes differ: {tuple(det_masks.shape)} vs {tuple(gt_masks.shape)}")
+    D, G = int(det_masks.shape[0]), int(gt_masks.shape[0])
+    n = det_masks[0].numel() if D else gt_masks[0].numel()
+    dev = det_masks.device
+    inter = torch.zeros(D, G, device=dev, dtype=torch.int32)
+    det_area = torch.zeros(D, device=dev, dtype=torch.int32)
+    gt_area = torch.zeros(G, device=dev, dtype=torch.int32)
+    if D + G == 0 or n == 0:
+        return inter, det_area, gt_area
+    ws = torch.empty(int(load().wm2f_mask_pair_counts_workspace(D, G, n)), device=dev, dtype=torch.uint8)
+    a, g = det_masks.view(torch.uint8), gt_masks.view(torch.uint8)
+    with torch.cuda.device(dev):
+        check(_timed("mask_pair_counts", a, lambda: load().wm2f_mask_pair_counts(
+            _p(a) if D else None, _p(g) if G else None, _p(inter), _p(det_area), _p(gt_area), _p(ws), D, G, n,
+            _stream(a))), "wm2f_mask_pair_counts")
+    return inter, det_area, gt_area
+
+
+def coco_match(inter, det_area, gt_area, det_label, gt_label, det_order, n_det, n_gt, iou_thresholds, area_ranges,
+               max_det: int):
+    """Greedy COCO matching of B images (wm2f_coco_match): inter (B, D, G), det_* (B, D), gt_* (B, G), n_det / n_gt (B)
+    int32; iou_thresholds (T), area_ranges (A, 2) fp64.  Returns det_rank (B, D) int32, det_matched / det_ignored
+    (B, A, T, D) uint8, gt_ignored (B, A, G) uint8."""
+    i32 = torch.int32
+    inter, det_area, gt_area = _req(inter, "inter", i32), _req(det_area, "det_area", i32), _req(gt_area, "gt_area", i32)
+    det_label, gt_label = _req(det_label, "det_label", i32), _req(gt_label, "gt_label", i32)
+    det_order, n_det, n_gt = _req(det_order, "det_order", i32), _req(n_det, "n_det", i32), _req(n_gt, "n_gt", i32)
+    thr, rng = _req(iou_thresholds, "iou_thresholds", torch.float64), _req(area_ranges, "area_ranges", torch.float64)
+    B, D, G = (int(v) for v in inter.shape)
+    T, A = int(thr.shape[0]), int(rng.shape[0])
+    if (det_area.shape != (B, D) or det_label.shape != (B, D) or det_order.shape != (B, D) or gt_area.shape != (B, G)
+            or gt_label.shape != (B, G) or n_det.shape != (B,) or n_gt.shape != (B,) or rng.shape != (A, 2)):
+        raise ValueError("coco_match: shapes disagree")
+    dev = inter.device
+    det_rank = torch.empty(B, D, device=dev, dtype=i32)
+    det_matched = torch.empty(B, A, T, D, device=dev, dtype=torch.uint8)
+    det_ignored = torch.empty(B, A, T, D, device=dev, dtype=torch.uint8)
+    gt_ignored = torch.empty(B, A, G, device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev):
+        check(_timed("coco_match", inter, lambda: load().wm2f_coco_match(
+            _p(inter), _p(det_area), _p(gt_area), _p(det_label), _p(gt_label), _p(det_order), _p(n_det), _p(n_gt),
+            _p(thr), _p(rng), _p(det_rank), _p(det_matched), _p(det_ignored), _p(gt_ignored), B, D, G, T, A, int(max_det),
+            _stream(inter))), "wm2f_coco_match")
+    return det_rank, det_matched, det_ignored, gt_ignored
