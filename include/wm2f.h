@@ -504,6 +504,36 @@ int wm2f_coco_match(const int32_t* inter, const int32_t* det_area, const int32_t
                     uint8_t* det_ignored, uint8_t* gt_ignored, int B, int D, int G, int T, int A, int max_det,
                     void* stream);
 
+/* ---- image preprocessing on device ---------------------------------------------------
+ * The tensor work of Mask2FormerImageProcessorPil._preprocess (image_processing_pil_mask2former.py:485-585), bit-exact.
+ * wm2f_resize_normalize_u8: B packed uint8 HWC RGB images of different sizes -> pixel_values (B, 3, Hp, Wp) float32 and
+ *     pixel_mask (B, Hp, Wp) int64.  Per image, Pillow's 8-bit bilinear resample: a horizontal pass into the uint8 (H, w, 3)
+ *     intermediate in `workspace`, then a vertical pass; each output = clip8((2^21 + sum coef * u8) >> 22).  Then
+ *     lut (3, 256) float32 maps (channel, byte) to the rescaled, normalised value.  Outside the (h, w) image:
+ *     pixel_values 0, pixel_mask 0; inside: pixel_mask 1.
+ *       desc   HOST int64 (B, WM2F_PRE_DESC_LEN): in_off (bytes into images), ws_off (bytes into workspace), H, W, h, w,
+ *              tx, cx, kx, ty, cy, ky.
+ *       tables (n_table) int32: at tx, w pairs (xmin, count) of the columns; at cx, w * kx fixed-point coefficients (22
+ *              fraction bits); ty / cy / ky the same for the h rows.  An unchanged side takes an identity table
+ *              (xmin = i, count 1, coefficient 2^22).
+ *     The horizontal pass reads every input row.  B <= WM2F_PRE_MAX_IMAGES and every side <= WM2F_PRE_MAX_SIDE, else
+ *     WM2F_EUNSUPPORTED.
+ * wm2f_resize_nearest_labels: B packed id maps (WM2F_U8 or WM2F_I32, n_map_elems elements) -> out (B, Hp, Wp) int32,
+ *     out[y][x] = map[yi[y]][xi[x]] inside the (h, w) image, ignore_index outside; present (B, 256) uint8 is cleared on
+ *     the stream and then flags every id value 0..255 that occurs inside the image.
+ *       desc   HOST int64 (B, WM2F_LAB_DESC_LEN): in_off (elements), H, W, h, w, xi, yi (offsets of the w column and h
+ *              row source indices in tables). */
+#define WM2F_PRE_MAX_IMAGES 32
+#define WM2F_PRE_MAX_SIDE 16384
+#define WM2F_PRE_DESC_LEN 12
+#define WM2F_LAB_DESC_LEN 7
+int wm2f_resize_normalize_u8(const uint8_t* images, int64_t images_bytes, const int64_t* desc, const int32_t* tables,
+                             int64_t n_table, const float* lut, uint8_t* workspace, int64_t workspace_bytes,
+                             float* pixel_values, int64_t* pixel_mask, int B, int Hp, int Wp, void* stream);
+int wm2f_resize_nearest_labels(const void* maps, int dtype, int64_t n_map_elems, const int64_t* desc,
+                               const int32_t* tables, int64_t n_table, int32_t* out, uint8_t* present, int B, int Hp,
+                               int Wp, int ignore_index, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,3 +12,4 @@ from .modeling import Mask2FormerForUniversalSegmentation, Mask2FormerForUnivers
 __version__ = "0.1.0"
 from .postprocess import Mask2FormerInstancePostProcessor  # noqa: F401
 from .metrics import MeanAveragePrecision  # noqa: F401
+from .preprocess import Mask2FormerImageProcessor  # noqa: F401

@@ -1349,3 +1349,47 @@ def coco_match(inter, det_area, gt_area, det_label, gt_label, det_order, n_det, 
             _p(thr), _p(rng), _p(det_rank), _p(det_matched), _p(det_ignored), _p(gt_ignored), B, D, G, T, A, int(max_det),
             _stream(inter))), "wm2f_coco_match")
     return det_rank, det_matched, det_ignored, gt_ignored
+
+
+def resize_normalize_u8(images: torch.Tensor, desc, tables: torch.Tensor, lut: torch.Tensor, Hp: int, Wp: int):
+    """Packed uint8 HWC images (flat, on the device) -> (pixel_values (B, 3, Hp, Wp) float32, pixel_mask (B, Hp, Wp)
+    int64) through Pillow's fixed-point bilinear resample and a (3, 256) float32 lookup table (include/wm2f.h).
+    `desc` is a host int64 array (B, 12): in_off, ws_off, H, W, h, w, tx, cx, kx, ty, cy, ky; `tables` int32 on the
+    device.  The uint8 intermediate lives in a workspace of sum(H * w * 3) bytes allocated here."""
+    import numpy as np
+    images, tables, lut = _req(images, "images", torch.uint8), _req(tables, "tables", torch.int32), _req(lut, "lut", torch.float32)
+    d = np.ascontiguousarray(desc, dtype=np.int64)
+    B = int(d.shape[0])
+    ws_bytes = int((d[:, 2] * d[:, 5] * 3).sum())
+    dev = images.device
+    ws = torch.empty(max(ws_bytes, 1), device=dev, dtype=torch.uint8)
+    pv = torch.empty(B, 3, Hp, Wp, device=dev, dtype=torch.float32)
+    pm = torch.empty(B, Hp, Wp, device=dev, dtype=torch.int64)
+    with torch.cuda.device(dev):
+        check(load().wm2f_resize_normalize_u8(
+            _p(images), images.numel(), d.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _p(tables), tables.numel(),
+            _p(lut), _p(ws), ws.numel(), _p(pv), _p(pm), B, Hp, Wp, _stream(images)), "wm2f_resize_normalize_u8")
+    return pv, pm
+
+
+def resize_nearest_labels(maps: torch.Tensor, desc, tables: torch.Tensor, Hp: int, Wp: int, ignore_index: int):
+    """Packed uint8 or int32 id maps (flat, on the device) -> (maps (B, Hp, Wp) int32 padded with `ignore_index`,
+    present (B, 256) uint8 flags of the id values inside each image) through host-built nearest index tables.
+    `desc` is a host int64 array (B, 7): in_off, H, W, h, w, xi, yi."""
+    import numpy as np
+    if not maps.is_cuda:
+        raise _lib.Wm2fError(f"maps is on {maps.device}: the wm2f kernels run on a GPU only (no CPU fallback)")
+    if maps.dtype not in (torch.uint8, torch.int32):
+        raise TypeError(f"maps must be uint8 or int32, got {maps.dtype}")
+    dtype = _lib.WM2F_U8 if maps.dtype == torch.uint8 else _lib.WM2F_I32
+    tables = _req(tables, "tables", torch.int32)
+    d = np.ascontiguousarray(desc, dtype=np.int64)
+    B = int(d.shape[0])
+    out = torch.empty(B, Hp, Wp, device=maps.device, dtype=torch.int32)
+    present = torch.empty(B, 256, device=maps.device, dtype=torch.uint8)
+    with torch.cuda.device(maps.device):
+        check(load().wm2f_resize_nearest_labels(
+            _p(maps.contiguous()), dtype, maps.numel(), d.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _p(tables),
+            tables.numel(), _p(out), _p(present), B, Hp, Wp, int(ignore_index), _stream(maps)),
+            "wm2f_resize_nearest_labels")
+    return out, present
