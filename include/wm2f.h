@@ -353,6 +353,19 @@ int wm2f_token_linear_fwd(const void* x, const void* w, const void* bias, const 
                           const void* ln_beta, const void* pos, void* out, void* out_plus_pos, int64_t M, int K, int N, int relu,
                           int64_t pos_rows, float eps, int out_group, void* stream);
 
+/* wm2f_token_linear_split_weight: W (N, K) fp32 row-major -> w_split, N * K * 6 bytes: the three bf16 pieces of every weight
+ *                        (w = h + m + l, each piece the RNE bf16 of what the previous ones leave) in the fragment order
+ *                        wm2f_token_linear_split_fwd reads.  N % 16 == 0, K % 32 == 0.  Run once per weight version.
+ * wm2f_token_linear_split_fwd: what wm2f_token_linear_fwd computes, with the same epilogues and arguments, at fp32 accuracy on
+ *                        the bf16 matrix cores: x split into three bf16 pieces in registers, six of the nine piece products
+ *                        accumulated in fp32.  N = 256, 288, 512, 768 or 1024 (the LayerNorm epilogue: N <= 288),
+ *                        K % 32 == 0.  Deterministic; a token's output does not depend on M or on the other tokens.
+ *                        Non-finite inputs give non-finite outputs in the same positions (NaN where fp32 may give inf). */
+int wm2f_token_linear_split_weight(const void* w, void* w_split, int N, int K, void* stream);
+int wm2f_token_linear_split_fwd(const void* x, const void* w_split, const void* bias, const void* residual, const void* ln_gamma,
+                                const void* ln_beta, const void* pos, void* out, void* out_plus_pos, int64_t M, int K, int N,
+                                int relu, int64_t pos_rows, float eps, int out_group, void* stream);
+
 /* wm2f_token_wgrad_bf16: the weight / bias gradient of such a Linear (the backward autograd derives for nn.Linear; train
  *                        step of HF:1036-1103 under bf16 autocast):  dw (N, K) fp32 = dy (M, N)^T . x (M, K),
  *                        db (N) fp32 = column sums of dy (NULL: skipped); dy, x bf16 row-major, fp32 accumulation on the bf16

@@ -32,8 +32,10 @@
 // Where it stands (one MI355X, config-2 shapes, tools/kbench.py --only tg; profiles/r02_kbench_token_gemm.jsonl): 260 us for
 // the 256 -> 256 projections (86.6 TFLOP/s, the library: 262 us), 280 us for the merged 288-wide one (library 292), 339 us
 // with the residual + LayerNorm epilogue (library GEMM + the separate LayerNorm pass: 311), 992 us for fc2 + LayerNorm + pos
-// (library 842: its K = 1024 kernel runs at 80 % of the peak).  Parity, not a win -- so the model keeps the library GEMMs by
-// default (WM2F_TOKEN_GEMM=1 switches).  Timing ablations of the profiling build (WM2F_TG_MODE, outputs not valid): without
+// (library 842: its K = 1024 kernel runs at 80 % of the peak).  Parity, not a win: on gfx950 the fp32 matrix rate is the fp32
+// vector rate, and this instruction does not co-execute with vector work.  The model's inference path now runs these
+// Linears on the split-bf16 kernel (token_gemm_split.hip, DESIGN §13: fp32 accuracy on the bf16 matrix cores); this one
+// stays callable (ops.token_linear(..., split=False)) as its accuracy reference in the tests.  Timing ablations of the profiling build (WM2F_TG_MODE, outputs not valid): without
 // the epilogue's loads and stores 231 us, without x loads 255, without LDS reads 261, without barriers 260, with none of
 // them 219 -- against 151 us of pure MFMA issue at the 2.38 GHz the chip holds under this load (tools/probes/mfma_clock.hip
 // measures 154.6 TFLOP/s for the same instruction mix on register operands): the epilogue (all waves of all CUs store at

@@ -1,0 +1,390 @@
+// Token GEMM of the pixel decoder at fp32 accuracy on the bf16 matrix cores ("split-bf16"):
+//     out (M, N) = epilogue( x (M, K) . W (N, K)^T + bias )
+// with the epilogues of token_gemm.hip (bias, ReLU, residual + LayerNorm, + pos second output, feature-group-major output).
+//
+// The split.  Every fp32 operand is written as three bf16 pieces, a = h + m + l, each the round-to-nearest
+// bf16 of what the previous pieces leave: h = bf16(a), m = bf16(a - h), l = bf16(a - h - m).  Both differences are exact in
+// fp32, |m| <= 2^-8 |a|, |l| <= 2^-16 |a|, and l takes the last <= 8 significant bits exactly, so h + m + l == a for every
+// a of magnitude >= 2^-110 (below it the pieces fall under bf16's subnormal step 2^-133).  A product x w is accumulated as
+// the six terms h.h + h.m + m.h + h.l + l.h + m.m, each product of two bf16 values exact in fp32; the three left out (m.l,
+// l.m, l.l) are bounded by 2^-23 |x w| and are of order 2^-28 |x w| on typical data -- an fp32 GEMM in accuracy: the
+// tests hold it to twice the error of the fp32-MFMA kernel (token_gemm.hip) against an fp64 reference.
+// Non-finite values: h is taken from x clamped to the largest finite bf16 (an RNE bf16 of |x| near FLT_MAX is inf, and
+// inf - inf between the pieces would turn a finite input into NaN); an inf or NaN input still makes its residual
+// pieces inf / NaN, so every output a non-finite input touches is non-finite.  The one difference from fp32: such an
+// output is NaN where an fp32 GEMM may give +-inf (inf - inf inside the pieces).
+//
+// Layout of the work (MI355X: 256 CUs, 160 KiB LDS, v_mfma_f32_16x16x32_bf16 = 16 cycles, 8 of them blocking vector issue):
+//   * W is split ONCE per weight version (wm2f_token_linear_split_weight) into fragment order
+//     [k-step (K/32)][row tile (N/16)][piece h|m|l][lane][8 bf16]: a (row tile, k-step) A fragment of one piece is 1 KiB of
+//     contiguous bytes, lane-linear, and one k-step's panel of a feature slice is contiguous;
+//   * one persistent workgroup per CU, 8 waves (2 per SIMD, 256 registers each), no loader wave: every wave issues its
+//     share of the NEXT k-step's panel by LDS-DMA (1 KiB pieces) into the other half of a two-panel ring, together with its
+//     own x loads of the next k-step, then computes the current one; one `s_waitcnt vmcnt(0)` + barrier per k-step;
+//   * a CU owns a contiguous range of 16-token column tiles, its waves split it as evenly as tiles allow, and a wave walks
+//     its share two column tiles (32 tokens) per turn: each A fragment read from LDS feeds 2 x 6 MFMAs (3 ds_read_b128 per
+//     12 MFMAs of 16 cycles: a quarter of the LDS array's 256 B/clk);
+//   * x is the B operand, loaded as fp32 (lane (j, g): token j, channels 8g .. 8g + 7 of the k-step) and split in
+//     registers once per element and feature slice; a wave owns ALL N features of its tokens when N <= 288, so the
+//     LayerNorm of a token is a reduction inside the wave.  N = 1024 (fc1) runs as four 256-wide slices one after the
+//     other on the same tokens, so the slices' x re-reads hit the caches, not HBM.
+// Roofline: bf16 MFMA, 6 x 2 M N K flop against 2.5 PFLOP/s; HBM: x once, out once (+ residual, + pos).
+#include "common.h"
+
+namespace wm2f {
+namespace {
+
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+using f32x8 = __attribute__((ext_vector_type(8))) float;
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+
+constexpr int kSgWaves = 8;
+constexpr int kSgThreads = kSgWaves * 64;
+constexpr int kSgCT = 2;      // column tiles (16 tokens each) per wave and turn
+constexpr int kKStep = 32;    // K of one v_mfma_f32_16x16x32_bf16
+constexpr int kFrag = 1024;   // bytes of one A fragment piece (64 lanes x 8 bf16)
+constexpr unsigned kOob = 0x80000000u;
+constexpr float kBf16Max = 3.38953139e38f;  // largest finite bf16, 0x7F7F
+
+__device__ __forceinline__ void split3(const f32x8 x, bf16x8& h, bf16x8& m, bf16x8& l) {
+  f32x8 xc;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) xc[i] = __builtin_amdgcn_fmed3f(x[i], -kBf16Max, kBf16Max);
+  // vector conversions: v_cvt_pk_bf16_f32 (RNE, a NaN stays a NaN); bf16 -> f32 is exact
+  h = __builtin_convertvector(xc, bf16x8);
+  const f32x8 r1 = x - __builtin_convertvector(h, f32x8);
+  m = __builtin_convertvector(r1, bf16x8);
+  const f32x8 r2 = r1 - __builtin_convertvector(m, f32x8);
+  l = __builtin_convertvector(r2, bf16x8);
+}
+
+__global__ __launch_bounds__(256) void split_weight_kernel(const float* __restrict__ w, bf16x8* __restrict__ ws, int N, int K) {
+  const int kg_n = K / 8;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;  // over (feature n, group of 8 channels)
+  if (i >= N * kg_n) return;
+  const int n = i / kg_n, kg = i - n * kg_n;
+  const f32x4* src = reinterpret_cast<const f32x4*>(w + (int64_t)n * K + kg * 8);
+  const f32x4 lo = src[0], hi = src[1];
+  const f32x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  bf16x8 h, m, l;
+  split3(v, h, m, l);
+  const int ks = kg >> 2, g = kg & 3, rt = n >> 4, lane = (n & 15) + 16 * g;
+  const int64_t base = ((int64_t)ks * (N / 16) + rt) * 3 * 64 + lane;
+  ws[base] = h;
+  ws[base + 64] = m;
+  ws[base + 128] = l;
+}
+
+struct SgArgs {
+  const float *x, *bias, *residual, *gamma, *beta, *pos;
+  const void* ws;
+  float *out, *out_pos;
+  int64_t M;
+  int K, N, relu;
+  int out_group;  // 0: out (M, N) row-major; G > 0: out (N / G, M, G)
+  int64_t pos_rows;
+  float eps;
+  int tiles_total;  // ceil(M / 16)
+};
+
+__device__ __forceinline__ void sg_barrier() {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+
+// NRT = row tiles of one feature slice (16: N = 256 and the 256-wide slices of N = 1024; 18: N = 288).
+// EPI = the epilogue, fixed at compile time (one LayerNorm epilogue inside the k-step loop beside the others spilled):
+// 0 = bias (+ ReLU) row-major, 1 = bias (+ ReLU) feature-group major, 2 = bias + residual + LayerNorm (+ pos)
+template <int NRT, int EPI>
+__global__ __launch_bounds__(kSgThreads) void token_gemm_split_kernel(SgArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [2][NRT][3][64][16 B], then bias | gamma | beta
+  constexpr int kPanelBytes = NRT * 3 * kFrag;
+  constexpr int kPieces = NRT * 3;
+  constexpr int CT = kSgCT;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n_cu = gridDim.x, cu = blockIdx.x;
+  const int t0 = (int)(((int64_t)a.tiles_total * cu) / n_cu), t1 = (int)(((int64_t)a.tiles_total * (cu + 1)) / n_cu);
+  const int n_t = t1 - t0;
+  const int n_ks = a.K / kKStep;
+  const int n_sl = a.N / (NRT * 16);
+  const int share_max = (n_t + kSgWaves - 1) / kSgWaves;
+  const int n_iter = (share_max + CT - 1) / CT;
+  const int spt = n_sl * n_ks;  // k-steps per turn
+  const int n_q = n_iter * spt;
+  float* vec = reinterpret_cast<float*>(smem + 2 * kPanelBytes);
+  for (int i = tid; i < 3 * a.N; i += kSgThreads) {
+    const int which = i / a.N, f = i - which * a.N;
+    const float* srcv = which == 0 ? a.bias : (which == 1 ? a.gamma : a.beta);
+    vec[i] = srcv ? srcv[f] : 0.f;
+  }
+  __syncthreads();
+  if (n_q == 0) return;  // workgroup-uniform
+
+  const int base = n_t / kSgWaves, extra = n_t % kSgWaves;
+  const int w0 = t0 + wave * base + (wave < extra ? wave : extra);
+  const int w1 = w0 + base + (wave < extra ? 1 : 0);
+  const int g = lane >> 4, j = lane & 15;
+  const int nrt_all = a.N / 16;
+  const __amdgpu_buffer_rsrc_t w_rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.ws, 0, a.N * a.K * 6, 0x00020000);
+  const __amdgpu_buffer_rsrc_t x_rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, (int)(a.M * a.K * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t o_rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.out, 0, (int)(a.M * a.N * 4), 0x00020000);
+
+  // issue the loads of k-step q: this wave's pieces of the W panel (LDS-DMA into ring slot q & 1) and its x of that step
+  f32x8 xr[CT];
+  auto issue = [&](int q) {
+    const int it = q / spt, r = q - it * spt, sl = r / n_ks, ks = r - sl * n_ks;
+    unsigned char* dst = smem + (q & 1) * kPanelBytes;
+    const int src = (ks * nrt_all + sl * NRT) * 3 * kFrag;
+    for (int f = wave; f < kPieces; f += kSgWaves)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rs, (lds_ptr_t)(dst + f * kFrag), 16, lane * 16, src + f * kFrag, 0, 0);
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+      const int tile = w0 + CT * it + c;
+      const int64_t t = (int64_t)tile * 16 + j;
+      const unsigned xo = (tile < w1 && t < a.M) ? (unsigned)((t * a.K + ks * kKStep + 8 * g) * 4) : kOob;
+      const f32x4 lo = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(x_rs, xo, 0, 0));
+      const f32x4 hi = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(x_rs, xo, 16, 0));
+      xr[c] = (f32x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    }
+  };
+
+  issue(0);
+  sg_barrier();  // (also publishes vec)
+
+  f32x4 acc[NRT][CT];
+#pragma unroll
+  for (int rt = 0; rt < NRT; ++rt)
+#pragma unroll
+    for (int c = 0; c < CT; ++c) acc[rt][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  for (int q = 0; q < n_q; ++q) {
+    const int it = q / spt, r = q - it * spt, sl = r / n_ks, ks = r - sl * n_ks;
+    const int ct0 = w0 + CT * it;
+    const int n_live = ct0 >= w1 ? 0 : (ct0 + 1 >= w1 ? 1 : 2);  // wave-uniform
+    bf16x8 bh[CT], bm[CT], bl[CT];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) split3(xr[c], bh[c], bm[c], bl[c]);
+    // the next step's loads fly under this step's MFMAs -- except before a LayerNorm epilogue, where their 16 registers
+    // made the epilogue spill: there they are issued after it
+    const bool late = EPI == 2 && ks + 1 == n_ks;
+    if (q + 1 < n_q && !late) issue(q + 1);
+
+    const unsigned char* panel = smem + (q & 1) * kPanelBytes;
+    auto read_a = [&](bf16x8 (&dst)[3], int rt) {
+#pragma unroll
+      for (int p = 0; p < 3; ++p) dst[p] = *reinterpret_cast<const bf16x8*>(panel + (rt * 3 + p) * kFrag + lane * 16);
+    };
+    // the six products of one (row tile, column tile); the small terms first
+    auto six = [&](f32x4 c, const bf16x8 (&av)[3], int cc) {
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1], bm[cc], c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[2], bh[cc], c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bl[cc], c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1], bh[cc], c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bm[cc], c, 0, 0, 0);
+      return __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bh[cc], c, 0, 0, 0);
+    };
+    // a turn with one live column tile runs the second on zeros (x loads out of range) and stores nothing of it: a
+    // separate one-tile loop beside this one made the compiler spill the accumulators
+    if (n_live > 0) {
+      bf16x8 av[2][3];
+      read_a(av[0], 0);
+#pragma unroll
+      for (int rt = 0; rt < NRT; ++rt) {
+        if (rt + 1 < NRT) read_a(av[(rt + 1) & 1], rt + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        acc[rt][0] = six(acc[rt][0], av[rt & 1], 0);
+        acc[rt][1] = six(acc[rt][1], av[rt & 1], 1);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+
+    if (ks + 1 == n_ks) {
+      // ---- epilogue of feature slice sl.  Lane (j, g) holds, per row tile rt and column tile c, features
+      //      n0 + rt*16 + 4g .. +3 of token (ct0 + c)*16 + j.
+      const int n0 = sl * NRT * 16;
+#pragma unroll
+      for (int c = 0; c < CT; ++c) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (c < n_live) {  // wave-uniform
+          const int64_t tk = (int64_t)(ct0 + c) * 16 + j;
+          const bool tok_ok = tk < a.M;
+          const unsigned row_o = tok_ok ? (unsigned)((tk * a.N + n0) * 4) : kOob;
+#pragma unroll
+          for (int rt = 0; rt < NRT; ++rt) {
+            f32x4 v = acc[rt][c] + *reinterpret_cast<const f32x4*>(vec + n0 + rt * 16 + 4 * g);
+            if (a.relu) v = __builtin_elementwise_max(v, (f32x4){0.f, 0.f, 0.f, 0.f});
+            acc[rt][c] = v;
+          }
+          if (EPI == 2) {  // LayerNorm over the token's N features (n_sl == 1): this lane's NRT * 4 values, then the 4 lane groups
+            constexpr int kEB = 2;  // row tiles per batch of epilogue loads (4 spilled beside the accumulators of two column tiles)
+            if (a.residual) {
+              const __amdgpu_buffer_rsrc_t r_rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.residual, 0, (int)(a.M * a.N * 4), 0x00020000);
+#pragma unroll
+              for (int h0 = 0; h0 < NRT; h0 += kEB) {
+                f32x4 rv[kEB];
+#pragma unroll
+                for (int i = 0; i < kEB; ++i)
+                  rv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_rs, row_o + (unsigned)(((h0 + i) * 16 + 4 * g) * 4), 0, 0));
+#pragma unroll
+                for (int i = 0; i < kEB; ++i) acc[h0 + i][c] += rv[i];
+                __builtin_amdgcn_sched_barrier(0);  // one batch of residual rows in registers at a time
+              }
+            }
+            float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+            for (int rt = 0; rt < NRT; ++rt) {
+              const f32x4 v = acc[rt][c];
+              s1 += (v[0] + v[1]) + (v[2] + v[3]);
+              s2 += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+            }
+            s1 += __shfl_xor(s1, 16, 64);
+            s1 += __shfl_xor(s1, 32, 64);
+            s2 += __shfl_xor(s2, 16, 64);
+            s2 += __shfl_xor(s2, 32, 64);
+            const float inv_n = 1.f / (float)a.N;
+            const float mean = s1 * inv_n;
+            float var = s2 * inv_n - mean * mean;
+            var = var < 0.f ? 0.f : var;
+            const float rstd = rsqrtf(var + a.eps);
+#pragma unroll
+            for (int rt = 0; rt < NRT; ++rt) {
+              const int f0 = rt * 16 + 4 * g;
+              const f32x4 gm = *reinterpret_cast<const f32x4*>(vec + a.N + f0), bt = *reinterpret_cast<const f32x4*>(vec + 2 * a.N + f0);
+              acc[rt][c] = (acc[rt][c] - mean) * rstd * gm + bt;
+            }
+#pragma unroll
+            for (int rt = 0; rt < NRT; ++rt)
+              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[rt][c]), o_rs, row_o + (unsigned)((rt * 16 + 4 * g) * 4), 0, 0);
+            if (a.out_pos) {  // the next layer's hidden + pos
+              const __amdgpu_buffer_rsrc_t p_rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.pos, 0, (int)(a.pos_rows * a.N * 4), 0x00020000);
+              const __amdgpu_buffer_rsrc_t q_rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.out_pos, 0, (int)(a.M * a.N * 4), 0x00020000);
+              const unsigned prow = tok_ok ? (unsigned)((tk % a.pos_rows) * a.N * 4) : kOob;
+#pragma unroll
+              for (int h0 = 0; h0 < NRT; h0 += kEB) {
+                f32x4 pv[kEB];
+#pragma unroll
+                for (int i = 0; i < kEB; ++i)
+                  pv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(p_rs, prow + (unsigned)(((h0 + i) * 16 + 4 * g) * 4), 0, 0));
+#pragma unroll
+                for (int i = 0; i < kEB; ++i)
+                  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[h0 + i][c] + pv[i]), q_rs,
+                                                         row_o + (unsigned)(((h0 + i) * 16 + 4 * g) * 4), 0, 0);
+              }
+            }
+          } else if (EPI == 1) {
+            // feature-group-major output (N / G, M, G); a lane's 4 consecutive features stay inside one group (G % 4 == 0)
+            const unsigned G = (unsigned)a.out_group;
+            const unsigned grp_bytes = (unsigned)(a.M * G * 4);
+            const unsigned tok_o = tok_ok ? (unsigned)(tk * G * 4) : kOob;
+#pragma unroll
+            for (int rt = 0; rt < NRT; ++rt) {
+              const unsigned f0 = (unsigned)(n0 + rt * 16 + 4 * g);
+              const unsigned grp = f0 / G;
+              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[rt][c]), o_rs, tok_o + grp * grp_bytes + (f0 - grp * G) * 4, 0, 0);
+            }
+          } else {
+#pragma unroll
+            for (int rt = 0; rt < NRT; ++rt)
+              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[rt][c]), o_rs, row_o + (unsigned)((rt * 16 + 4 * g) * 4), 0, 0);
+          }
+        }
+#pragma unroll
+        for (int rt = 0; rt < NRT; ++rt) acc[rt][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      }
+    }
+    if (q + 1 < n_q && late) issue(q + 1);
+    sg_barrier();  // step q + 1's panel and x have landed; every wave is done with slot q & 1
+  }
+}
+
+int device_cu_count(int* n_cu) {
+  static int cached = 0;
+  if (cached == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
+    cached = prop.multiProcessorCount;
+  }
+  *n_cu = cached;
+  return 0;
+}
+
+}  // namespace
+}  // namespace wm2f
+
+using namespace wm2f;
+
+extern "C" int wm2f_token_linear_split_weight(const void* w, void* w_split, int N, int K, void* stream) {
+  const char* who = "wm2f_token_linear_split_weight";
+  WM2F_REQUIRE(w && w_split, "%s: null pointer", who);
+  WM2F_REQUIRE(N > 0 && K > 0 && N % 16 == 0 && K % kKStep == 0, "%s: N = %d must be a multiple of 16 and K = %d of %d", who, N, K, kKStep);
+  WM2F_REQUIRE((int64_t)N * K * 6 < (1ll << 31), "%s: the split weight must stay below 2 GiB", who);
+  const int total = N * (K / 8);
+  hipLaunchKernelGGL(split_weight_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)w,
+                     (bf16x8*)w_split, N, K);
+  WM2F_CHECK_LAUNCH(who);
+  return WM2F_OK;
+}
+
+extern "C" int wm2f_token_linear_split_fwd(const void* x, const void* w_split, const void* bias, const void* residual,
+                                           const void* ln_gamma, const void* ln_beta, const void* pos, void* out,
+                                           void* out_plus_pos, int64_t M, int K, int N, int relu, int64_t pos_rows, float eps,
+                                           int out_group, void* stream) {
+  const char* who = "wm2f_token_linear_split_fwd";
+  WM2F_REQUIRE(x && w_split && bias && out, "%s: null pointer", who);
+  WM2F_REQUIRE(M > 0 && K > 0 && N > 0, "%s: non-positive size", who);
+  WM2F_REQUIRE(N == 256 || N == 288 || N == 512 || N == 768 || N == 1024,
+               "%s: N = %d is not built (256, 288 and multiples of 256 up to 1024 are)", who, N);
+  WM2F_REQUIRE(K % kKStep == 0, "%s: K = %d must be a multiple of %d", who, K, kKStep);
+  WM2F_REQUIRE(M * (int64_t)K * 4 < (1ll << 31) && M * (int64_t)N * 4 < (1ll << 31), "%s: x / out must stay below 2 GiB (32-bit buffer offsets)", who);
+  WM2F_REQUIRE((int64_t)N * K * 6 < (1ll << 31), "%s: the split weight must stay below 2 GiB", who);
+  WM2F_REQUIRE(pos_rows * (int64_t)N * 4 < (1ll << 31), "%s: pos must stay below 2 GiB", who);
+  WM2F_REQUIRE((ln_gamma == nullptr) == (ln_beta == nullptr), "%s: LayerNorm needs both gamma and beta", who);
+  WM2F_REQUIRE(!ln_gamma || N <= 288, "%s: the LayerNorm epilogue needs N <= 288 (one feature slice per token)", who);
+  WM2F_REQUIRE(!residual || ln_gamma, "%s: the residual belongs to the LayerNorm epilogue", who);
+  WM2F_REQUIRE(!out_plus_pos || (pos && ln_gamma && pos_rows > 0), "%s: out_plus_pos needs pos, pos_rows and the LayerNorm epilogue", who);
+  WM2F_REQUIRE(out_group == 0 || (out_group > 0 && out_group % 4 == 0 && N % out_group == 0 && !ln_gamma),
+               "%s: out_group = %d must divide N, be a multiple of 4 and exclude the LayerNorm epilogue", who, out_group);
+  int n_cu = 0;
+  if (device_cu_count(&n_cu) != 0) {
+    set_error("%s: cannot query the device", who);
+    return WM2F_ELAUNCH;
+  }
+  SgArgs a;
+  a.x = (const float*)x;
+  a.ws = w_split;
+  a.bias = (const float*)bias;
+  a.residual = (const float*)residual;
+  a.gamma = (const float*)ln_gamma;
+  a.beta = (const float*)ln_beta;
+  a.pos = (const float*)pos;
+  a.out = (float*)out;
+  a.out_pos = (float*)out_plus_pos;
+  a.M = M;
+  a.K = K;
+  a.N = N;
+  a.relu = relu;
+  a.out_group = out_group;
+  a.pos_rows = pos_rows;
+  a.eps = eps;
+  a.tiles_total = (int)ceil_div64(M, 16);
+  int grid = n_cu;
+  if (grid > a.tiles_total) grid = a.tiles_total;
+  const int nrt = N == 288 ? 18 : 16;
+  const size_t lds = (size_t)2 * nrt * 3 * kFrag + (size_t)3 * N * sizeof(float);
+  const int epi = ln_gamma ? 2 : (out_group > 0 ? 1 : 0);
+  void (*kfn)(SgArgs) = nullptr;
+  if (N == 288) kfn = epi == 2 ? token_gemm_split_kernel<18, 2> : (epi == 1 ? token_gemm_split_kernel<18, 1> : token_gemm_split_kernel<18, 0>);
+  else kfn = epi == 2 ? token_gemm_split_kernel<16, 2> : (epi == 1 ? token_gemm_split_kernel<16, 1> : token_gemm_split_kernel<16, 0>);
+  hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) {
+    set_error("%s: cannot raise dynamic LDS to %zu: %s", who, lds, hipGetErrorString(e));
+    return WM2F_ELAUNCH;
+  }
+  hipLaunchKernelGGL(kfn, dim3(grid), dim3(kSgThreads), lds, (hipStream_t)stream, a);
+  WM2F_CHECK_LAUNCH(who);
+  return WM2F_OK;
+}

@@ -126,9 +126,10 @@ class MSDeformAttn(nn.Module):
             return self._cat["w_lanes"], self._cat["b_lanes"]
         return self._cat["w"], self._cat["b"]
 
-    def forward(self, hidden, pos, ref, level_hw, hp=None, hidden_lp=None):
+    def forward(self, hidden, pos, ref, level_hw, hp=None, hidden_lp=None, project=True):
         """hidden (B,S,C); pos (S,C) shared by the batch; ref (S,L,2); hp = hidden + pos if already known (training: possibly in
-        bf16, as the fused LayerNorm of the previous layer wrote it); hidden_lp = hidden in bf16 if already known."""
+        bf16, as the fused LayerNorm of the previous layer wrote it); hidden_lp = hidden in bf16 if already known.
+        project=False (inference only): the attention output before output_proj, for a caller that fuses that projection."""
         B, S, C = hidden.shape
         H, L, P = self.n_heads, self.n_levels, self.n_points
         if hp is None:
@@ -158,13 +159,23 @@ class MSDeformAttn(nn.Module):
             # inference, the encoder's own shape: one merged projection with its rows in the kernel's lane order
             w, b = self._offsets_logits_weight(lanes=True)
             # (under autocast the projection stays a bf16 library GEMM, as the dependency's Linear is there)
-            hm_rows = HEAD_MAJOR_ROWS and not torch.is_autocast_enabled("cuda") and ops.token_linear_applies(hp, w)
-            hm_value = HEAD_MAJOR_VALUE and hm_rows and ops.token_linear_applies(hidden, self.value_proj.weight)
-            if hm_value:
-                value = ops.token_linear(hidden, self.value_proj.weight, self.value_proj.bias, out_group=C // H)
+            amp = torch.is_autocast_enabled("cuda")
+            hm_rows = HEAD_MAJOR_ROWS and not amp and ops.token_linear_applies(hp, w)
+            own_value = not amp and ops.token_linear_applies(hidden, self.value_proj.weight)
+            hm_value = HEAD_MAJOR_VALUE and hm_rows and own_value
+            vp = self.value_proj
+            if own_value:  # the split-bf16 token GEMM (fp32 accuracy)
+                vws = ops.split_weight_cached(self, "value_proj", vp.weight)
+                value = (ops.token_linear(hidden, vp.weight, vp.bias, out_group=C // H, w_split=vws) if hm_value
+                         else ops.token_linear(hidden, vp.weight, vp.bias, w_split=vws).view(B, S, H, C // H))
             else:
-                value = self.value_proj(hidden).view(B, S, H, C // H)
-            rows = ops.token_linear(hp, w, b, out_group=36) if hm_rows else F.linear(hp, w, b)
+                value = vp(hidden).view(B, S, H, C // H)
+            if hm_rows:
+                if "ws_lanes" not in self._cat:
+                    self._cat["ws_lanes"] = ops.split_weight(w)
+                rows = ops.token_linear(hp, w, b, out_group=36, w_split=self._cat["ws_lanes"])
+            else:
+                rows = F.linear(hp, w, b)
             out = ops.ms_deform_attn_fused_lanes(value, level_hw, rows, H, head_major=hm_rows, value_head_major=hm_value,
                                                  slab_order=hm_rows)
         else:  # inference: one merged projection; softmax + location arithmetic fused into the kernel
@@ -172,7 +183,7 @@ class MSDeformAttn(nn.Module):
             w, b = self._offsets_logits_weight()
             ol = F.linear(hp, w, b)  # (B, S, 288): [offsets (H*L*P*2) | logits (H*L*P)] per token
             out = ops.ms_deform_attn_fused_packed(value, level_hw, ol, ref, H, L, P)
-        return self.output_proj(out)
+        return self.output_proj(out) if project else out
 
 
 class PixelDecoderEncoderLayer(nn.Module):
@@ -200,6 +211,19 @@ class PixelDecoderEncoderLayer(nn.Module):
             # bias + ReLU in the fc1 GEMM epilogue
             B_, S_, C_ = hidden.shape
             ln1, ln2 = self.self_attn_layer_norm, self.final_layer_norm
+            op = self.self_attn.output_proj
+            if (ops.token_linear_applies(hidden, op.weight) and ops.token_linear_applies(hidden, self.fc1.weight)
+                    and B_ * S_ * self.fc1.out_features * 4 < (1 << 31)):
+                # all four Linears on the split-bf16 token GEMM (fp32 accuracy): output_proj with the residual +
+                # LayerNorm in its epilogue, fc1 with bias + ReLU, fc2 with the residual + LayerNorm and the next layer's
+                # hidden + pos
+                a = self.self_attn(hidden, pos, ref, level_hw, hp, project=False)
+                hidden = ops.token_linear(a, op.weight, op.bias, residual=hidden, ln=(ln1.weight, ln1.bias, ln1.eps),
+                                          w_split=ops.split_weight_cached(self, "output_proj", op.weight))
+                f = ops.token_linear(hidden, self.fc1.weight, self.fc1.bias, relu=True,
+                                     w_split=ops.split_weight_cached(self, "fc1", self.fc1.weight))
+                return ops.token_linear(f, self.fc2.weight, self.fc2.bias, residual=hidden, ln=(ln2.weight, ln2.bias, ln2.eps),
+                                        pos=pos, w_split=ops.split_weight_cached(self, "fc2", self.fc2.weight))
             a = self.self_attn(hidden, pos, ref, level_hw, hp)
             hidden = ops.add_layernorm(a, hidden, ln1.weight, ln1.bias, ln1.eps)
             f = torch._addmm_activation(self.fc1.bias, hidden.reshape(B_ * S_, C_), self.fc1.weight.t(), use_gelu=False)
@@ -418,6 +442,14 @@ class MaskedCrossAttention(nn.Module):
 
     def project_kv(self, key_in, value_in):
         E = self.embed_dim
+        wk, wv = self.in_proj_weight[E:2 * E], self.in_proj_weight[2 * E:]
+        if (not torch.is_grad_enabled() and not torch.is_autocast_enabled("cuda") and ops.token_linear_applies(key_in, wk)
+                and ops.token_linear_applies(value_in, wv)):
+            # inference: the split-bf16 token GEMM (fp32 accuracy)
+            w = self.in_proj_weight
+            k = ops.token_linear(key_in, wk, self.in_proj_bias[E:2 * E], w_split=ops.split_weight_cached(self, "k", wk, base=w))
+            v = ops.token_linear(value_in, wv, self.in_proj_bias[2 * E:], w_split=ops.split_weight_cached(self, "v", wv, base=w))
+            return k, v
         # (up to B x 16384 tokens per level: in training the weight gradients of these two run on wm2f_token_wgrad_*)
         k = ops.linear_tokens(key_in, self.in_proj_weight[E:2 * E], self.in_proj_bias[E:2 * E])
         v = ops.linear_tokens(value_in, self.in_proj_weight[2 * E:], self.in_proj_bias[2 * E:])

@@ -7,6 +7,7 @@ RAISES if the tensors are not on a GPU or the library is missing -- there is no 
 from __future__ import annotations
 
 import ctypes
+import weakref
 from typing import Sequence
 
 import torch
@@ -892,20 +893,49 @@ def add_layernorm_train(x, residual, gamma, beta, eps: float, pos: torch.Tensor 
 
 
 def token_linear_applies(x: torch.Tensor, weight: torch.Tensor) -> bool:
-    """Shapes wm2f_token_linear_fwd is built for: fp32 on a GPU, N in {256, 288}, K a multiple of 64, x / out below 2 GiB."""
+    """Shapes token_linear is built for: fp32 on a GPU, N in {256, 288, 512, 768, 1024}, K a multiple of 32, x / out below
+    2 GiB (the fp32-MFMA kernel, split=False, additionally needs N in {256, 288} and K a multiple of 64)."""
     N, K = weight.shape
     M = x.numel() // max(K, 1)
-    return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and N in (256, 288) and K % 64 == 0
-            and x.shape[-1] == K and M * K * 4 < (1 << 31) and M * N * 4 < (1 << 31))
+    return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and N in (256, 288, 512, 768, 1024)
+            and K % 32 == 0 and x.shape[-1] == K and M * K * 4 < (1 << 31) and M * N * 4 < (1 << 31)
+            and N * K * 6 < (1 << 31))
+
+
+def split_weight(weight: torch.Tensor) -> torch.Tensor:
+    """The three bf16 pieces of an fp32 weight (N, K) in wm2f_token_linear_split_fwd's fragment order (N * K * 6 bytes,
+    returned as a uint8 tensor).  Callers that reuse a weight cache this per weight version (split_weight_cached)."""
+    weight = _req(weight, "weight")
+    N, K = weight.shape
+    ws = torch.empty(N * K * 6, device=weight.device, dtype=torch.uint8)
+    with torch.cuda.device(weight.device):
+        check(load().wm2f_token_linear_split_weight(_p(weight), _p(ws), N, K, _stream(weight)), "wm2f_token_linear_split_weight")
+    return ws
+
+
+def split_weight_cached(owner, name: str, weight: torch.Tensor, base: torch.Tensor | None = None) -> torch.Tensor:
+    """split_weight(weight), kept in owner.__dict__ under `name` and redone when the weight changes: another tensor (held by
+    weak reference: `base` when weight is a fresh view of it each call), another version, storage or device."""
+    ident = weight if base is None else base
+    c = owner.__dict__.setdefault("_wm2f_split", {})
+    key = (ident._version, weight.data_ptr(), weight.device, tuple(weight.shape))
+    hit = c.get(name)
+    if hit is None or hit[0]() is not ident or hit[1] != key:
+        hit = (weakref.ref(ident), key, split_weight(weight))
+        c[name] = hit
+    return hit[2]
 
 
 def token_linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, relu: bool = False, residual: torch.Tensor | None = None,
-                 ln: tuple | None = None, pos: torch.Tensor | None = None, out_group: int = 0):
+                 ln: tuple | None = None, pos: torch.Tensor | None = None, out_group: int = 0, split: bool = True,
+                 w_split: torch.Tensor | None = None):
     """Linear over tokens with its epilogue fused (inference, no autograd): x (..., K) @ weight (N, K)^T + bias, then
     optional ReLU, optional LayerNorm(value + residual) with ln = (gamma, beta, eps), and with `pos` (rows_per_image, N)
     additionally out + pos broadcast over the batch.  Returns out, or (out, out + pos).
     out_group = G > 0: the result comes back feature-group major, (N // G, *x.shape[:-1], G) -- with G = 36 K1's operand rows
-    head-major (ms_deform_attn_fused_lanes(..., head_major=True))."""
+    head-major (ms_deform_attn_fused_lanes(..., head_major=True)).
+    split=True (default): the split-bf16 kernel (wm2f_token_linear_split_fwd, fp32 accuracy on the bf16 matrix cores), with
+    `w_split` = split_weight(weight) if the caller keeps one; split=False: the fp32-MFMA kernel (wm2f_token_linear_fwd)."""
     x, weight, bias = _req(x, "x"), _req(weight, "weight"), _req(bias, "bias")
     N, K = weight.shape
     if x.shape[-1] != K or bias.shape != (N,):
@@ -930,10 +960,20 @@ def token_linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, relu
         if M % pos_rows:
             raise ValueError("token_linear: pos rows do not divide the token count")
         out_pos = torch.empty_like(out)
+    tag = f"token_linear_K{K}_N{N}" + ("_ln" if ln is not None else "")
     with torch.cuda.device(x.device):
-        check(_timed(f"token_linear_K{K}_N{N}" + ("_ln" if ln is not None else ""), x, lambda: load().wm2f_token_linear_fwd(
-            _p(x), _p(weight), _p(bias), _p(residual), _p(gamma), _p(beta), _p(pos), _p(out), _p(out_pos), M, K, N, 1 if relu else 0,
-            pos_rows, eps, int(out_group), _stream(x))), "wm2f_token_linear_fwd")
+        if split:
+            if w_split is None:
+                w_split = split_weight(weight)
+            elif w_split.dtype != torch.uint8 or w_split.numel() != N * K * 6 or w_split.device != x.device:
+                raise ValueError("token_linear: w_split is not split_weight(weight)")
+            check(_timed(tag + "_split", x, lambda: load().wm2f_token_linear_split_fwd(
+                _p(x), _p(w_split), _p(bias), _p(residual), _p(gamma), _p(beta), _p(pos), _p(out), _p(out_pos), M, K, N,
+                1 if relu else 0, pos_rows, eps, int(out_group), _stream(x))), "wm2f_token_linear_split_fwd")
+        else:
+            check(_timed(tag, x, lambda: load().wm2f_token_linear_fwd(
+                _p(x), _p(weight), _p(bias), _p(residual), _p(gamma), _p(beta), _p(pos), _p(out), _p(out_pos), M, K, N,
+                1 if relu else 0, pos_rows, eps, int(out_group), _stream(x))), "wm2f_token_linear_fwd")
     return (out, out_pos) if pos is not None else out
 
 
