@@ -366,6 +366,20 @@ int wm2f_token_linear_split_fwd(const void* x, const void* w_split, const void* 
                                 const void* ln_beta, const void* pos, void* out, void* out_plus_pos, int64_t M, int K, int N,
                                 int relu, int64_t pos_rows, float eps, int out_group, void* stream);
 
+/* wm2f_conv1x1_split_fwd: 1x1 convolution without padding, NCHW fp32, at fp32 accuracy on the bf16 matrix cores (the split
+ *                        arithmetic of wm2f_token_linear_split_fwd):  out (B, N, Ho, Wo) = epilogue(W (N, K) .
+ *                        x (B, K, Hi, Wi) sampled at (stride ho, stride wo)), Ho = (Hi - 1) / stride + 1, likewise Wo.  w_split =
+ *                        wm2f_token_linear_split_weight of W (N, K).  Epilogue, fixed by the arguments: bias == NULL: none;
+ *                        + bias[N]; relu != 0: max(., 0) after it; residual (B, N, Ho, Wo) != NULL: + residual before the ReLU
+ *                        (needs bias and relu).  K % 32 == 0, N % 64 == 0, stride 1 or 2, one image of x / out below 2 GiB.
+ *                        Deterministic; an image's output does not depend on B or on the other images.  config = -1: the
+ *                        kernel's choice of tile configuration; >= 0: that entry of its table (the same bits, another speed).
+ * wm2f_conv1x1_split_config: the tile configuration wm2f_conv1x1_split_fwd picks for (N, P = Ho * Wo, B) on n_cu CUs: an index
+ *                        into the kernel's table, -1 if none fits (for tests and profiles). */
+int wm2f_conv1x1_split_fwd(const void* x, const void* w_split, const void* bias, const void* residual, void* out, int B, int K,
+                           int N, int Hi, int Wi, int stride, int relu, int config, void* stream);
+int wm2f_conv1x1_split_config(int N, int P, int B, int n_cu);
+
 /* wm2f_token_wgrad_bf16: the weight / bias gradient of such a Linear (the backward autograd derives for nn.Linear; train
  *                        step of HF:1036-1103 under bf16 autocast):  dw (N, K) fp32 = dy (M, N)^T . x (M, K),
  *                        db (N) fp32 = column sums of dy (NULL: skipped); dy, x bf16 row-major, fp32 accumulation on the bf16

@@ -14,10 +14,21 @@ from torch import nn
 from . import ops
 
 
+def _infer_gpu(x: torch.Tensor) -> bool:
+    """Inference on the GPU in fp32 without autocast."""
+    return (not torch.is_grad_enabled()) and x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled("cuda")
+
+
 def _fused_ok(x: torch.Tensor) -> bool:
     """Inference on the GPU with a float4-friendly map: use the fused bias(+residual)+ReLU pass."""
-    return ((not torch.is_grad_enabled()) and x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled("cuda")
-            and (x.shape[-1] * x.shape[-2]) % 4 == 0)
+    return _infer_gpu(x) and (x.shape[-1] * x.shape[-2]) % 4 == 0
+
+
+def _split_1x1(conv: nn.Conv2d, x: torch.Tensor, w: torch.Tensor) -> bool:
+    """Inference 1x1 convolution that the split-bf16 kernel covers (ops.conv1x1, any map size)."""
+    return (ops.CONV1X1_SPLIT and _infer_gpu(x) and conv.kernel_size == (1, 1) and conv.padding == (0, 0)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.stride[0] == conv.stride[1]
+            and ops.conv1x1_applies(x, w, conv.stride[0]))
 
 
 def _folded(conv: nn.Conv2d, bn: nn.BatchNorm2d, cache: dict):
@@ -52,6 +63,10 @@ class ConvLayer(nn.Module):
             w, b = _folded(c, self.normalization, self._fold)
             if extra_bias is not None:
                 b = b + extra_bias
+            if _split_1x1(c, x, w) and (residual is None or relu):
+                # 1x1: one split-bf16 GEMM with bias (+ residual) + ReLU in its store
+                ws = ops.split_weight_cached(self, "conv", w.view(w.shape[0], w.shape[1]), base=w)
+                return ops.conv1x1(x, w, b, residual, relu, c.stride[0], w_split=ws)
             if _fused_ok(x):
                 y = torch.nn.functional.conv2d(x, w, None, c.stride, c.padding)
                 if (y.shape[-1] * y.shape[-2]) % 4 == 0:
@@ -81,8 +96,12 @@ class ShortCut(nn.Module):
     def folded_raw(self, x):
         """Inference: the shortcut convolution WITHOUT its folded bias, and that bias (the bottleneck adds it
         in its fused epilogue)."""
-        w, b = _folded(self.convolution, self.normalization, self._fold)
-        return torch.nn.functional.conv2d(x, w, None, self.convolution.stride), b
+        c = self.convolution
+        w, b = _folded(c, self.normalization, self._fold)
+        if _split_1x1(c, x, w):
+            ws = ops.split_weight_cached(self, "conv", w.view(w.shape[0], w.shape[1]), base=w)
+            return ops.conv1x1(x, w, None, stride=c.stride[0], w_split=ws), b
+        return torch.nn.functional.conv2d(x, w, None, c.stride), b
 
 
 class BottleNeckLayer(nn.Module):

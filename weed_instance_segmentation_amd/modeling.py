@@ -324,7 +324,7 @@ class Mask2FormerPixelDecoder(nn.Module):
             start = 0
             for lvl, x in enumerate(levels):
                 conv, gn = self.input_projections[lvl]
-                raw = F.conv2d(x, conv.weight, None, conv.stride, conv.padding)
+                raw = self._conv1x1(conv, x, f"in{lvl}", bias=False)
                 ops.group_norm_tokens_(raw, conv.bias, gn.num_groups, gn.weight, gn.bias, gn.eps, hidden, start)
                 start += level_hw[lvl][0] * level_hw[lvl][1]
         else:
@@ -348,14 +348,26 @@ class Mask2FormerPixelDecoder(nn.Module):
             if fast and feat.shape[-1] % 4 == 0 and feat.dtype == torch.float32:
                 # GroupNorm + upsample-add and GroupNorm + ReLU as one statistics pass and one fused pass each
                 gn_a, gn_l = adapter[1], layer[1]
-                out = ops.group_norm_act_(adapter[0](feat), gn_a.num_groups, gn_a.weight, gn_a.bias, gn_a.eps,
+                out = ops.group_norm_act_(self._conv1x1(adapter[0], feat, "adapter"), gn_a.num_groups, gn_a.weight, gn_a.bias, gn_a.eps,
                                           up=outs[-1].contiguous())
                 outs.append(ops.group_norm_act_(layer[0](out), gn_l.num_groups, gn_l.weight, gn_l.bias, gn_l.eps, relu=True))
                 continue
             lat = adapter(feat)
             out = lat + F.interpolate(outs[-1], size=lat.shape[-2:], mode="bilinear", align_corners=False)
             outs.append(layer(out))
+        if fast:
+            return self._conv1x1(self.mask_projection, outs[-1], "mask_projection"), outs[:3]
         return self.mask_projection(outs[-1]), outs[:3]
+
+    def _conv1x1(self, conv: nn.Conv2d, x: torch.Tensor, name: str, bias: bool = True) -> torch.Tensor:
+        """Inference: a 1x1 convolution on the split-bf16 kernel (ops.conv1x1) where it applies, else the module's own
+        convolution; bias=False leaves the module's bias out (a later pass adds it)."""
+        w = conv.weight
+        if (ops.CONV1X1_SPLIT and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
+                and conv.groups == 1 and ops.conv1x1_applies(x, w)):
+            ws = ops.split_weight_cached(self, name, w.view(w.shape[0], w.shape[1]), base=w)
+            return ops.conv1x1(x, w, conv.bias if bias else None, w_split=ws)
+        return F.conv2d(x, w, conv.bias if bias else None, conv.stride, conv.padding)
 
 
 class Mask2FormerPixelLevelModule(nn.Module):

@@ -977,6 +977,75 @@ def token_linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, relu
     return (out, out_pos) if pos is not None else out
 
 
+# The inference routes of the 1x1 convolutions (ResNet bottlenecks, pixel-decoder projections) take the split kernel while
+# this is True; False sends them through conv1x1(..., split=False), the library convolution plus bias_act_ (the accuracy
+# reference of the tests).
+CONV1X1_SPLIT = True
+
+
+def conv1x1_applies(x: torch.Tensor, weight: torch.Tensor, stride: int = 1) -> bool:
+    """Shapes wm2f_conv1x1_split_fwd is built for: fp32 NCHW on a GPU, weight (N, K, 1, 1) or (N, K) with K % 32 == 0 and
+    N % 64 == 0, stride 1 or 2, one image of x / out below 2 GiB, the split weight below 2 GiB."""
+    if x.dim() != 4 or weight.dim() not in (2, 4) or (weight.dim() == 4 and weight.shape[2:] != (1, 1)):
+        return False
+    N, K = int(weight.shape[0]), int(weight.shape[1])
+    _, C, H, W = x.shape
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and C == K and K % 32 == 0
+            and N % 64 == 0 and stride in (1, 2) and K * H * W * 4 < (1 << 31) and N * Ho * Wo * 4 < (1 << 31)
+            and N * K * 6 < (1 << 31))
+
+
+def conv1x1(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None, residual: torch.Tensor | None = None,
+            relu: bool = False, stride: int = 1, split: bool = True, w_split: torch.Tensor | None = None,
+            config: int = -1) -> torch.Tensor:
+    """1x1 convolution without padding, epilogue fused (inference, no autograd): act(conv(x, weight, stride) + bias
+    (+ residual)), x (B, K, H, W) fp32.  The residual epilogue needs bias and relu.
+    split=True: wm2f_conv1x1_split_fwd (fp32 accuracy on the bf16 matrix cores), with `w_split` = split_weight of the
+    weight seen as (N, K) if the caller keeps one; shapes outside conv1x1_applies take the split=False path.  config >= 0
+    forces an entry of the kernel's tile table (tests, tuning; the same bits), -1 lets the kernel choose.
+    split=False: F.conv2d, then bias_act_ (or the same in torch ops when Ho * Wo is not a multiple of 4)."""
+    if residual is not None and (bias is None or not relu):
+        raise ValueError("conv1x1: the residual epilogue is bias + residual + ReLU")
+    if relu and bias is None:
+        raise ValueError("conv1x1: the ReLU epilogues carry a bias")
+    N, K = int(weight.shape[0]), int(weight.shape[1])
+    if not split or not conv1x1_applies(x, weight, stride):
+        w4 = weight if weight.dim() == 4 else weight.view(N, K, 1, 1)
+        y = torch.nn.functional.conv2d(x, w4, None, stride)
+        if bias is None:
+            return y
+        if (y.shape[-1] * y.shape[-2]) % 4 == 0:
+            return bias_act_(y, bias, residual, relu)
+        y = y + bias[None, :, None, None]
+        if residual is not None:
+            y = y + residual
+        return torch.relu(y) if relu else y
+    x = _req(x, "x")
+    w2 = _req(weight.reshape(N, K), "weight")
+    B, _, H, W = x.shape
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if bias is not None:
+        bias = _req(bias, "bias")
+        if bias.shape != (N,):
+            raise ValueError(f"conv1x1: bias {tuple(bias.shape)} for {N} channels")
+    if residual is not None:
+        residual = _req(residual, "residual")
+        if residual.shape != (B, N, Ho, Wo):
+            raise ValueError(f"conv1x1: residual {tuple(residual.shape)}, output ({B}, {N}, {Ho}, {Wo})")
+    if w_split is None:
+        w_split = split_weight(w2)
+    elif w_split.dtype != torch.uint8 or w_split.numel() != N * K * 6 or w_split.device != x.device:
+        raise ValueError("conv1x1: w_split is not split_weight(weight)")
+    out = torch.empty(B, N, Ho, Wo, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        check(_timed(f"conv1x1_K{K}_N{N}_P{Ho * Wo}", x, lambda: load().wm2f_conv1x1_split_fwd(
+            _p(x), _p(w_split), _p(bias), _p(residual), _p(out), B, K, N, H, W, int(stride), 1 if relu else 0, int(config),
+            _stream(x))),
+            "wm2f_conv1x1_split_fwd")
+    return out
+
+
 def token_wgrad_applies(dy: torch.Tensor, x: torch.Tensor) -> bool:
     """Shapes wm2f_token_wgrad_bf16 / _f32 are built for: both operands bf16 or both fp32 on a GPU, feature counts multiples
     of 8, operands below 2 GiB."""
