@@ -380,6 +380,20 @@ int wm2f_conv1x1_split_fwd(const void* x, const void* w_split, const void* bias,
                            int N, int Hi, int Wi, int stride, int relu, int config, void* stream);
 int wm2f_conv1x1_split_config(int N, int P, int B, int n_cu);
 
+/* wm2f_conv3x3_split_fwd: 3x3 convolution with padding 1, NCHW fp32, at fp32 accuracy on the bf16 matrix cores (the split
+ *                        arithmetic of wm2f_conv1x1_split_fwd):  out (B, N, Ho, Wo) = epilogue(conv3x3(x (B, Cin,
+ *                        Hi, Wi), W (N, Cin, 3, 3)), stride 1 or 2), Ho = (Hi - 1) / stride + 1, likewise Wo.  w_split =
+ *                        wm2f_token_linear_split_weight of the tap-major weight W.permute(0, 2, 3, 1) seen as (N, 9 Cin).
+ *                        Epilogue: bias == NULL: none; + bias[N]; relu != 0: max(., 0) after it (needs bias).  Cin % 32 == 0,
+ *                        N % 64 == 0, one image of x / out below 2 GiB.  Deterministic, no split-K: an image's output does not
+ *                        depend on B, on the other images or on config.  config = -1: the kernel's choice of tile
+ *                        configuration; >= 0: that entry of its table (the same bits, another speed).
+ * wm2f_conv3x3_split_config: the tile configuration wm2f_conv3x3_split_fwd picks for (N, P = Ho * Wo, B) on n_cu CUs: an index
+ *                        into the kernel's table, -1 if none fits (for tests and profiles). */
+int wm2f_conv3x3_split_fwd(const void* x, const void* w_split, const void* bias, void* out, int B, int Cin, int N, int Hi,
+                           int Wi, int stride, int relu, int config, void* stream);
+int wm2f_conv3x3_split_config(int N, int P, int B, int n_cu);
+
 /* wm2f_token_wgrad_bf16: the weight / bias gradient of such a Linear (the backward autograd derives for nn.Linear; train
  *                        step of HF:1036-1103 under bf16 autocast):  dw (N, K) fp32 = dy (M, N)^T . x (M, K),
  *                        db (N) fp32 = column sums of dy (NULL: skipped); dy, x bf16 row-major, fp32 accumulation on the bf16

@@ -31,6 +31,13 @@ def _split_1x1(conv: nn.Conv2d, x: torch.Tensor, w: torch.Tensor) -> bool:
             and ops.conv1x1_applies(x, w, conv.stride[0]))
 
 
+def _split_3x3(conv: nn.Conv2d, x: torch.Tensor, w: torch.Tensor) -> bool:
+    """Inference 3x3 convolution that the split-bf16 kernel covers (ops.conv3x3, any map size)."""
+    return (ops.CONV3X3_SPLIT and _infer_gpu(x) and conv.kernel_size == (3, 3) and conv.padding == (1, 1)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.stride[0] == conv.stride[1]
+            and ops.conv3x3_applies(x, w, conv.stride[0]))
+
+
 def _folded(conv: nn.Conv2d, bn: nn.BatchNorm2d, cache: dict):
     """Inference-time BatchNorm folding: conv(x, w) * g/sqrt(v+eps) + (b - m*g/sqrt(v+eps)) == conv(x, w', b').
     Cached per (weight / statistics version), so the fold is recomputed only after the parameters change."""
@@ -67,6 +74,11 @@ class ConvLayer(nn.Module):
                 # 1x1: one split-bf16 GEMM with bias (+ residual) + ReLU in its store
                 ws = ops.split_weight_cached(self, "conv", w.view(w.shape[0], w.shape[1]), base=w)
                 return ops.conv1x1(x, w, b, residual, relu, c.stride[0], w_split=ws)
+            if _split_3x3(c, x, w) and residual is None and relu:
+                # 3x3: one split-bf16 implicit GEMM with bias + ReLU in its store; the folded w is the cache's identity,
+                # so a new fold (weight or BatchNorm version) re-splits
+                ws = ops.split_weight_cached(self, "conv3x3", w, tap_major=True)
+                return ops.conv3x3(x, w, b, True, c.stride[0], w_split=ws)
             if _fused_ok(x):
                 y = torch.nn.functional.conv2d(x, w, None, c.stride, c.padding)
                 if (y.shape[-1] * y.shape[-2]) % 4 == 0:

@@ -350,7 +350,7 @@ class Mask2FormerPixelDecoder(nn.Module):
                 gn_a, gn_l = adapter[1], layer[1]
                 out = ops.group_norm_act_(self._conv1x1(adapter[0], feat, "adapter"), gn_a.num_groups, gn_a.weight, gn_a.bias, gn_a.eps,
                                           up=outs[-1].contiguous())
-                outs.append(ops.group_norm_act_(layer[0](out), gn_l.num_groups, gn_l.weight, gn_l.bias, gn_l.eps, relu=True))
+                outs.append(ops.group_norm_act_(self._conv3x3(layer[0], out, f"layer_{k}"), gn_l.num_groups, gn_l.weight, gn_l.bias, gn_l.eps, relu=True))
                 continue
             lat = adapter(feat)
             out = lat + F.interpolate(outs[-1], size=lat.shape[-2:], mode="bilinear", align_corners=False)
@@ -368,6 +368,15 @@ class Mask2FormerPixelDecoder(nn.Module):
             ws = ops.split_weight_cached(self, name, w.view(w.shape[0], w.shape[1]), base=w)
             return ops.conv1x1(x, w, conv.bias if bias else None, w_split=ws)
         return F.conv2d(x, w, conv.bias if bias else None, conv.stride, conv.padding)
+
+    def _conv3x3(self, conv: nn.Conv2d, x: torch.Tensor, name: str) -> torch.Tensor:
+        """Inference: a 3x3 convolution (padding 1, no bias) on the split-bf16 kernel (ops.conv3x3) where it applies, else
+        the module's own convolution."""
+        w = conv.weight
+        if (ops.CONV3X3_SPLIT and conv.bias is None and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
+                and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and ops.conv3x3_applies(x, w)):
+            return ops.conv3x3(x, w, w_split=ops.split_weight_cached(self, name, w, tap_major=True))
+        return conv(x)
 
 
 class Mask2FormerPixelLevelModule(nn.Module):

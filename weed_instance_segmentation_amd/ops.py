@@ -913,17 +913,26 @@ def split_weight(weight: torch.Tensor) -> torch.Tensor:
     return ws
 
 
-def split_weight_cached(owner, name: str, weight: torch.Tensor, base: torch.Tensor | None = None) -> torch.Tensor:
+def split_weight_cached(owner, name: str, weight: torch.Tensor, base: torch.Tensor | None = None,
+                        tap_major: bool = False) -> torch.Tensor:
     """split_weight(weight), kept in owner.__dict__ under `name` and redone when the weight changes: another tensor (held by
-    weak reference: `base` when weight is a fresh view of it each call), another version, storage or device."""
+    weak reference: `base` when weight is a fresh view of it each call), another version, storage or device.
+    tap_major=True: weight is a 3x3 kernel (N, Cin, 3, 3), split as conv3x3 reads it (split_weight_3x3)."""
     ident = weight if base is None else base
     c = owner.__dict__.setdefault("_wm2f_split", {})
     key = (ident._version, weight.data_ptr(), weight.device, tuple(weight.shape))
     hit = c.get(name)
     if hit is None or hit[0]() is not ident or hit[1] != key:
-        hit = (weakref.ref(ident), key, split_weight(weight))
+        hit = (weakref.ref(ident), key, split_weight_3x3(weight) if tap_major else split_weight(weight))
         c[name] = hit
     return hit[2]
+
+
+def split_weight_3x3(weight: torch.Tensor) -> torch.Tensor:
+    """The split of a 3x3 kernel (N, Cin, 3, 3) for wm2f_conv3x3_split_fwd: split_weight of its tap-major reorder
+    (N, 3, 3, Cin) seen as (N, 9 Cin), so that column (3 dy + dx) Cin + c is tap (dy, dx) of channel c."""
+    N = int(weight.shape[0])
+    return split_weight(weight.permute(0, 2, 3, 1).reshape(N, -1).contiguous())
 
 
 def token_linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, relu: bool = False, residual: torch.Tensor | None = None,
@@ -1043,6 +1052,64 @@ def conv1x1(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = N
             _p(x), _p(w_split), _p(bias), _p(residual), _p(out), B, K, N, H, W, int(stride), 1 if relu else 0, int(config),
             _stream(x))),
             "wm2f_conv1x1_split_fwd")
+    return out
+
+
+# The inference routes of the 3x3 convolutions (ResNet conv2, the pixel decoder's FPN layer_1) take the split kernel while
+# this is True; False sends them through conv3x3(..., split=False), the library convolution plus bias_act_ (the accuracy
+# reference of the tests).
+CONV3X3_SPLIT = True
+
+
+def conv3x3_applies(x: torch.Tensor, weight: torch.Tensor, stride: int = 1) -> bool:
+    """Shapes wm2f_conv3x3_split_fwd is built for: fp32 NCHW on a GPU, weight (N, Cin, 3, 3) with Cin % 32 == 0 and
+    N % 64 == 0, stride 1 or 2 (padding 1, dilation 1, one group), one image of x / out below 2 GiB, the split weight
+    below 2 GiB."""
+    if x.dim() != 4 or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        return False
+    N, C = int(weight.shape[0]), int(weight.shape[1])
+    _, K, H, W = x.shape
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and C == K and K % 32 == 0
+            and N % 64 == 0 and stride in (1, 2) and K * H * W * 4 < (1 << 31) and N * Ho * Wo * 4 < (1 << 31)
+            and N * 9 * K * 6 < (1 << 31))
+
+
+def conv3x3(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None, relu: bool = False, stride: int = 1,
+            split: bool = True, w_split: torch.Tensor | None = None, config: int = -1) -> torch.Tensor:
+    """3x3 convolution with padding 1, epilogue fused (inference, no autograd): act(conv(x, weight, stride) + bias),
+    x (B, Cin, H, W) fp32, weight (N, Cin, 3, 3).  The ReLU epilogue needs a bias.
+    split=True: wm2f_conv3x3_split_fwd (fp32 accuracy on the bf16 matrix cores), with `w_split` = split_weight_3x3(weight)
+    if the caller keeps one; shapes outside conv3x3_applies take the split=False path.  config >= 0 forces an entry of the
+    kernel's tile table (tests, tuning; the same bits), -1 lets the kernel choose.
+    split=False: F.conv2d, then bias_act_ (or the same in torch ops when Ho * Wo is not a multiple of 4)."""
+    if relu and bias is None:
+        raise ValueError("conv3x3: the ReLU epilogue carries a bias")
+    if not split or not conv3x3_applies(x, weight, stride):
+        y = torch.nn.functional.conv2d(x, weight, None, stride, 1)
+        if bias is None:
+            return y
+        if (y.shape[-1] * y.shape[-2]) % 4 == 0:
+            return bias_act_(y, bias, None, relu)
+        y = y + bias[None, :, None, None]
+        return torch.relu(y) if relu else y
+    x = _req(x, "x")
+    N, Cin = int(weight.shape[0]), int(weight.shape[1])
+    B, _, H, W = x.shape
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if bias is not None:
+        bias = _req(bias, "bias")
+        if bias.shape != (N,):
+            raise ValueError(f"conv3x3: bias {tuple(bias.shape)} for {N} channels")
+    if w_split is None:
+        w_split = split_weight_3x3(_req(weight, "weight"))
+    elif w_split.dtype != torch.uint8 or w_split.numel() != N * 9 * Cin * 6 or w_split.device != x.device:
+        raise ValueError("conv3x3: w_split is not split_weight_3x3(weight)")
+    out = torch.empty(B, N, Ho, Wo, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        check(_timed(f"conv3x3_C{Cin}_N{N}_P{Ho * Wo}", x, lambda: load().wm2f_conv3x3_split_fwd(
+            _p(x), _p(w_split), _p(bias), _p(out), B, Cin, N, H, W, int(stride), 1 if relu else 0, int(config), _stream(x))),
+            "wm2f_conv3x3_split_fwd")
     return out
 
 
