@@ -35,6 +35,7 @@ extern "C" {
 #define WM2F_BF16 1
 #define WM2F_I32 2 /* integer maps of the mAP entry points */
 #define WM2F_U8 3
+#define WM2F_U16 4 /* semantic maps of the CCL entry points */
 
 #define WM2F_OK 0
 #define WM2F_EINVAL (-1)      /* bad argument / unsupported shape */
@@ -574,6 +575,41 @@ int wm2f_resize_normalize_u8(const uint8_t* images, int64_t images_bytes, const 
 int wm2f_resize_nearest_labels(const void* maps, int dtype, int64_t n_map_elems, const int64_t* desc,
                                const int32_t* tables, int64_t n_table, int32_t* out, uint8_t* present, int B, int Hp,
                                int Wp, int ignore_index, void* stream);
+
+/* ---- connected components of class maps ------------------------------------------------
+ * The cv2 steps of the reference's dataset loaders (datasets/pheno_bench/dataset.py:48-135, crop_weed
+ * dataset_from_png_annotations.py:48-131): cv2.resize(INTER_NEAREST) of the mask, cv2.connectedComponents per class,
+ * the instance map painted with ids 1, 2, ... in (class, component) order.
+ * Two pixels join when they are 8-neighbours with the same nonzero class.  Components are numbered the way OpenCV's
+ * block-based 8-connectivity labelling numbers them: by (class, first 2x2 block), where the first block of a component
+ * is the minimum of (r >> 1) * ceil(W / 2) + (c >> 1) over its pixels.  The result does not depend on the schedule.
+ * workspace: wm2f_ccl_workspace(H, W) bytes (-1 for a bad size): parent, class, slot, root list, each (H, W) int32,
+ *     and a counter.
+ * wm2f_ccl_label: class map of the (H, W) output: pixel (y, x) reads source pixel (ty[y], tx[x]) of the (src_H, src_W)
+ *     map (ty / tx int32 device tables, clamped; both null = identity, then the sizes must agree) and maps it by mode:
+ *       WM2F_CCL_VALUE   the value itself (src_dtype WM2F_U8, WM2F_U16 or WM2F_I32), 0 = background;
+ *       WM2F_CCL_BINARY  1 where the value is nonzero;
+ *       WM2F_CCL_RGB     (src_H, src_W, 3) uint8: 1 + the index of the first of the n_colors HOST rgb triples in
+ *                        `colors` that equals the pixel, 0 if none (n_colors <= WM2F_CCL_MAX_COLORS).
+ *     Then labels the components; count (1 int32) receives their number n (cleared on the stream first).
+ * wm2f_ccl_keys: keys (n) int64 = class * 2^32 + first block of each component, in the workspace's root-list order;
+ *     the keys are distinct.  The caller sorts them (ascending) into `order` (n int64 indices into that list).
+ * wm2f_ccl_paint: the component at sorted position i gets id i + 1 (i + 2 from id 255 on when skip_255) and
+ *     out (H, W) int32 = its id, `background` outside every component; comp_class (n) int32, if not null, = the class
+ *     of the component at sorted position i.
+ * wm2f_resize_nearest: dst (H, W) = src (src_H, src_W) pixels of elem_bytes (1, 2, 3 or 4) bytes at (ty[y], tx[x]). */
+#define WM2F_CCL_VALUE 0
+#define WM2F_CCL_BINARY 1
+#define WM2F_CCL_RGB 2
+#define WM2F_CCL_MAX_COLORS 16
+int64_t wm2f_ccl_workspace(int H, int W);
+int wm2f_ccl_label(const void* src, int mode, int src_dtype, int src_H, int src_W, const int32_t* ty, const int32_t* tx,
+                   const uint8_t* colors, int n_colors, int H, int W, void* workspace, int32_t* count, void* stream);
+int wm2f_ccl_keys(const void* workspace, int n, int H, int W, int64_t* keys, void* stream);
+int wm2f_ccl_paint(void* workspace, const int64_t* order, int n, int H, int W, int skip_255, int background, int32_t* out,
+                   int32_t* comp_class, void* stream);
+int wm2f_resize_nearest(const void* src, int elem_bytes, int src_H, int src_W, const int32_t* ty, const int32_t* tx,
+                        void* dst, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }

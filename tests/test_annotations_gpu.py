@@ -1,0 +1,294 @@
+"""GPU instance maps from semantic masks against the CPU restatement of the reference loaders'
+steps 2-4 (scipy labels renumbered by OpenCV's first-block rule), bit for bit, dicts included.  Needs an MI355X (-m gpu)."""
+import numpy as np
+import pytest
+import torch
+
+from test_annotations_cpu import restate_cc, restate_color, restate_resize, restate_semantic
+
+pytestmark = pytest.mark.gpu
+
+CROPWEED = {"crop": {"color": [0, 255, 0], "id": 0}, "weed": {"color": [255, 0, 0], "id": 1}}
+
+
+@pytest.fixture(scope="module")
+def A():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from weed_instance_segmentation_amd import annotations
+    return annotations
+
+
+def _dev(a: np.ndarray) -> torch.Tensor:
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _check_semantic(A, sem: np.ndarray, dsize=None):
+    inst, d = A.semantic_to_instance_map(_dev(sem), dsize)
+    exp, exp_d = restate_semantic(sem, dsize)
+    assert inst.is_cuda and inst.dtype == torch.int32
+    got = inst.cpu().numpy()
+    assert got.shape == exp.shape
+    bad = np.argwhere(got != exp)
+    assert bad.size == 0, f"{len(bad)} pixels differ, first at {tuple(bad[0])}: {got[tuple(bad[0])]} vs {exp[tuple(bad[0])]}"
+    assert d == exp_d
+    assert all(type(k) is int and type(v) is int for k, v in d.items())
+    return got, d
+
+
+def _random_classes(rng, shape, density, n_classes, dtype=np.uint16):
+    fg = rng.random(shape) < density
+    return np.where(fg, rng.integers(1, n_classes + 1, shape), 0).astype(dtype)
+
+
+# ------------------------------------------------------------------------------------------- class maps
+@pytest.mark.parametrize("density", [0.05, 0.3, 0.55, 0.8, 1.0])
+def test_random_uint16_maps(A, density):
+    rng = np.random.default_rng(int(density * 100))
+    _check_semantic(A, _random_classes(rng, (300, 417), density, 4))
+
+
+def test_random_blobs_1024(A):
+    """Coarse blobs (upsampled noise): components of all sizes crossing many tile borders."""
+    rng = np.random.default_rng(7)
+    coarse = _random_classes(rng, (64, 64), 0.6, 3)
+    _check_semantic(A, np.kron(coarse, np.ones((16, 16), np.uint16))[:1024, :1024])
+    fine = _random_classes(rng, (256, 256), 0.5, 2)
+    _check_semantic(A, np.kron(fine, np.ones((4, 4), np.uint16)))
+
+
+def test_checkerboard_is_one_component(A):
+    yy, xx = np.mgrid[0:200, 0:333]
+    sem = ((yy + xx) % 2 == 0).astype(np.uint16)
+    got, d = _check_semantic(A, sem)
+    assert d == {1: 1}
+
+
+def test_diagonals_through_tile_corners(A):
+    H = W = 256
+    sem = np.zeros((H, W), np.uint16)
+    for k in range(-W, W, 32):
+        for y in range(H):
+            if 0 <= y + k < W:
+                sem[y, y + k] = 1  # main diagonals through every tile corner
+            if 0 <= W - 1 - y + k < W:
+                sem[y, W - 1 - y + k] = 2  # anti-diagonals
+    _check_semantic(A, sem)
+    # isolated diagonal pairs that touch only across a tile corner
+    sem = np.zeros((128, 128), np.uint16)
+    for c in (32, 64, 96):
+        sem[c - 1, c - 1] = sem[c, c] = 3
+        sem[c - 1, c + 8] = sem[c, c + 7] = 3  # anti-diagonal pair across the row border
+        sem[c + 8, c - 1] = sem[c + 7, c] = 3  # anti-diagonal pair across the column border
+    got, d = _check_semantic(A, sem)
+    assert len(d) == 9
+
+
+def test_serpentine_spans_many_tiles(A):
+    H = W = 1024
+    sem = np.zeros((H, W), np.uint16)
+    sem[::4, 1:W - 1] = 5
+    for i, y in enumerate(range(0, H - 4, 4)):
+        x = W - 2 if i % 2 == 0 else 1
+        sem[y:y + 5, x] = 5
+    got, d = _check_semantic(A, sem)
+    assert d == {1: 5}
+
+
+def test_spiral(A):
+    n = 515
+    sem = np.zeros((n, n), np.uint16)
+    top, left, bottom, right = 0, 0, n - 1, n - 1
+    while top <= bottom and left <= right:
+        sem[top, left:right + 1] = 9
+        sem[top:bottom + 1, right] = 9
+        sem[bottom, left:right + 1] = 9
+        if left + 2 <= right:
+            sem[top + 2:bottom + 1, left] = 9
+        sem[top + 2, left:left + 3] = 9
+        top, left, bottom, right = top + 2, left + 2, bottom - 2, right - 2
+    _check_semantic(A, sem)
+
+
+def test_all_background_and_all_one_class(A):
+    inst, d = A.semantic_to_instance_map(_dev(np.zeros((70, 90), np.uint16)))
+    assert d == {} and bool((inst == 255).all())
+    got, d = _check_semantic(A, np.full((70, 90), 3, np.uint16))
+    assert d == {1: 3} and (got == 1).all()
+
+
+@pytest.mark.parametrize("shape", [(1, 1), (1, 777), (777, 1), (33, 65), (767, 1023), (1024, 1024)])
+def test_sizes(A, shape):
+    rng = np.random.default_rng(shape[0] * 7 + shape[1])
+    _check_semantic(A, _random_classes(rng, shape, 0.5, 3))
+
+
+def test_more_than_254_components_skip_255(A):
+    sem = np.zeros((64, 128), np.uint16)
+    sem[::3, ::3] = 1
+    sem[1::3, 1::6] = 2
+    got, d = _check_semantic(A, sem)
+    assert len(d) >= 300 and 255 not in d and 255 not in np.unique(got[sem > 0])
+
+
+def test_large_class_values(A):
+    rng = np.random.default_rng(3)
+    sem = _random_classes(rng, (200, 300), 0.5, 3)
+    sem = np.array([0, 1000, 65535, 7], np.uint16)[sem]
+    got, d = _check_semantic(A, sem)
+    assert set(d.values()) == {7, 1000, 65535}
+
+
+def test_block_order_across_tile_border(A):
+    """Two single pixels on one block row, in different tiles: the lower-left one comes first (cv2), not the upper-right
+    one that raster order of first pixels would put first (scipy)."""
+    sem = np.zeros((64, 64), np.uint16)
+    sem[32, 33] = 1  # tile column 1, block (16, 16)
+    sem[33, 30] = 1  # tile column 0, block (16, 15)
+    got, d = _check_semantic(A, sem)
+    assert got[33, 30] == 1 and got[32, 33] == 2
+
+
+def test_uint8_and_int32_inputs(A):
+    rng = np.random.default_rng(11)
+    sem = _random_classes(rng, (150, 170), 0.5, 5, np.uint8)
+    a, da = A.semantic_to_instance_map(_dev(sem))
+    b, db = A.semantic_to_instance_map(_dev(sem.astype(np.int32)))
+    exp, exp_d = restate_semantic(sem)
+    assert np.array_equal(a.cpu().numpy(), exp) and np.array_equal(b.cpu().numpy(), exp) and da == db == exp_d
+
+
+def test_two_runs_identical(A):
+    rng = np.random.default_rng(5)
+    sem = _dev(_random_classes(rng, (1024, 1024), 0.55, 3))
+    a, da = A.semantic_to_instance_map(sem)
+    b, db = A.semantic_to_instance_map(sem)
+    assert torch.equal(a, b) and da == db
+
+
+# ------------------------------------------------------------------------------------------- resize fused in
+@pytest.mark.parametrize("src,dsize", [((1488, 1984), (768, 1024)), ((430, 600), (426, 594)), ((100, 77), (231, 160))])
+def test_semantic_with_resize(A, src, dsize):
+    rng = np.random.default_rng(src[0])
+    coarse = _random_classes(rng, (src[0] // 8 + 1, src[1] // 8 + 1), 0.5, 3)
+    sem = np.kron(coarse, np.ones((8, 8), np.uint16))[:src[0], :src[1]]
+    sem = np.ascontiguousarray(sem ^ (rng.random(src) < 0.05).astype(np.uint16))  # single-pixel detail
+    _check_semantic(A, sem, dsize)
+
+
+def test_resize_nearest_matches_formula(A):
+    rng = np.random.default_rng(2)
+    for dt in (np.uint8, np.uint16, np.int32):
+        m = rng.integers(0, 255, (1488, 999)).astype(dt)
+        got = A.resize_nearest(_dev(m), (1024, 687))
+        assert got.dtype == _dev(m).dtype
+        assert np.array_equal(got.cpu().numpy(), restate_resize(m, (1024, 687)))
+    rgb = rng.integers(0, 256, (430, 333, 3)).astype(np.uint8)
+    got = A.resize_nearest(_dev(rgb), (320, 426))
+    assert np.array_equal(got.cpu().numpy(), restate_resize(rgb, (320, 426)))
+
+
+# ------------------------------------------------------------------------------------------- colour masks
+def _colour_mask(rng, shape):
+    palette = np.array([[0, 0, 0], [0, 255, 0], [255, 0, 0], [0, 254, 0], [10, 20, 30]], np.uint8)
+    coarse = rng.choice(5, size=(shape[0] // 4 + 1, shape[1] // 4 + 1), p=[0.4, 0.25, 0.25, 0.05, 0.05])
+    idx = np.kron(coarse, np.ones((4, 4), np.int64))[:shape[0], :shape[1]]
+    idx = np.where(rng.random(shape) < 0.03, rng.integers(0, 3, shape), idx)
+    return np.ascontiguousarray(palette[idx])
+
+
+@pytest.mark.parametrize("dsize", [None, (640, 480)])
+def test_color_mask(A, dsize):
+    rng = np.random.default_rng(9)
+    rgb = _colour_mask(rng, (966, 1296))
+    inst, d = A.color_mask_to_instance_map(_dev(rgb), CROPWEED, dsize)
+    exp, exp_d = restate_color(rgb, CROPWEED, dsize)
+    assert np.array_equal(inst.cpu().numpy(), exp) and d == exp_d
+    assert set(d.values()) <= {0, 1}
+
+
+# ------------------------------------------------------------------------------------------- connectedComponents
+def test_connected_components_contract(A):
+    rng = np.random.default_rng(4)
+    m = (rng.random((513, 700)) < 0.45).astype(np.uint8) * 255
+    n, lab = A.connected_components(_dev(m))
+    exp_n, exp = restate_cc(m)
+    assert n == exp_n and lab.dtype == torch.int32 and np.array_equal(lab.cpu().numpy(), exp)
+    assert exp_n > 300  # no 255 skip in cv2's own numbering
+    n, lab = A.connected_components(_dev(np.zeros((5, 5), np.uint8)))
+    assert n == 1 and int(lab.abs().sum()) == 0
+    hand = np.array([[0, 0, 0, 0, 0, 1], [1, 0, 0, 0, 0, 0]], np.uint8)
+    n, lab = A.connected_components(_dev(hand))
+    assert n == 3 and lab[1, 0] == 1 and lab[0, 5] == 2
+
+
+# ------------------------------------------------------------------------------------------- datasets end to end
+def _save(path, arr):
+    from PIL import Image
+    Image.fromarray(arr).save(path)
+
+
+def _expected_item(proc, image_path, mask_restated, id_map):
+    from PIL import Image
+    image = Image.open(image_path).convert("RGB")
+    w, h = image.size
+    s = 256 / max(w, h)
+    image = image.resize((int(w * s), int(h * s)), resample=Image.BILINEAR)
+    return proc(images=[image], segmentation_maps=[mask_restated], instance_id_to_semantic_id=id_map,
+                return_tensors="pt", ignore_index=255)
+
+
+def _compare_item(item, inp, exp_map, exp_d):
+    assert isinstance(item["original_map"], np.ndarray) and item["original_map"].dtype == np.int32
+    assert np.array_equal(item["original_map"], exp_map)
+    assert item["id_to_semantic"] == exp_d
+    assert item["target_size"] == exp_map.shape
+    assert torch.equal(item["pixel_values"].cpu(), inp["pixel_values"][0].cpu())
+    assert torch.equal(item["mask_labels"].cpu(), inp["mask_labels"][0].cpu())
+    assert torch.equal(item["class_labels"].cpu(), inp["class_labels"][0].cpu())
+
+
+def test_pheno_bench_dataset_end_to_end(A, tmp_path):
+    from weed_instance_segmentation_amd import Mask2FormerImageProcessor
+    proc = Mask2FormerImageProcessor(size={"height": 256, "width": 256})
+    rng = np.random.default_rng(21)
+    (tmp_path / "img").mkdir()
+    (tmp_path / "ann").mkdir()
+    for i, (H, W) in enumerate([(300, 410), (330, 250)]):
+        _save(str(tmp_path / "img" / f"t{i}.png"), rng.integers(0, 256, (H, W, 3)).astype(np.uint8))
+        coarse = _random_classes(rng, (H // 24 + 1, W // 24 + 1), 0.35, 3)
+        sem = np.ascontiguousarray(np.kron(coarse, np.ones((24, 24), np.uint16))[:H, :W] * np.uint16(300))
+        _save(str(tmp_path / "ann" / f"t{i}.png"), sem)
+    ds = A.PhenoBenchDataset(str(tmp_path / "img"), str(tmp_path / "ann"), proc, {}, max_input_dim=256)
+    assert len(ds) == 2
+    for i in range(2):
+        item = ds[i]
+        img_path, mask_path = ds.valid_files[i]
+        sem = A._read_semantic_png(mask_path)
+        assert sem.dtype == np.uint16 and sem.max() >= 300
+        H, W = sem.shape
+        s = 256 / max(H, W)
+        exp_map, exp_d = restate_semantic(sem, (int(W * s), int(H * s)))
+        assert len(exp_d) > 1
+        _compare_item(item, _expected_item(proc, img_path, exp_map, exp_d), exp_map, exp_d)
+
+
+def test_crop_weed_dataset_end_to_end(A, tmp_path):
+    from weed_instance_segmentation_amd import Mask2FormerImageProcessor
+    proc = Mask2FormerImageProcessor(size={"height": 256, "width": 256})
+    rng = np.random.default_rng(22)
+    (tmp_path / "img").mkdir()
+    (tmp_path / "ann").mkdir()
+    H, W = 288, 384
+    _save(str(tmp_path / "img" / "001_image.png"), rng.integers(0, 256, (H, W, 3)).astype(np.uint8))
+    palette = np.array([[0, 0, 0], [0, 255, 0], [255, 0, 0]], np.uint8)
+    coarse = rng.choice(3, size=(H // 32, W // 32), p=[0.6, 0.2, 0.2])
+    rgb = np.ascontiguousarray(palette[np.kron(coarse, np.ones((32, 32), np.int64))])
+    _save(str(tmp_path / "ann" / "001_annotation.png"), rgb)
+    label2id = {"crop": 0, "weed": 1}
+    ds = A.CropWeedDataset(str(tmp_path / "img"), str(tmp_path / "ann"), proc, label2id, max_input_dim=256)
+    item = ds[0]
+    s = 256 / max(H, W)
+    exp_map, exp_d = restate_color(rgb, CROPWEED, (int(W * s), int(H * s)))
+    assert len(exp_d) > 1
+    _compare_item(item, _expected_item(proc, ds.valid_files[0][0], exp_map, exp_d), exp_map, exp_d)

@@ -18,6 +18,9 @@ WM2F_F32 = 0
 WM2F_BF16 = 1
 WM2F_I32 = 2
 WM2F_U8 = 3
+WM2F_U16 = 4
+WM2F_CCL_VALUE, WM2F_CCL_BINARY, WM2F_CCL_RGB = 0, 1, 2
+WM2F_CCL_MAX_COLORS = 16
 # return codes of include/wm2f.h
 WM2F_OK, WM2F_EINVAL, WM2F_EUNSUPPORTED, WM2F_ELAUNCH = 0, -1, -2, -3
 
@@ -102,6 +105,11 @@ SIGNATURES = {
     "wm2f_resize_normalize_u8": (c_int, [_P, c_int64, POINTER(c_int64), _P, c_int64, _P, _P, c_int64, _P, _P, _I, _I, _I,
                                          _P]),
     "wm2f_resize_nearest_labels": (c_int, [_P, _I, c_int64, POINTER(c_int64), _P, c_int64, _P, _P, _I, _I, _I, _I, _P]),
+    "wm2f_ccl_workspace": (c_int64, [_I, _I]),
+    "wm2f_ccl_label": (c_int, [_P, _I, _I, _I, _I, _P, _P, POINTER(ctypes.c_uint8), _I, _I, _I, _P, _P, _P]),
+    "wm2f_ccl_keys": (c_int, [_P, _I, _I, _I, _P, _P]),
+    "wm2f_ccl_paint": (c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "wm2f_resize_nearest": (c_int, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P]),
 }
 
 # additions of the profiling library (include/wm2f_prof.h)
