@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: images/sec of the Mask2Former hot path at 1024x1024, batch 8 per GPU.
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,15 +11,18 @@ of the whole forward over one batch already resident in HBM.  N > 1: the image b
 one process per GPU with its own batch of 8 (weak scaling, no data-path collective in the
 forward-only workload; `--mode train` adds the RCCL gradient all-reduce).
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints
+that line; its extra objects come from the HIP-event launch times taken inside the timed region:
   roofline      dominant hand-written kernel (K1, MSDeformAttn): algorithmic bytes per launch /
-                mean launch duration measured with HIP events inside the timed region.
+                mean launch duration.
   roofline_k3   same for the mask einsum against the fp32 MFMA peak.
+  kernels_us    launches and mean duration of every timed wm2f kernel.
+--full adds the legs that run work of their own after the timed region (N = 1, rank 0 only):
   cpu_baseline  the CPU oracle (oracle/m2f_oracle.py, kind "port") timed on this host on a
-                bounded sample of the same workload (N = 1, rank 0 only).
-  train_step    BASELINE.json configs[2] beside the headline line (N = 1, default flags only): a short bf16-autocast
-                full train step leg at batch 16 (Hungarian matching + losses + backward + AdamW), run AFTER the timed
-                forward region and the CPU sample -- ms per step, images/sec and the K1 / K2 / K3 launch times.
+                bounded sample of the same workload (--cpu-images).
+  train_step    BASELINE.json configs[2] beside the headline line (default flags only, --train-leg): a short
+                bf16-autocast full train step leg at batch 16 (Hungarian matching + losses + backward + AdamW), run
+                after the CPU sample -- ms per step, images/sec and the K1 / K2 / K3 launch times.
                 `value` / `metric` stay configs[1].
 
 --dump-outputs DIR (rank 0): right after the timed region, what the last timed step returned is written as
@@ -179,8 +182,10 @@ def main():
     ap.add_argument("--batch", type=int, default=8, help="images per GPU")
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--mode", choices=["fwd", "train"], default="fwd")
-    ap.add_argument("--cpu-images", type=int, default=2, help="images in the CPU-baseline sample (0 = skip)")
-    ap.add_argument("--train-leg", type=int, default=1, help="1: after the default run also time a short configs[2] train leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the CPU baseline and the configs[2] train leg (see the module docstring)")
+    ap.add_argument("--cpu-images", type=int, default=2, help="--full: images in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--train-leg", type=int, default=1, help="--full: 1 = also time a short configs[2] train leg (0 = skip)")
     ap.add_argument("--amp", choices=["off", "bf16"], default="off",
                     help="bf16: run the step under torch.autocast(bfloat16) (BASELINE configs 2-4)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -309,7 +314,7 @@ def main():
         line["kernels_us"] = {k: {"launches": n, "avg_us": round(us, 2)} for k, (n, us) in sorted(ksum.items())}
         if dumped is not None:
             line["dump_outputs"] = {"dir": a.dump_outputs, "arrays": dumped[0], "bytes": dumped[1]}
-        if world == 1 and a.cpu_images > 0:
+        if a.full and world == 1 and a.cpu_images > 0:
             cb, res, xc = cpu_baseline(model, S, a.cpu_images)
             # the same sample through the HIP path, as a last parity check beside the timing
             model.eval()
@@ -319,7 +324,7 @@ def main():
             cb["mask_logit_max_abs_err"] = float((o.masks_queries_logits.cpu() - ref).abs().max())
             cb["mask_logit_rel_err"] = cb["mask_logit_max_abs_err"] / float(ref.abs().max())
             line["cpu_baseline"] = {k: (round(v, 6) if isinstance(v, float) else v) for k, v in cb.items()}
-        if world == 1 and a.train_leg and which == "BASELINE.json configs[1]":
+        if a.full and world == 1 and a.train_leg and which == "BASELINE.json configs[1]":
             torch.cuda.empty_cache()  # 288 GB of HBM: the forward model simply stays resident beside the train leg's
             line["train_step"] = train_leg(dev)
         print(json.dumps(line), flush=True)

@@ -3,7 +3,7 @@
 configs[0]  PhenoBench crop/weed 256 x 256, ResNet-50 Mask2Former, batch 2: sample files -> collate_fn -> model -> loss ->
             instance post-processing, every stage against the CPU oracle.
 configs[1]  synthetic 1024 x 1024, R50, 100 queries, fp32 forward, batch 8: tests/test_fullsize_gpu.py (kernels at size) and
-            bench.py's cpu_baseline leg (whole forward against the oracle); here the batch-8 forward's size-independent
+            `bench.py --full`'s cpu_baseline leg (whole forward against the oracle); here the batch-8 forward's size-independent
             properties.
 configs[2]  the same model, bf16 autocast, full train step, batch 16.
 configs[3]  Swin-T backbone, 1024 x 1024, bf16, batch 8 per GPU (64 over 8 GPUs): forward + train step of one rank's share
@@ -216,7 +216,7 @@ def _train_step_losses(model, x, ml, cl, seed=3):
 
 def test_config1_resnet50_1024_fp32_batch8_forward_properties():
     """BASELINE.json configs[1]: synthetic 1024 x 1024 3-class, ResNet-50, 100 queries, fp32 forward-only, batch 8 -- the
-    bench workload.  (Against the oracle at this size: bench.py's cpu_baseline leg, 2 images, every run.)
+    bench workload.  (Against the oracle at this size: `bench.py --full`'s cpu_baseline leg, 2 images.)
     Run to run: STRICT.  Everything behind the backbone -- pixel decoder (K1, token GEMMs, fused passes, library GEMMs /
     convolutions) and transformer decoder (K2, K3, mask bits) -- is bit-identical between two calls on identical backbone
     features, and so are two whole forwards once the libraries have settled on their kernels (the FIRST call of a process

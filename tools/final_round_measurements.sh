@@ -2,7 +2,7 @@ set -e
 O=$GRAFT_REPO_ROOT/gpurun_out/final_r3
 mkdir -p $O
 cd $GRAFT_REPO_ROOT
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 echo "bench done"
 python bench.py --mode train --batch 8 --steps 3 --warmup 2 --cpu-images 0 --train-leg 0 > $O/bench_train_f32.json 2> $O/bench_train_f32.err
 echo "train f32 done"
