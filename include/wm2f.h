@@ -611,6 +611,31 @@ int wm2f_ccl_paint(void* workspace, const int64_t* order, int n, int H, int W, i
 int wm2f_resize_nearest(const void* src, int elem_bytes, int src_H, int src_W, const int32_t* ty, const int32_t* tx,
                         void* dst, int H, int W, void* stream);
 
+/* ---- polygon rasterisation ------------------------------------------------------------------
+ * cv2.fillPoly(img, pts, color) with the reference's arguments (int32 image, LINE_8, shift 0, no offset), for a
+ * chain of calls painted in order: call k paints value values[k] over the union of its outline (8-connected
+ * LineIterator lines, clipLine-clipped) and its scan fill (FillEdgeCollection: crossings of the active edges, sorted
+ * and paired), all contours of one call sharing one edge table (even-odd).  A later call overwrites an earlier one;
+ * pixels no call covers keep their value.  The result does not depend on the schedule.
+ * Inputs are DEVICE int32 arrays:
+ *   verts (n_verts, 2) x, y with |x|, |y| <= WM2F_POLY_MAX_COORD;
+ *   contour_offsets (n_contours + 1): contour c is verts[contour_offsets[c] .. contour_offsets[c + 1]), non-empty,
+ *     contour_offsets[0] = 0 and contour_offsets[n_contours] = n_verts;
+ *   call_offsets (n_calls + 1): call k is contours [call_offsets[k], call_offsets[k + 1]), non-decreasing from 0 to
+ *     n_contours;  values (n_calls);
+ *   call_row0 (n_calls), item_offsets (n_calls + 1): the rows the scan fill visits, call k rows call_row0[k] ..
+ *     call_row0[k] + item_offsets[k + 1] - item_offsets[k] - 1, each inside [0, H); item_offsets[0] = 0 and
+ *     item_offsets[n_calls] = n_items.  Any range that holds every row where a vertex y0 <= row < vertex y1 of the
+ *     call is correct (ops.fill_polygons uses [max(0, min y), min(H, max y) - 1]).
+ * out (H, W) int32, painted in place.  workspace: wm2f_poly_workspace(H, W, n_verts) bytes (-1 for a bad size):
+ * one 24-byte edge record per vertex and an (H, W) int32 rank map. */
+#define WM2F_POLY_MAX_SIDE 16384
+#define WM2F_POLY_MAX_COORD (1 << 24)
+int64_t wm2f_poly_workspace(int H, int W, int n_verts);
+int wm2f_poly_fill(int32_t* out, int H, int W, const int32_t* verts, int n_verts, const int32_t* contour_offsets,
+                   int n_contours, const int32_t* call_offsets, const int32_t* values, const int32_t* call_row0,
+                   const int32_t* item_offsets, int n_calls, int n_items, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

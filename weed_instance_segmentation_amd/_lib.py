@@ -21,6 +21,8 @@ WM2F_U8 = 3
 WM2F_U16 = 4
 WM2F_CCL_VALUE, WM2F_CCL_BINARY, WM2F_CCL_RGB = 0, 1, 2
 WM2F_CCL_MAX_COLORS = 16
+WM2F_POLY_MAX_SIDE = 16384
+WM2F_POLY_MAX_COORD = 1 << 24
 # return codes of include/wm2f.h
 WM2F_OK, WM2F_EINVAL, WM2F_EUNSUPPORTED, WM2F_ELAUNCH = 0, -1, -2, -3
 
@@ -110,6 +112,8 @@ SIGNATURES = {
     "wm2f_ccl_keys": (c_int, [_P, _I, _I, _I, _P, _P]),
     "wm2f_ccl_paint": (c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "wm2f_resize_nearest": (c_int, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P]),
+    "wm2f_poly_workspace": (c_int64, [_I, _I, _I]),
+    "wm2f_poly_fill": (c_int, [_P, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P]),
 }
 
 # additions of the profiling library (include/wm2f_prof.h)

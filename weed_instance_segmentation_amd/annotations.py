@@ -14,6 +14,18 @@ are drop-ins for datasets/pheno_bench/dataset.py:PhenoBenchDataset and for the C
 
 Components are numbered the way OpenCV's block-based labelling numbers them: by the first 2 x 2 block of the component in
 block-raster order, which is not the raster order of the first pixel (scipy / skimage order).
+
+The polygon loaders' `cv2.fillPoly` runs on csrc/polygon.hip:
+
+    from weed_instance_segmentation_amd.annotations import SorghumWeedDataset
+    from weed_instance_segmentation_amd.annotations import CropWeedYamlDataset as CropWeedDataset
+    from weed_instance_segmentation_amd.annotations import load_ground_truth
+
+stand for datasets/sorghum_weed/dataset.py:SorghumWeedDataset, the CWFID YAML loader
+(dataset_from_yaml_annotations.py:CropWeedDataset) and models/mask2former/inference.py:load_ground_truth.
+
+- `fill_poly(img, pts, color)`: the `cv2.fillPoly(img, pts, color)` contract on an (H, W) int32 device map.
+- `polygons_to_instance_map(polygons, ids, size)`: one fillPoly per polygon, in order, in one launch chain.
 """
 from __future__ import annotations
 
@@ -27,7 +39,8 @@ from . import _lib, ops
 from ._lib import Wm2fError
 
 __all__ = ["cv2_nearest_table", "connected_components", "resize_nearest", "semantic_to_instance_map",
-           "color_mask_to_instance_map", "PhenoBenchDataset", "CropWeedDataset"]
+           "color_mask_to_instance_map", "PhenoBenchDataset", "CropWeedDataset", "fill_poly",
+           "polygons_to_instance_map", "SorghumWeedDataset", "CropWeedYamlDataset", "load_ground_truth"]
 
 
 def cv2_nearest_table(src_size: int, dst_size: int) -> np.ndarray:
@@ -186,18 +199,23 @@ class _AnnotatedPngDataset(torch.utils.data.Dataset):
             width, height = new_width, new_height
         target_size = (height, width)
         instance_map, id_to_semantic = self._instance_map(torch.from_numpy(mask).to(self.device), dsize)
-        instance_map = instance_map.cpu().numpy()
-        inputs = self.processor(images=[image], segmentation_maps=[instance_map],
-                                instance_id_to_semantic_id=id_to_semantic, return_tensors="pt", ignore_index=255)
-        return {
-            "pixel_values": inputs["pixel_values"][0],
-            "mask_labels": inputs["mask_labels"][0],
-            "class_labels": inputs["class_labels"][0],
-            "target_size": target_size,
-            "original_map": instance_map,
-            "id_to_semantic": id_to_semantic,
-            "file_name": file_name,
-        }
+        return _assemble_item(self.processor, image, instance_map.cpu().numpy(), id_to_semantic, target_size, file_name)
+
+
+def _assemble_item(processor, image, instance_map: np.ndarray, id_to_semantic: dict, target_size, file_name) -> dict:
+    """The item every reference loader returns: the processor's outputs for one image and its (H, W) int32 instance map
+    (255 = ignore), with the map itself, the id dict, the target size and the file name."""
+    inputs = processor(images=[image], segmentation_maps=[instance_map], instance_id_to_semantic_id=id_to_semantic,
+                       return_tensors="pt", ignore_index=255)
+    return {
+        "pixel_values": inputs["pixel_values"][0],
+        "mask_labels": inputs["mask_labels"][0],
+        "class_labels": inputs["class_labels"][0],
+        "target_size": target_size,
+        "original_map": instance_map,
+        "id_to_semantic": id_to_semantic,
+        "file_name": file_name,
+    }
 
 
 class PhenoBenchDataset(_AnnotatedPngDataset):
@@ -239,3 +257,265 @@ class CropWeedDataset(_AnnotatedPngDataset):
 
     def _instance_map(self, mask, dsize):
         return color_mask_to_instance_map(mask, self.color_map(), dsize)
+
+
+# ------------------------------------------------------------------------------------------- polygons
+def _contour(pts, name: str) -> np.ndarray:
+    a = np.asarray(pts)
+    if a.ndim == 3 and a.shape[1] == 1:  # cv2's (N, 1, 2) contour layout
+        a = a[:, 0, :]
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f"{name}: expected an (N, 2) array of x, y points, got shape {a.shape}")
+    if a.shape[0] == 0:
+        raise ValueError(f"{name}: a contour needs at least one point (cv2.fillPoly fails on an empty one)")
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"{name}: expected integer points, got {a.dtype}")
+    if int(np.abs(a.astype(np.int64)).max()) > _lib.WM2F_POLY_MAX_COORD:
+        raise ValueError(f"{name}: coordinates must lie within +-{_lib.WM2F_POLY_MAX_COORD}")
+    return a.astype(np.int64)
+
+
+def _check_map(img, name: str) -> torch.Tensor:
+    img = _require_cuda(img, name)
+    if img.dim() != 2 or img.dtype != torch.int32 or not img.is_contiguous():
+        raise TypeError(f"{name}: expected a contiguous (H, W) int32 map, got {tuple(img.shape)} {img.dtype}")
+    if img.shape[0] <= 0 or img.shape[1] <= 0:
+        raise ValueError(f"{name}: empty map {tuple(img.shape)}")
+    return img
+
+
+def _fill_calls(img: torch.Tensor, calls, values) -> torch.Tensor:
+    """One fillPoly per entry of `calls` (a list of contour lists), in order, with the matching value."""
+    verts, n_contours = [], []
+    for k, contours in enumerate(calls):
+        for j, pts in enumerate(contours):
+            a = np.asarray(pts)
+            if a.ndim != 2 or a.shape[1] != 2 or a.shape[0] == 0 or a.dtype.kind not in "iu":
+                a = _contour(pts, f"polygon {k}, contour {j}")  # the (N, 1, 2) layout, or raises with the reason
+            verts.append(a)
+        n_contours.append(len(contours))
+    if not verts:
+        v, c_off = np.zeros((0, 2), dtype=np.int64), np.zeros(1, dtype=np.int64)
+    else:
+        v = np.concatenate(verts).astype(np.int64, copy=False)
+        if int(np.abs(v).max()) > _lib.WM2F_POLY_MAX_COORD:
+            raise ValueError(f"coordinates must lie within +-{_lib.WM2F_POLY_MAX_COORD}")
+        c_off = np.concatenate([[0], np.cumsum([len(a) for a in verts])])
+    k_off = np.concatenate([[0], np.cumsum(n_contours, dtype=np.int64)])
+    return ops.fill_polygons(img, v, c_off, k_off, np.asarray(values, dtype=np.int64))
+
+
+def fill_poly(img: torch.Tensor, pts, color: int) -> torch.Tensor:
+    """`cv2.fillPoly(img, pts, color)` with the reference's arguments (LINE_8, shift 0, no offset) on an (H, W) int32
+    device map, in place; returns `img`.  `pts` is a list of (N, 2) integer x, y arrays; its contours share one edge
+    table, so overlaps follow the even-odd rule (holes), as in cv2.  The outline is painted too, and points outside the
+    map are clipped as OpenCV clips them."""
+    img = _check_map(img, "img")
+    if isinstance(pts, np.ndarray) and pts.ndim == 2:
+        raise ValueError("pts: expected a list of (N, 2) contours, as cv2.fillPoly takes; got one (N, 2) array")
+    return _fill_calls(img, [list(pts)], [int(color)])
+
+
+def polygons_to_instance_map(polygons, ids, size, background: int = 255, device="cuda") -> torch.Tensor:
+    """The instance map of the polygon loaders: an (H, W) int32 map of `background` with size = (H, W), then
+    `cv2.fillPoly(map, [polygons[i]], ids[i])` for every i in order (later polygons overwrite earlier ones), as one
+    chain of kernels.  Returns the map on the device."""
+    h, w = int(size[0]), int(size[1])
+    if h <= 0 or w <= 0:
+        raise ValueError(f"size must be positive (H, W), got {size}")
+    if len(polygons) != len(ids):
+        raise ValueError(f"{len(polygons)} polygons but {len(ids)} ids")
+    out = torch.full((h, w), int(background), dtype=torch.int32, device=device)
+    _check_map(out, "map")
+    return _fill_calls(out, [[p] for p in polygons], [int(i) for i in ids])
+
+
+# ---- host-side annotation parsing (the reference loaders' rules; no GPU involved)
+def _via_polygons(entry: dict, label2id: dict, scale_x: float, scale_y: float, skip_255: bool):
+    """The polygons of one VIA-JSON entry (Sorghum, inference.py's ground truth): 'polygon' shapes whose 'classname'
+    is in label2id, in order, ids 1, 2, ... (255 skipped when skip_255), points scaled by int(v * scale) per axis.
+    Returns (polygons, ids, id_to_semantic)."""
+    polygons, ids, id_to_semantic = [], [], {}
+    current = 1
+    for region in entry.get("regions", []):
+        shape_attr = region["shape_attributes"]
+        region_attr = region["region_attributes"]
+        if shape_attr["name"] != "polygon":
+            continue
+        class_name = region_attr.get("classname", None)
+        if class_name not in label2id:
+            continue
+        if skip_255 and current == 255:
+            current += 1
+        xs = [int(x * scale_x) for x in shape_attr["all_points_x"]]
+        ys = [int(y * scale_y) for y in shape_attr["all_points_y"]]
+        polygons.append(np.array(list(zip(xs, ys)), dtype=np.int64).reshape(-1, 2))
+        ids.append(current)
+        id_to_semantic[current] = label2id[class_name]
+        current += 1
+    return polygons, ids, id_to_semantic
+
+
+def _cwfid_polygons(annotation: dict, label2id: dict, scale: float):
+    """The polygons of one CWFID YAML file: regions whose 'type' is in label2id, ids 1, 2, ... with 255 skipped.  A
+    float pair becomes a one-point list; other scalars, length mismatches and fewer than 3 points skip the region
+    (the id is not consumed).  Returns (polygons, ids, id_to_semantic)."""
+    polygons, ids, id_to_semantic = [], [], {}
+    current = 1
+    regions = annotation.get("annotation", []) or []
+    for region in regions:
+        type_name = region.get("type")
+        if type_name not in label2id:
+            continue
+        if current == 255:
+            current += 1
+        points = region.get("points", {})
+        xs, ys = points.get("x", []), points.get("y", [])
+        if not isinstance(xs, list) or not isinstance(ys, list):
+            if isinstance(xs, float) and isinstance(ys, float):
+                xs, ys = [xs], [ys]
+            else:
+                print("skipping region with invalid points format (not lists)")
+                print(f"xs: {xs}\n ys: {ys}")
+                continue
+        if len(xs) != len(ys) or len(xs) < 3:
+            continue
+        polygons.append(np.array([[int(x * scale), int(y * scale)] for x, y in zip(xs, ys)], dtype=np.int64))
+        ids.append(current)
+        id_to_semantic[current] = label2id[type_name]
+        current += 1
+    return polygons, ids, id_to_semantic
+
+
+def _open_scaled(image_path: str, max_input_dim: int):
+    """The image as the reference loaders read it: RGB, resized with PIL BILINEAR to int(side * s), s = max_input_dim /
+    max(w, h), when larger than max_input_dim.  Returns (image, scale_factor)."""
+    from PIL import Image
+    image = Image.open(image_path).convert("RGB")
+    width, height = image.size
+    scale_factor = 1.0
+    if max(width, height) > max_input_dim:
+        scale_factor = max_input_dim / max(width, height)
+        image = image.resize(size=(int(width * scale_factor), int(height * scale_factor)), resample=Image.BILINEAR)
+    return image, scale_factor
+
+
+class SorghumWeedDataset(torch.utils.data.Dataset):
+    """datasets/sorghum_weed/dataset.py:SorghumWeedDataset with the instance map painted on the GPU.  `annotation_path`
+    is a VIA JSON file; entries are kept when their image exists in `image_folder_path` and they have regions.
+    `max_input_dim` and `max_images` stand for config.MAX_INPUT_DIM and config.MAX_IMAGES."""
+
+    def __init__(self, image_folder_path, annotation_path, processor, label2id: dict, max_input_dim: int = 1024,
+                 max_images=None, device="cuda"):
+        import json
+        self.image_folder = image_folder_path
+        self.processor = processor
+        self.label2id = label2id
+        self.max_input_dim = int(max_input_dim)
+        self.device = torch.device(device)
+        with open(annotation_path, "r") as f:
+            self.data = list(json.load(f).values())
+        self.valid_entries = []
+        for entry in self.data:
+            if os.path.exists(os.path.join(self.image_folder, entry["filename"])) and len(entry.get("regions", [])) > 0:
+                self.valid_entries.append(entry)
+                if max_images is not None and len(self.valid_entries) >= max_images:
+                    break
+        print(f'\t\tLoaded {len(self.valid_entries)} valid images from "{annotation_path}"')
+
+    def __len__(self):
+        return len(self.valid_entries)
+
+    def __getitem__(self, idx: int) -> dict:
+        entry = self.valid_entries[idx]
+        image, scale = _open_scaled(os.path.join(self.image_folder, entry["filename"]), self.max_input_dim)
+        width, height = image.size
+        polygons, ids, id_to_semantic = _via_polygons(entry, self.label2id, scale, scale, skip_255=True)
+        instance_map = polygons_to_instance_map(polygons, ids, (height, width), 255, self.device).cpu().numpy()
+        return _assemble_item(self.processor, image, instance_map, id_to_semantic, (height, width), entry["filename"])
+
+
+class CropWeedYamlDataset(torch.utils.data.Dataset):
+    """The CWFID YAML loader (dataset_from_yaml_annotations.py:CropWeedDataset) with the instance map painted on the
+    GPU.  `annotation_path` is a folder of `*.yaml` files (sorted); each names its image with the 'filename' key."""
+
+    def __init__(self, image_folder_path, annotation_path, processor, label2id: dict, max_input_dim: int = 1024,
+                 max_images=None, device="cuda"):
+        import yaml
+        self.image_folder = image_folder_path
+        self.annotation_path = annotation_path
+        self.processor = processor
+        self.label2id = label2id
+        self.max_input_dim = int(max_input_dim)
+        self.device = torch.device(device)
+        yaml_files = sorted(glob.glob(os.path.join(self.annotation_path, "*.yaml")))
+        self.valid_files = []
+        print(f'Scanning {len(yaml_files)} annotation files in "{self.annotation_path}"...')
+        for yaml_path in yaml_files:
+            try:
+                with open(yaml_path, "r") as f:
+                    data = yaml.safe_load(f)
+                if not data:
+                    continue
+                img_filename = data.get("filename")
+                if not img_filename:
+                    continue
+                img_path = os.path.join(self.image_folder, img_filename)
+                if os.path.exists(img_path):
+                    self.valid_files.append((img_path, yaml_path))
+                    if max_images is not None and len(self.valid_files) >= max_images:
+                        break
+            except Exception as e:
+                print(f'Warning: Error reading "{yaml_path}":\n\t {e}')
+        print(f'\tLoaded {len(self.valid_files)} valid image/yaml pairs from "{self.image_folder}"')
+
+    def __len__(self):
+        return len(self.valid_files)
+
+    def __getitem__(self, idx: int) -> dict:
+        import yaml
+        image_path, yaml_path = self.valid_files[idx]
+        image, scale = _open_scaled(image_path, self.max_input_dim)
+        with open(yaml_path, "r") as f:
+            annotation = yaml.safe_load(f)
+        width, height = image.size
+        polygons, ids, id_to_semantic = _cwfid_polygons(annotation, self.label2id, scale)
+        instance_map = polygons_to_instance_map(polygons, ids, (height, width), 255, self.device).cpu().numpy()
+        return _assemble_item(self.processor, image, instance_map, id_to_semantic, (height, width),
+                              os.path.basename(image_path))
+
+
+def load_ground_truth(image_name: str, target_size: tuple, annotation_file: str, img_dir: str, label2id: dict,
+                      device="cuda"):
+    """models/mask2former/inference.py:load_ground_truth with the map painted on the GPU.  target_size = (W, H); points
+    scale by target / original size per axis (1:1 when the image is missing); zero background, ids 1, 2, ... (no 255
+    skip).  Returns {'segmentation': (H, W) int32 CPU tensor, 'segments_info': [{'id', 'label_id', 'score'}]}, or None
+    where the reference prints a message and returns None."""
+    import json
+    if not os.path.exists(annotation_file):
+        print(f"Annotation file not found: {annotation_file}")
+        return None
+    try:
+        with open(annotation_file, "r") as f:
+            data = json.load(f)
+    except Exception as e:
+        print(f"Error loading JSON: {e}")
+        return None
+    entry = next((item for item in data.values() if item["filename"] == image_name), None)
+    if not entry:
+        print(f'No annotation found for "{image_name}"')
+        return None
+    image_path = os.path.join(img_dir, image_name)
+    if os.path.exists(image_path):
+        from PIL import Image
+        with Image.open(image_path) as orig_img:
+            orig_w, orig_h = orig_img.size
+    else:
+        print("Warning: Original image file not found. Assuming 1:1 scale.")
+        orig_w, orig_h = target_size
+    target_w, target_h = target_size
+    polygons, ids, id_to_semantic = _via_polygons(entry, label2id, target_w / orig_w, target_h / orig_h,
+                                                  skip_255=False)
+    segmentation = polygons_to_instance_map(polygons, ids, (target_h, target_w), 0, device).cpu()
+    segments_info = [{"id": i, "label_id": id_to_semantic[i], "score": 1.0} for i in ids]
+    return {"segmentation": segmentation, "segments_info": segments_info}
