@@ -498,6 +498,36 @@ int wm2f_instance_segmentation(const void* mask_logits, const int32_t* kept_q, c
 int wm2f_instance_maps(const void* image_logits, const int32_t* kept_q, int n, void* maps, int h, int w, int gh,
                        int gw, int Ho, int Wo, void* stream);
 
+/* ---- semantic and panoptic post-processing on device ------------------------------------
+ * The pixel work of Mask2FormerImageProcessor.post_process_semantic_segmentation and
+ * post_process_panoptic_segmentation, transformers 5.15.0 image_processing_mask2former.py:550-625 and :748-841
+ * (compute_segments :167-224).  mask_logits (B, Q, h, w) fp32 DEVICE; gh x gw = the dependency's 384 x 384 grid;
+ * Ho x Wo = one target size (one call per distinct size); rows (nrows) int32 DEVICE: the image of each output slot.
+ * wm2f_semantic_scores:        scores (B, C, gh, gw) fp32 = sum over q, ascending, of class_probs[b,q,c] *
+ *                              sigmoid(bilinear(logits[b,q])); class_probs (B, Q, C) fp32 DEVICE (softmax without the
+ *                              null class).
+ * wm2f_semantic_resize_argmax: segmentation (nrows, Ho, Wo) int64 = first-max argmax over c of the bilinear resize of
+ *                              scores[rows[j]] to Ho x Wo; out_scores (nrows, C, Ho, Wo) fp32 = that resize, or NULL.
+ * wm2f_panoptic_probs:         probs (B, K, gh, gw) fp32 = sigmoid(bilinear(logits[b, kept_q[b,k]])) for
+ *                              k < n_kept[b]; kept_q (B, K), n_kept (B) int32 DEVICE.
+ * wm2f_panoptic_segments:      segmentation (nrows, Ho, Wo) int32 = first-max argmax over k < n_kept of
+ *                              bilinear(probs[b,k]) * scores[b,k] (b = rows[j]); counts (B, K, 2) int32, zeroed by the
+ *                              caller, accumulates [0] = #pixels with that product >= mask_threshold, [1] = #pixels
+ *                              whose argmax is k.  scores (B, K) fp32 DEVICE.  n_kept[rows[j]] > 0 is required.
+ * wm2f_panoptic_relabel:       segmentation[j][p] = table[rows[j] * K + segmentation[j][p]] in place; table (B, K)
+ *                              int32 DEVICE (segment id of each kept query, 0 = rejected). */
+int wm2f_semantic_scores(const void* mask_logits, const void* class_probs, void* scores, int B, int Q, int C, int h,
+                         int w, int gh, int gw, void* stream);
+int wm2f_semantic_resize_argmax(const void* scores, const int32_t* rows, int nrows, void* segmentation,
+                                void* out_scores, int C, int gh, int gw, int Ho, int Wo, void* stream);
+int wm2f_panoptic_probs(const void* mask_logits, const int32_t* kept_q, const int32_t* n_kept, void* probs, int B,
+                        int Q, int K, int h, int w, int gh, int gw, void* stream);
+int wm2f_panoptic_segments(const void* probs, const int32_t* rows, const int32_t* n_kept, const void* scores,
+                           int32_t* segmentation, int32_t* counts, int nrows, int K, int gh, int gw, int Ho, int Wo,
+                           float mask_threshold, void* stream);
+int wm2f_panoptic_relabel(int32_t* segmentation, const int32_t* rows, const int32_t* table, int nrows, int K,
+                          int64_t n_pixels, void* stream);
+
 /* ---- label expansion on device ------------------------------------------
  * The tensor work of convert_segmentation_map_to_binary_masks (image_processing_mask2former.py:227-259,
  * image_processing_pil_mask2former.py:81-114), so that a sample can travel as its (H, W) instance-id map instead of

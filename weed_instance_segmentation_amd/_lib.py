@@ -55,6 +55,11 @@ SIGNATURES = {
     "wm2f_instance_any": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_instance_segmentation": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_instance_maps": (c_int, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "wm2f_semantic_scores": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "wm2f_semantic_resize_argmax": (c_int, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "wm2f_panoptic_probs": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "wm2f_panoptic_segments": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, c_float, _P]),
+    "wm2f_panoptic_relabel": (c_int, [_P, _P, _P, _I, _I, c_int64, _P]),
     "wm2f_mask_einsum_bf16_fwd": (c_int, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "wm2f_nchw_to_pixel_major_bf16": (c_int, [_P, _P, _I, _I, _I, _P]),
     "wm2f_mask_einsum_fwd": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),

@@ -1328,6 +1328,82 @@ def instance_maps(image_logits, kept_q, n, size):
     return maps
 
 
+# ------------------------------------------------------ semantic and panoptic post-processing
+def semantic_scores(mask_logits: torch.Tensor, class_probs: torch.Tensor) -> torch.Tensor:
+    """einsum("bqc,bqhw->bchw", class_probs, sigmoid(bilinear_384(mask_logits))): (B, C, 384, 384) fp32."""
+    mask_logits, class_probs = _req(mask_logits, "mask_logits"), _req(class_probs, "class_probs")
+    B, Q, h, w = mask_logits.shape
+    C = class_probs.shape[-1]
+    if class_probs.shape != (B, Q, C):
+        raise ValueError(f"semantic_scores: class_probs {tuple(class_probs.shape)} does not match logits {tuple(mask_logits.shape)}")
+    S = torch.empty(B, C, _GRID[0], _GRID[1], device=mask_logits.device, dtype=torch.float32)
+    with torch.cuda.device(mask_logits.device):
+        check(_timed("semantic_scores", S, lambda: load().wm2f_semantic_scores(
+            _p(mask_logits), _p(class_probs), _p(S), B, Q, C, h, w, _GRID[0], _GRID[1], _stream(S))), "wm2f_semantic_scores")
+    return S
+
+
+def semantic_resize_argmax(scores: torch.Tensor, rows: torch.Tensor, size, want_scores: bool = False):
+    """Bilinear resize of scores[rows] (B, C, gh, gw) to `size`, first-max argmax over C: ((n, H, W) int64,
+    (n, C, H, W) fp32 resized scores or None)."""
+    scores, rows = _req(scores, "scores"), _req(rows, "rows", torch.int32)
+    _, C, gh, gw = scores.shape
+    n, H, W = rows.numel(), int(size[0]), int(size[1])
+    seg = torch.empty(n, H, W, device=scores.device, dtype=torch.int64)
+    out = torch.empty(n, C, H, W, device=scores.device, dtype=torch.float32) if want_scores else None
+    with torch.cuda.device(scores.device):
+        check(_timed("semantic_resize_argmax", seg, lambda: load().wm2f_semantic_resize_argmax(
+            _p(scores), _p(rows), n, _p(seg), _p(out), C, gh, gw, H, W, _stream(seg))), "wm2f_semantic_resize_argmax")
+    return seg, out
+
+
+def panoptic_probs(mask_logits: torch.Tensor, kept_q: torch.Tensor, n_kept: torch.Tensor) -> torch.Tensor:
+    """sigmoid(bilinear_384(mask_logits[b, kept_q[b, k]])) for k < n_kept[b]: (B, K, 384, 384) fp32 (slots past
+    n_kept[b] are left unwritten)."""
+    mask_logits = _req(mask_logits, "mask_logits")
+    kept_q, n_kept = _req(kept_q, "kept_q", torch.int32), _req(n_kept, "n_kept", torch.int32)
+    B, Q, h, w = mask_logits.shape
+    K = kept_q.shape[1]
+    G = torch.empty(B, K, _GRID[0], _GRID[1], device=mask_logits.device, dtype=torch.float32)
+    with torch.cuda.device(mask_logits.device):
+        check(_timed("panoptic_probs", G, lambda: load().wm2f_panoptic_probs(
+            _p(mask_logits), _p(kept_q), _p(n_kept), _p(G), B, Q, K, h, w, _GRID[0], _GRID[1], _stream(G))),
+            "wm2f_panoptic_probs")
+    return G
+
+
+def panoptic_segments(probs: torch.Tensor, rows: torch.Tensor, n_kept: torch.Tensor, scores: torch.Tensor, counts: torch.Tensor,
+                      size, mask_threshold: float) -> torch.Tensor:
+    """Argmax over the kept queries of bilinear(probs[b, k]) * scores[b, k] at `size` for the images `rows`:
+    (n, H, W) int32 query indices.  Adds into counts (B, K, 2) int32 the pixels at or above mask_threshold and the
+    pixels each query owns."""
+    probs, rows = _req(probs, "probs"), _req(rows, "rows", torch.int32)
+    n_kept, scores = _req(n_kept, "n_kept", torch.int32), _req(scores, "scores")
+    counts = _req(counts, "counts", torch.int32)
+    B, K, gh, gw = probs.shape
+    if scores.shape != (B, K) or counts.shape != (B, K, 2) or n_kept.shape != (B,):
+        raise ValueError("panoptic_segments: scores (B, K), counts (B, K, 2) and n_kept (B,) must match probs (B, K, h, w)")
+    n, H, W = rows.numel(), int(size[0]), int(size[1])
+    seg = torch.empty(n, H, W, device=probs.device, dtype=torch.int32)
+    with torch.cuda.device(probs.device):
+        check(_timed("panoptic_segments", seg, lambda: load().wm2f_panoptic_segments(
+            _p(probs), _p(rows), _p(n_kept), _p(scores), _p(seg), _p(counts), n, K, gh, gw, H, W, float(mask_threshold),
+            _stream(seg))), "wm2f_panoptic_segments")
+    return seg
+
+
+def panoptic_relabel_(seg: torch.Tensor, rows: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+    """seg[j] = table[rows[j]][seg[j]] in place (seg (n, H, W) int32 query indices, table (B, K) int32 segment ids)."""
+    seg, rows, table = _req(seg, "seg", torch.int32), _req(rows, "rows", torch.int32), _req(table, "table", torch.int32)
+    n = rows.numel()
+    if seg.shape[0] != n:
+        raise ValueError("panoptic_relabel_: one map per row")
+    with torch.cuda.device(seg.device):
+        check(_timed("panoptic_relabel", seg, lambda: load().wm2f_panoptic_relabel(
+            _p(seg), _p(rows), _p(table), n, int(table.shape[1]), seg[0].numel(), _stream(seg))), "wm2f_panoptic_relabel")
+    return seg
+
+
 # ------------------------------------------------------ point-sampled mask loss over all levels (SURVEY 8f rank 1)
 def _ptr_table(tensors):
     return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])

@@ -1,4 +1,5 @@
-"""Device-side `post_process_instance_segmentation`.
+"""Device-side `post_process_instance_segmentation`, and the semantic and panoptic
+post-processing of the same processor (see their docstrings).
 
 Mirrors `Mask2FormerImageProcessor.post_process_instance_segmentation` of transformers 5.15.0
 (models/mask2former/image_processing_mask2former.py:627-746) -- same arguments, same return structure -- for the
@@ -18,9 +19,13 @@ as in the dependency's instance path.
 """
 from __future__ import annotations
 
+import logging
+
 import torch
 
 from . import ops
+
+logger = logging.getLogger(__name__)
 
 
 def binary_mask_to_rle(mask: torch.Tensor) -> list[int]:
@@ -36,6 +41,64 @@ def binary_mask_to_rle(mask: torch.Tensor) -> list[int]:
 def convert_segmentation_to_rle(segmentation: torch.Tensor) -> list[list[int]]:
     """One run-length list per distinct id of the map, background (-1) included (:100-118)."""
     return [binary_mask_to_rle(torch.where(segmentation == idx, 1, 0)) for idx in torch.unique(segmentation)]
+
+
+class SemanticSegmentationPostProcessorOutput(dict):
+    """One image of `post_process_semantic_segmentation(..., return_segmentation_scores=True)`: `segmentation` (H, W)
+    int64 class ids and `segmentation_scores` (C, H, W) fp32, by key or by attribute (the dependency's class of this
+    name, without importing it)."""
+
+    def __init__(self, segmentation: torch.Tensor, segmentation_scores: torch.Tensor):
+        super().__init__(segmentation=segmentation, segmentation_scores=segmentation_scores)
+
+    def __getattr__(self, name):
+        try:
+            return self[name]
+        except KeyError:
+            raise AttributeError(name) from None
+
+
+def assign_segment_ids(labels, scores, above, owned, overlap_mask_area_threshold: float, label_ids_to_fuse):
+    """The host half of the dependency's compute_segments (image_processing_mask2former.py:167-224) for ONE image, from
+    per-query pixel counts instead of masks.  labels / scores: the kept queries' class and score (host numbers, query
+    order); above[k]: pixels whose score-weighted probability is >= mask_threshold (`original_area`); owned[k]: pixels
+    whose argmax is k (`mask_k_area`).  Returns (ids, segments_info): ids[k] = segment id painted for query k, 0 if
+    the query is rejected.
+
+    The dependency's rules, kept as they are:
+    - a query survives if owned > 0, above > 0 and float32(owned / above) > overlap_mask_area_threshold -- a float32
+      torch division, so an exact 4 / 5 passes at 0.8 (float32(0.8) > 0.8);
+    - ids start at 1; a label in label_ids_to_fuse remembers its first id, and a later query of that label reuses it
+      AND resets the running counter to it, so the next new segment repeats an id (labels [A, B, A, C] with A fused
+      give ids [1, 2, 1, 2]);
+    - was_fused is True for every segment of a fused label; score = round(float(score), 6)."""
+    n = len(labels)
+    ratio = (torch.tensor(list(owned), dtype=torch.int64) / torch.tensor(list(above), dtype=torch.int64)).tolist() if n else []
+    ids = [0] * n
+    segments = []
+    current, memory = 0, {}
+    for k in range(n):
+        label = int(labels[k])
+        fuse = label in label_ids_to_fuse
+        if not (owned[k] > 0 and above[k] > 0 and ratio[k] > overlap_mask_area_threshold):
+            continue
+        if label in memory:
+            current = memory[label]
+        else:
+            current += 1
+        ids[k] = current
+        segments.append({"id": current, "label_id": label, "was_fused": fuse, "score": round(float(scores[k]), 6)})
+        if fuse:
+            memory[label] = current
+    return ids, segments
+
+
+def _device_logits(outputs):
+    logits = outputs.masks_queries_logits
+    if not logits.is_cuda:
+        from ._lib import Wm2fError
+        raise Wm2fError(f"masks_queries_logits is on {logits.device}: the wm2f kernels run on a GPU only (no CPU fallback)")
+    return logits.float().contiguous()
 
 
 class Mask2FormerInstancePostProcessor:
@@ -112,4 +175,118 @@ class Mask2FormerInstancePostProcessor:
             if return_binary_maps and ks:
                 segmentation = ops.instance_maps(logits[i], kept_q_all[i], len(ks), sizes[i])
             results.append({"segmentation": segmentation, "segments_info": segments})
+        return results
+
+    def post_process_semantic_segmentation(self, outputs, target_sizes=None, return_segmentation_scores: bool = False):
+        """`Mask2FormerImageProcessor.post_process_semantic_segmentation` (image_processing_mask2former.py:550-625):
+        same arguments, same return structure, on the GPU.
+
+        S = einsum("bqc,bqhw->bchw", softmax(class logits)[..., :-1], sigmoid(bilinear_384(mask logits))) (bilinear,
+        align_corners=False, to the dependency's fixed 384 x 384 grid); with target sizes S is resized bilinearly to
+        each one; the map is the argmax over classes, the first class winning ties.  Returns per image an (H, W) int64
+        map ((384, 384) without target sizes), or with return_segmentation_scores=True a
+        SemanticSegmentationPostProcessorOutput whose segmentation_scores are the (C, H, W) fp32 scores the map was
+        taken from.  The (B, Q, C + 1) softmax is torch on the device; the einsum, the resize and the argmax run in
+        csrc/postprocess_sp.hip; nothing is copied to the host."""
+        logits = _device_logits(outputs)
+        cls = outputs.class_queries_logits
+        B = cls.shape[0]
+        if target_sizes is not None and len(target_sizes) != B:
+            raise ValueError("Make sure that you pass in as many target sizes as the batch dimension of the logits")
+        dev = logits.device
+        probs = torch.softmax(cls.detach().to(dev).float(), dim=-1)[..., :-1].contiguous()
+        S = ops.semantic_scores(logits, probs)
+        results: list = [None] * B
+        if target_sizes is None:
+            seg, _ = ops.semantic_resize_argmax(S, torch.arange(B, device=dev, dtype=torch.int32), ops._GRID)
+            for i in range(B):
+                results[i] = (seg[i], S[i])
+        else:
+            sizes = [tuple(int(v) for v in t) for t in target_sizes]
+            for size in dict.fromkeys(sizes):  # one launch per distinct target size
+                rows = [i for i in range(B) if sizes[i] == size]
+                seg, sc = ops.semantic_resize_argmax(S, torch.tensor(rows, device=dev, dtype=torch.int32), size,
+                                                     want_scores=return_segmentation_scores)
+                for j, i in enumerate(rows):
+                    results[i] = (seg[j], sc[j] if sc is not None else None)
+        if not return_segmentation_scores:
+            return [m for m, _ in results]
+        return [SemanticSegmentationPostProcessorOutput(m, sc) for m, sc in results]
+
+    def post_process_panoptic_segmentation(self, outputs, threshold: float = 0.5, mask_threshold: float = 0.5,
+                                           overlap_mask_area_threshold: float = 0.8, label_ids_to_fuse=None,
+                                           target_sizes=None):
+        """`Mask2FormerImageProcessor.post_process_panoptic_segmentation` (image_processing_mask2former.py:748-841,
+        compute_segments :167-224): same arguments, same return structure, on the GPU.
+
+        - Selection, on the host with torch as the dependency's CPU path: scores, labels = softmax(class logits).max(-1);
+          a query is kept if label != num_labels and score > threshold (strict, unlike the instance path's >=), in
+          query order.
+        - Map values: p_k = sigmoid(bilinear_384(logits_k)), resized bilinearly to the target size if one is given (the
+          384 x 384 grid itself otherwise), then multiplied by score_k; every pixel goes to the first kept query of
+          maximal value.
+        - original_area = pixels with that score-weighted value >= mask_threshold; mask_k_area = pixels owned by k;
+          segment ids, fusion and the area test as in `assign_segment_ids` (duplicate ids included).
+        - The map is int32, 0 where no segment was painted.  An image without a kept query gets a float32 map of -1
+          (at the target size, 384 x 384 without one) and no segments.
+        label_ids_to_fuse=None logs the dependency's warning and fuses nothing.
+
+        Kernels (csrc/postprocess_sp.hip) compute the kept queries' 384 x 384 probabilities, then per target pixel
+        the argmax and the two per-query counts; ONE device-to-host copy of the (B, K, 2) counts feeds the host
+        id assignment, and a last kernel relabels the map through the k -> id table."""
+        if label_ids_to_fuse is None:
+            logger.warning("`label_ids_to_fuse` unset. No instance will be fused.")
+            label_ids_to_fuse = set()
+        logits = _device_logits(outputs)
+        cls = outputs.class_queries_logits
+        B = cls.shape[0]
+        num_labels = cls.shape[-1] - 1
+        if target_sizes is not None and len(target_sizes) != B:
+            raise ValueError("Make sure that you pass in as many target sizes as the batch dimension of the logits")
+        dev = logits.device
+        sizes = [tuple(int(v) for v in t) for t in target_sizes] if target_sizes is not None else [ops._GRID] * B
+
+        # ---- query selection on the host (remove_low_and_no_objects, :121-146)
+        cls_cpu = cls.detach().float().cpu()
+        pred_scores, pred_labels = torch.nn.functional.softmax(cls_cpu, dim=-1).max(-1)
+        keep = pred_labels.ne(num_labels) & (pred_scores > threshold)
+        kept = [torch.nonzero(keep[i]).flatten() for i in range(B)]
+        n_kept = [int(k.numel()) for k in kept]
+        K = max(1, max(n_kept))
+        kept_q = torch.zeros(B, K, dtype=torch.int32)
+        kept_s = torch.zeros(B, K, dtype=torch.float32)
+        for i in range(B):
+            kept_q[i, :n_kept[i]] = kept[i].to(torch.int32)
+            kept_s[i, :n_kept[i]] = pred_scores[i, kept[i]]
+
+        results: list = [None] * B
+        groups = []
+        if any(n_kept):
+            kept_q_d, kept_s_d = kept_q.to(dev), kept_s.to(dev)
+            n_kept_d = torch.tensor(n_kept, dtype=torch.int32).to(dev)
+            G = ops.panoptic_probs(logits, kept_q_d, n_kept_d)
+            counts = torch.zeros(B, K, 2, dtype=torch.int32, device=dev)
+            live = [i for i in range(B) if n_kept[i]]
+            for size in dict.fromkeys(sizes[i] for i in live):  # one launch per distinct target size
+                rows = [i for i in live if sizes[i] == size]
+                rows_d = torch.tensor(rows, dtype=torch.int32).to(dev)
+                groups.append((rows, rows_d, ops.panoptic_segments(G, rows_d, n_kept_d, kept_s_d, counts, size, mask_threshold)))
+            # ---- the one device-to-host copy of the call's pixel results
+            counts_cpu = counts.cpu()
+            table = torch.zeros(B, K, dtype=torch.int32)
+            segments = [[] for _ in range(B)]
+            for i in live:
+                n = n_kept[i]
+                ids, segments[i] = assign_segment_ids(pred_labels[i, kept[i]].tolist(), kept_s[i, :n].tolist(),
+                                                      counts_cpu[i, :n, 0].tolist(), counts_cpu[i, :n, 1].tolist(),
+                                                      overlap_mask_area_threshold, label_ids_to_fuse)
+                table[i, :n] = torch.tensor(ids, dtype=torch.int32)
+            table_d = table.to(dev)
+            for rows, rows_d, seg in groups:
+                ops.panoptic_relabel_(seg, rows_d, table_d)
+                for j, i in enumerate(rows):
+                    results[i] = {"segmentation": seg[j], "segments_info": segments[i]}
+        for i in range(B):
+            if not n_kept[i]:
+                results[i] = {"segmentation": torch.full(sizes[i], -1.0, dtype=torch.float32, device=dev), "segments_info": []}
         return results
