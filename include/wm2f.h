@@ -252,6 +252,26 @@ int wm2f_masked_xattn_bf16_bwd(const void* q, const void* k, const void* v, cons
                                const void* out, const void* lse, const void* grad_out, void* grad_q, void* grad_k,
                                void* grad_v, void* workspace, int B, int heads, int Q, int N, int D, void* stream);
 
+/* ---- Swin backbone: shifted-window attention, inference forward ---------------------------------
+ * One launch per Swin layer for pad + roll + window partition + q k^T * D^-1/2 + relative-position bias + shift mask +
+ * softmax + p v + window reverse + roll back + crop (transformers modeling_swin.py:401-468, :486-505, :553-626).
+ *   q, k, v    (B, H*W, heads*D) in IMAGE order, as the three Linears write them
+ *   k_pad, v_pad (heads*D): key / value row of a padding token (a zero row through the Linear = its bias); NULL = zeros
+ *   bias_table ((2 ws - 1)^2, heads) fp32: the relative-position-bias PARAMETER itself, indexed in the kernel
+ *   out        (B, H*W, heads*D) in image order, dtype of q
+ * Contract: Hp = ceil(H / ws) ws, Wp likewise; padding tokens sit at the bottom / right of the (Hp, Wp) frame, are NOT masked
+ * (they are keys of every real query of their window) and get no output.  Window (wy, wx), slot (i, j) holds the token at
+ * padded-frame position ((wy ws + i + shift) mod Hp, (wx ws + j + shift) mod Wp).  With shift > 0 a slot's region id is
+ * 3 ((r >= Hp - ws) + (r >= Hp - shift)) + ((c >= Wp - ws) + (c >= Wp - shift)) of its rolled-frame coordinates
+ * r = wy ws + i, c = wx ws + j, and a score gets -100 (finite) where query and key ids differ.  Softmax in fp32 over the ws^2
+ * keys of the window.  0 <= shift < ws; the window is never reduced for small maps.
+ * dtype WM2F_F32: fp32 operands, exact-fp32 products.  WM2F_BF16: bf16 operands as a bf16-autocast Linear writes them, bf16
+ * matrix cores with fp32 accumulation, scores and softmax in fp32, P rounded to bf16 once, bf16 out.
+ * ws in {4, 7, 12}, D in {16, 32}, 16-byte aligned operands; anything else returns WM2F_EUNSUPPORTED. */
+int wm2f_swin_window_attn_fwd(const void* q, const void* k, const void* v, const void* k_pad, const void* v_pad,
+                              const void* bias_table, void* out, int B, int H, int W, int heads, int D, int ws, int shift,
+                              int dtype, void* stream);
+
 /* ---- K4: Hungarian-matcher cost matrices ------------------------------------------------------
  * Replaces Mask2FormerHungarianMatcher.forward up to (not including) the scipy solver,
  * HF:444-472 with sample_point HF:245-274 and the pair-wise losses HF:328-374, batched over

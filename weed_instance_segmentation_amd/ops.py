@@ -638,6 +638,68 @@ def masked_xattn(q, k, v, mask, row_open, heads: int) -> torch.Tensor:
     return _MaskedXAttn.apply(q, k, v, mask, row_open, heads)
 
 
+# ----------------------------------------------------------------------------------------- Swin window attention
+SWIN_WINDOW_SIZES = (4, 7, 12)
+SWIN_HEAD_DIMS = (16, 32)
+
+
+def swin_window_attention_applies(window_size: int, head_dim: int, dtype: torch.dtype, device) -> bool:
+    """Shapes wm2f_swin_window_attn_fwd is built for: a GPU, fp32 or bf16 tokens, window 4 / 7 / 12, head_dim 16 / 32."""
+    return (torch.device(device).type == "cuda" and dtype in (torch.float32, torch.bfloat16)
+            and int(window_size) in SWIN_WINDOW_SIZES and int(head_dim) in SWIN_HEAD_DIMS)
+
+
+def swin_window_attention(q, k, v, bias_table, dims, heads: int, window_size: int, shift: int, k_pad=None, v_pad=None):
+    """Shifted-window attention of one Swin layer in ONE launch (inference only, no autograd): pad, roll, window partition,
+    softmax(q k^T / sqrt(D) + relative-position bias + shift mask) v, window reverse, roll back and crop.
+    q, k, v (B, H*W, heads*D) in image order, fp32 or bf16; bias_table ((2 ws - 1)^2, heads) fp32, the parameter itself;
+    dims = (H, W); k_pad / v_pad (heads*D): key / value row of a padding token (the k / v Linear's bias), None = zeros.
+    Returns (B, H*W, heads*D) in image order, dtype of q.  Contract: include/wm2f.h."""
+    ts = {"q": q, "k": k, "v": v, "bias_table": bias_table, "k_pad": k_pad, "v_pad": v_pad}
+    for name, t in ts.items():
+        if t is not None and not isinstance(t, torch.Tensor):
+            raise TypeError(f"swin_window_attention: {name}: expected a tensor")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts.values()):
+        raise _lib.Wm2fError("swin_window_attention has no backward: call it under no_grad or on tensors that do not "
+                             "require grad (the training path of the Swin backbone runs stock ops)")
+    if q.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"swin_window_attention: q: expected float32 or bfloat16, got {q.dtype}")
+    dt = q.dtype
+    q, k, v = _req(q, "q", dt), _req(k, "k", dt), _req(v, "v", dt)
+    bias_table = _req(bias_table, "bias_table")
+    H, W = int(dims[0]), int(dims[1])
+    ws, shift, heads = int(window_size), int(shift), int(heads)
+    if q.dim() != 3 or heads <= 0 or q.shape[2] % heads:
+        raise ValueError(f"swin_window_attention: q {tuple(q.shape)} heads {heads}")
+    B, N, E = q.shape
+    D = E // heads
+    if N != H * W or H <= 0 or W <= 0 or k.shape != q.shape or v.shape != q.shape:
+        raise ValueError(f"swin_window_attention: q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} dims {(H, W)}")
+    if ws <= 0 or not 0 <= shift < ws:
+        raise ValueError(f"swin_window_attention: shift {shift} outside [0, window {ws})")
+    if bias_table.shape != ((2 * ws - 1) ** 2, heads):
+        raise ValueError(f"swin_window_attention: bias_table {tuple(bias_table.shape)} != {((2 * ws - 1) ** 2, heads)}")
+    if not swin_window_attention_applies(ws, D, dt, q.device):
+        raise ValueError(f"swin_window_attention: window {ws} / head_dim {D} not built "
+                         f"(windows {SWIN_WINDOW_SIZES}, head dims {SWIN_HEAD_DIMS})")
+    pads = []
+    for name, t in (("k_pad", k_pad), ("v_pad", v_pad)):
+        if t is not None:
+            t = _req(t, name, dt)
+            if t.shape != (E,):
+                raise ValueError(f"swin_window_attention: {name} {tuple(t.shape)} != {(E,)}")
+            if t.data_ptr() % 16:  # a view into a flat parameter bucket: the kernel reads 16-byte pieces
+                t = t.clone()
+        pads.append(t)
+    out = torch.empty_like(q)
+    lib = load()
+    with torch.cuda.device(q.device):
+        check(_timed(f"swin_window_attn_ws{ws}", q, lambda: lib.wm2f_swin_window_attn_fwd(
+            _p(q), _p(k), _p(v), _p(pads[0]), _p(pads[1]), _p(bias_table), _p(out), B, H, W, heads, D, ws, shift,
+            WM2F_BF16 if dt == torch.bfloat16 else WM2F_F32, _stream(q))), "wm2f_swin_window_attn_fwd")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- K4
 def matcher_cost(mask_logits, class_logits, tgt_masks, tgt_counts, tgt_classes, points, w_class, w_mask, w_dice):
     """K4 -- all cost matrices of a step in one go (HF:444-472), no sync.
