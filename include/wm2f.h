@@ -272,6 +272,37 @@ int wm2f_swin_window_attn_fwd(const void* q, const void* k, const void* v, const
                               const void* bias_table, void* out, int B, int H, int W, int heads, int D, int ws, int shift,
                               int dtype, void* stream);
 
+/* ---- Swin backbone: shifted-window attention, training forward and backward -----------------------
+ * wm2f_swin_window_attn_train_fwd is wm2f_swin_window_attn_fwd (same kernel template, same contract and numbers) that also
+ * writes lse (B, heads, H*W) fp32: the log-sum-exp of every real query's score row, which the backward needs.
+ *
+ * wm2f_swin_window_attn_bwd: the gradients of that forward under the contract paragraph above.
+ *   q, k, v, k_pad, v_pad, bias_table: the forward's inputs;  lse: the training forward's;  grad_out (B, H*W, heads*D) in
+ *   image order, dtype of q
+ *   grad_q, grad_k, grad_v (B, H*W, heads*D), image order, dtype of q: overwritten, every row (each real token is a query and a
+ *     key of exactly one window, so the three are complete inside one workgroup: plain vector stores)
+ *   grad_k_pad, grad_v_pad (heads*D) fp32 or NULL: dK / dV summed over every padding slot of every window and image -- the
+ *     share of the k / v Linear's bias gradient that comes from padding rows
+ *   grad_bias_table ((2 ws - 1)^2, heads) fp32 or NULL: per head and relative offset, dS summed over every (query, key) pair of
+ *     that offset, window and image; masked pairs and padding keys included, padding queries contribute nothing
+ * S is recomputed as the forward computes it, P = exp(S - lse), dP = dO V^T, delta = rowsum(P dP), dS = P (dP - delta),
+ * dV = P^T dO, dK = dS^T Q D^-1/2, dQ = dS K D^-1/2.  WM2F_F32: exact-fp32 products.  WM2F_BF16: bf16 matrix cores, fp32
+ * S / P / dS / accumulation, P and dS rounded to bf16 once as MFMA operands, bf16 grad_q / k / v.
+ * The two cross-workgroup sums (table, padding rows) go through `workspace` -- one partial per (image, window, head) written by
+ * its workgroup, added in a fixed order by a second kernel: no float atomics to global memory, bit-identical run to run.
+ * workspace: wm2f_swin_window_attn_bwd_workspace(...) bytes = 4 B nW heads ((2 ws - 1)^2 + 2 D), 16-byte aligned; the largest
+ * case, Swin-L stage 1 at 1024 x 1024 with B = 8 (484 windows, 6 heads, ws 12): 55.1 MB.  May be NULL when all three optional
+ * outputs are NULL.  ws in {4, 7, 12}, D in {16, 32}, 16-byte aligned operands; anything else returns WM2F_EUNSUPPORTED (the
+ * workspace query returns 0). */
+int wm2f_swin_window_attn_train_fwd(const void* q, const void* k, const void* v, const void* k_pad, const void* v_pad,
+                                    const void* bias_table, void* out, void* lse, int B, int H, int W, int heads, int D, int ws,
+                                    int shift, int dtype, void* stream);
+int64_t wm2f_swin_window_attn_bwd_workspace(int B, int H, int W, int heads, int D, int ws);
+int wm2f_swin_window_attn_bwd(const void* q, const void* k, const void* v, const void* k_pad, const void* v_pad,
+                              const void* bias_table, const void* lse, const void* grad_out, void* grad_q, void* grad_k,
+                              void* grad_v, void* grad_k_pad, void* grad_v_pad, void* grad_bias_table, void* workspace, int B,
+                              int H, int W, int heads, int D, int ws, int shift, int dtype, void* stream);
+
 /* ---- K4: Hungarian-matcher cost matrices ------------------------------------------------------
  * Replaces Mask2FormerHungarianMatcher.forward up to (not including) the scipy solver,
  * HF:444-472 with sample_point HF:245-274 and the pair-wise losses HF:328-374, batched over

@@ -19,6 +19,11 @@ Per (model, stage, input 1024 x 1024 | 800 x 1344, B = 1 | 8, fp32 | bf16, shift
 - both are HIP-event times per call, median over --rounds rounds of --iters calls, the two routes alternating round by
   round in one process after 3 warm-up calls each; `max_abs_diff` compares their outputs.
 The `backbones` lines time SwinBackbone.forward (B = 1, 1024 x 1024) with backbone_swin.FUSED_WINDOW_ATTENTION on and off.
+
+--train times forward + backward instead (default --out profiles/swin_window_attn_bwd_bench.jsonl), 1024 x 1024 only:
+ops.swin_window_attention_train against the same stock lines with autograd on, q / k / v and the bias table requiring
+grad, one fixed cotangent (`"train": true` lines; `max_rel_diff_grad_q` compares the two routes' grad_q); the `backbones`
+lines are SwinBackbone in train() with every parameter requiring grad, forward + backward of sum(f.square().mean()).
 """
 from __future__ import annotations
 
@@ -103,7 +108,7 @@ def alternate(fns, rounds, iters):
 def bench_stages(name, args, f):
     cfg = MODELS[name]
     ws = cfg["window_size"]
-    for size in INPUTS:
+    for size in (INPUTS[:1] if args.train else INPUTS):
         for stage, heads in enumerate(cfg["num_heads"]):
             dims = (size[0] // (4 << stage), size[1] // (4 << stage))
             dim = cfg["embed_dim"] << stage
@@ -123,6 +128,26 @@ def bench_stages(name, args, f):
                         with torch.autocast("cuda", torch.bfloat16, enabled=dtype == torch.bfloat16):
                             return stock_attention(layer, q, k, v, dims)
 
+                    if args.train:
+                        param = layer.attention.relative_position_bias.relative_position_bias_table
+                        leaves = [q.requires_grad_(), k.requires_grad_(), v.requires_grad_(), param]
+                        cot = torch.randn(q.shape, device="cuda", generator=g).to(dtype)
+                        fwd_fused = lambda: ops.swin_window_attention_train(q, k, v, param, dims, heads, ws, layer.shift)
+                        fused_t = lambda: torch.autograd.grad(fwd_fused(), leaves, cot)
+                        stock_t = lambda: torch.autograd.grad(stock(), leaves, cot)
+                        gf, gs = fused_t()[0].float(), stock_t()[0].float()
+                        diff = ((gf - gs).norm() / gs.norm()).item()
+                        fused_ms, stock_ms = alternate([fused_t, stock_t], args.rounds, args.iters)
+                        rec = {"model": name, "train": True, "stage": stage + 1, "input": list(size), "tokens": list(dims),
+                               "B": B, "heads": heads, "head_dim": dim // heads, "window": ws, "shift": layer.shift,
+                               "dtype": str(dtype).split(".")[1], "fused_ms": round(fused_ms, 4),
+                               "stock_ms": round(stock_ms, 4), "speedup": round(stock_ms / fused_ms, 2),
+                               "max_rel_diff_grad_q": diff}
+                        print(json.dumps(rec), flush=True)
+                        f.write(json.dumps(rec) + "\n")
+                        del q, k, v, cot, gf, gs
+                        torch.cuda.empty_cache()
+                        continue
                     with torch.no_grad():
                         diff = (fused().float() - stock().float()).abs().max().item()
                         fused_ms, stock_ms = alternate([fused, stock], args.rounds, args.iters)
@@ -139,18 +164,25 @@ def bench_stages(name, args, f):
 def bench_backbones(args, f):
     for name, cfg in MODELS.items():
         model = SwinBackbone({**cfg, "out_features": ["stage1", "stage2", "stage3", "stage4"]}).cuda().eval()
+        if args.train:
+            model.train()
         x = torch.randn(1, 3, 1024, 1024, device="cuda")
         for dtype in (torch.float32, torch.bfloat16):
             def run(on):
                 def fn():
                     backbone_swin.FUSED_WINDOW_ATTENTION = on
+                    if args.train:
+                        with torch.autocast("cuda", torch.bfloat16, enabled=dtype == torch.bfloat16):
+                            loss = sum(fm.square().mean() for fm in model(x))
+                        model.zero_grad(set_to_none=True)
+                        return loss.backward()
                     with torch.no_grad(), torch.autocast("cuda", torch.bfloat16, enabled=dtype == torch.bfloat16):
                         return model(x)
                 return fn
 
             fused_ms, stock_ms = alternate([run(True), run(False)], args.rounds, max(args.iters // 2, 1))
             backbone_swin.FUSED_WINDOW_ATTENTION = True
-            rec = {"model": name, "whole_backbone_forward": True, "input": [1024, 1024], "B": 1,
+            rec = {"model": name, "whole_backbone_forward_backward" if args.train else "whole_backbone_forward": True, "input": [1024, 1024], "B": 1,
                    "dtype": str(dtype).split(".")[1], "fused_ms": round(fused_ms, 3), "stock_ms": round(stock_ms, 3),
                    "speedup": round(stock_ms / fused_ms, 2)}
             print(json.dumps(rec), flush=True)
@@ -162,8 +194,11 @@ def main():
     ap.add_argument("--model", required=True, choices=list(MODELS) + ["backbones"])
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "swin_window_attn_bench.jsonl"))
+    ap.add_argument("--train", action="store_true", help="forward + backward instead of the inference forward")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "swin_window_attn_bwd_bench.jsonl" if args.train else "swin_window_attn_bench.jsonl")
     if not torch.cuda.is_available():
         raise SystemExit("swin_attn_bench needs an MI355X")
     torch.set_num_threads(min(16, torch.get_num_threads()))

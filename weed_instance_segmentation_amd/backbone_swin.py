@@ -1,6 +1,6 @@
-"""Swin Transformer backbone.  Inference on a GPU runs each layer's shifted-window attention in one launch of
-ops.swin_window_attention; training, CPU tensors and shapes that kernel is not built for run
-stock PyTorch-ROCm ops (the backward of the fused op is out of scope).
+"""Swin Transformer backbone.  On a GPU each layer's shifted-window attention is one launch: ops.swin_window_attention
+when autograd records nothing, ops.swin_window_attention_train (one more launch in the backward) when it does (DESIGN.md
+section 19); CPU tensors and shapes those kernels are not built for run stock PyTorch-ROCm ops.
 
 Needed because the reference's own checkpoint is Swin-Large (config.py:4) and BASELINE.json's configs 4 / 5
 are Swin-T / Swin-B.  Restates transformers' SwinBackbone (models/swin/modeling_swin.py:1070-1150 of
@@ -117,11 +117,8 @@ class Layer(nn.Module):  # modeling_swin.py:508-626
         return m.masked_fill(m != 0, -100.0).masked_fill(m == 0, 0.0)
 
     def _fused_applies(self, x):
-        """One launch for the whole window attention: GPU tokens, a shape the kernel is built for, and nothing for
-        autograd to record (the op has no backward)."""
+        """One launch for the whole window attention: GPU tokens and a shape the kernels are built for."""
         if not (FUSED_WINDOW_ATTENTION and x.is_cuda):
-            return False
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             return False
         dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
         return ops.swin_window_attention_applies(self.ws, self.attention.head_dim, dtype, x.device)
@@ -130,9 +127,17 @@ class Layer(nn.Module):  # modeling_swin.py:508-626
         at = self.attention
         h = self.layernorm_before(x)  # image-order tokens: no pad, no roll, no partition, no pad rows in the GEMMs
         q, k, v = at.q_proj(h), at.k_proj(h), at.v_proj(h)
-        pad = lambda lin: None if lin.bias is None else lin.bias.detach().to(q.dtype)  # a zero row through the Linear
-        a = ops.swin_window_attention(q, k, v, at.relative_position_bias.relative_position_bias_table.detach().float(), dims,
-                                      at.heads, self.ws, self.shift, pad(at.k_proj), pad(at.v_proj))
+        table = at.relative_position_bias.relative_position_bias_table
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            # autograd records: the table and the biases go in undetached, through casts it sees -- the padding rows' share
+            # of k_proj.bias.grad / v_proj.bias.grad comes back through k_pad / v_pad
+            pad = lambda lin: None if lin.bias is None else lin.bias.to(q.dtype)
+            a = ops.swin_window_attention_train(q, k, v, table.float(), dims, at.heads, self.ws, self.shift,
+                                                pad(at.k_proj), pad(at.v_proj))
+        else:
+            pad = lambda lin: None if lin.bias is None else lin.bias.detach().to(q.dtype)  # a zero row through the Linear
+            a = ops.swin_window_attention(q, k, v, table.detach().float(), dims, at.heads, self.ws, self.shift,
+                                          pad(at.k_proj), pad(at.v_proj))
         x = x + _drop_path(at.o_proj(a), self.drop_path, self.training)
         return x + self.mlp(self.layernorm_after(x))
 

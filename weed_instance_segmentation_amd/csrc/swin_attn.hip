@@ -63,11 +63,13 @@ struct alignas(16) SwinSmemBf16 {
   int tok[PAIRS][SwinGeom<WS>::LP];
 };
 
-template <typename T, int WS, int D>
+// TRAIN: the same forward, also writing the log-sum-exp of every real query's row to lse (B, heads, H*W) for the backward
+// (swin_attn_bwd.hip).
+template <typename T, int WS, int D, bool TRAIN>
 __global__ __launch_bounds__(SwinGeom<WS>::PAIRS* SwinGeom<WS>::WPP* kWave) void swin_window_attn_kernel(
     const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, const T* __restrict__ k_pad,
-    const T* __restrict__ v_pad, const float* __restrict__ bias_table, T* __restrict__ out, int H, int W, int heads,
-    int shift, int nWy, int nWx, int total_pairs, float scale) {
+    const T* __restrict__ v_pad, const float* __restrict__ bias_table, T* __restrict__ out, float* __restrict__ lse, int H,
+    int W, int heads, int shift, int nWy, int nWx, int total_pairs, float scale) {
   using G = SwinGeom<WS>;
   constexpr bool BF16 = std::is_same<T, uint16_t>::value;
   constexpr int L = G::L, LT = G::LT, LP = G::LP, NB = G::NB, PAIRS = G::PAIRS, WPP = G::WPP;
@@ -267,6 +269,9 @@ __global__ __launch_bounds__(SwinGeom<WS>::PAIRS* SwinGeom<WS>::WPP* kWave) void
 
     // ---- O^T: column = query n, rows d = 16 i + 4 g + r -> 4 consecutive channels of the query's own token
     if (live && qtok >= 0) {
+      if constexpr (TRAIN) {
+        if (g == 0) lse[((int64_t)b * heads + head) * H * W + qtok] = mx + logf(lsum);  // the accurate log: an error here is a normalisation error of every P of the row
+      }
       T* op = out + qrow + 4 * g;
 #pragma unroll
       for (int i = 0; i < DT; ++i) {
@@ -285,24 +290,24 @@ __global__ __launch_bounds__(SwinGeom<WS>::PAIRS* SwinGeom<WS>::WPP* kWave) void
 
 template <typename T, int WS, int D>
 void launch_swin(const void* q, const void* k, const void* v, const void* k_pad, const void* v_pad, const void* bias_table,
-                 void* out, int H, int W, int heads, int shift, int nWy, int nWx, int total_pairs, hipStream_t st) {
+                 void* out, void* lse, int H, int W, int heads, int shift, int nWy, int nWx, int total_pairs, hipStream_t st) {
   using G = SwinGeom<WS>;
   const float scale = 1.0f / sqrtf((float)D);
-  hipLaunchKernelGGL((swin_window_attn_kernel<T, WS, D>), dim3(ceil_div(total_pairs, G::PAIRS)), dim3(G::PAIRS * G::WPP * kWave),
-                     0, st, (const T*)q, (const T*)k, (const T*)v, (const T*)k_pad, (const T*)v_pad,
-                     (const float*)bias_table, (T*)out, H, W, heads, shift, nWy, nWx, total_pairs, scale);
+  const dim3 grid(ceil_div(total_pairs, G::PAIRS)), block(G::PAIRS * G::WPP * kWave);
+  if (lse != nullptr)
+    hipLaunchKernelGGL((swin_window_attn_kernel<T, WS, D, true>), grid, block, 0, st, (const T*)q, (const T*)k, (const T*)v,
+                       (const T*)k_pad, (const T*)v_pad, (const float*)bias_table, (T*)out, (float*)lse, H, W, heads, shift,
+                       nWy, nWx, total_pairs, scale);
+  else
+    hipLaunchKernelGGL((swin_window_attn_kernel<T, WS, D, false>), grid, block, 0, st, (const T*)q, (const T*)k, (const T*)v,
+                       (const T*)k_pad, (const T*)v_pad, (const float*)bias_table, (T*)out, (float*)nullptr, H, W, heads,
+                       shift, nWy, nWx, total_pairs, scale);
 }
 
-}  // namespace
-
-}  // namespace wm2f
-
-using namespace wm2f;
-
-extern "C" int wm2f_swin_window_attn_fwd(const void* q, const void* k, const void* v, const void* k_pad, const void* v_pad,
-                                         const void* bias_table, void* out, int B, int H, int W, int heads, int D, int ws,
-                                         int shift, int dtype, void* stream) {
-  const char* who = "wm2f_swin_window_attn_fwd";
+// Argument checks and dispatch of both exported forwards; lse == nullptr is the inference form.
+int swin_fwd(const char* who, const void* q, const void* k, const void* v, const void* k_pad, const void* v_pad,
+             const void* bias_table, void* out, void* lse, int B, int H, int W, int heads, int D, int ws, int shift, int dtype,
+             void* stream) {
   WM2F_REQUIRE(q && k && v && bias_table && out, "%s: null pointer", who);
   WM2F_REQUIRE(B > 0 && H > 0 && W > 0 && heads > 0, "%s: non-positive size", who);
   WM2F_REQUIRE(ws > 0 && shift >= 0 && shift < ws, "%s: shift %d outside [0, window %d)", who, shift, ws);
@@ -319,7 +324,7 @@ extern "C" int wm2f_swin_window_attn_fwd(const void* q, const void* k, const voi
   }
   hipStream_t st = (hipStream_t)stream;
 #define WM2F_SW(Tv, WSv, Dv) \
-  launch_swin<Tv, WSv, Dv>(q, k, v, k_pad, v_pad, bias_table, out, H, W, heads, shift, nWy, nWx, (int)pairs, st)
+  launch_swin<Tv, WSv, Dv>(q, k, v, k_pad, v_pad, bias_table, out, lse, H, W, heads, shift, nWy, nWx, (int)pairs, st)
 #define WM2F_SW_D(Tv, WSv)       \
   do {                           \
     if (D == 32) WM2F_SW(Tv, WSv, 32); \
@@ -338,4 +343,25 @@ extern "C" int wm2f_swin_window_attn_fwd(const void* q, const void* k, const voi
 #undef WM2F_SW
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;
+}
+
+}  // namespace
+
+}  // namespace wm2f
+
+using namespace wm2f;
+
+extern "C" int wm2f_swin_window_attn_fwd(const void* q, const void* k, const void* v, const void* k_pad, const void* v_pad,
+                                         const void* bias_table, void* out, int B, int H, int W, int heads, int D, int ws,
+                                         int shift, int dtype, void* stream) {
+  return swin_fwd("wm2f_swin_window_attn_fwd", q, k, v, k_pad, v_pad, bias_table, out, nullptr, B, H, W, heads, D, ws, shift,
+                  dtype, stream);
+}
+
+extern "C" int wm2f_swin_window_attn_train_fwd(const void* q, const void* k, const void* v, const void* k_pad,
+                                               const void* v_pad, const void* bias_table, void* out, void* lse, int B, int H,
+                                               int W, int heads, int D, int ws, int shift, int dtype, void* stream) {
+  WM2F_REQUIRE(lse != nullptr, "wm2f_swin_window_attn_train_fwd: null lse");
+  return swin_fwd("wm2f_swin_window_attn_train_fwd", q, k, v, k_pad, v_pad, bias_table, out, lse, B, H, W, heads, D, ws, shift,
+                  dtype, stream);
 }
