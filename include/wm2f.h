@@ -657,6 +657,42 @@ int wm2f_resize_nearest_labels(const void* maps, int dtype, int64_t n_map_elems,
                                const int32_t* tables, int64_t n_table, int32_t* out, uint8_t* present, int B, int Hp,
                                int Wp, int ignore_index, void* stream);
 
+/* ---- training augmentation on device: flip, resize, crop --------------------------------
+ * Per image, explicit parameters flip in {0, 1}, the resized size (h, w), the window origin (y0, x0) and the window size
+ * (ch, cw) with y0 + ch <= h, x0 + cw <= w and (ch, cw) <= (Hp, Wp).  The result is, bit for bit, what Pillow makes of
+ * image.transpose(FLIP_LEFT_RIGHT).resize((w, h)).crop((x0, y0, x0 + cw, y0 + ch)), then the processor's lookup / padding:
+ *   1. the flip is applied to the SOURCE, before the resize: column c of the flipped image is column W - 1 - c of the
+ *      stored one, and the tap tables are those of (W -> w) applied to the mirrored image.  The output is never mirrored
+ *      instead (Pillow's nearest index table is not mirror-symmetric);
+ *   2. the resize is the one of wm2f_resize_normalize_u8 / wm2f_resize_nearest_labels, of the whole flipped frame;
+ *   3. the window's pixels are exactly that frame's pixels at rows y0 .. y0 + ch - 1, columns x0 .. x0 + cw - 1.  The
+ *      (h, w) frame is virtual: only the window is computed, and nothing of size h or w is stored;
+ *   4. lut (3, 256) maps (channel, byte) to the rescaled, normalised value;
+ *   5. below and right of the window up to (Hp, Wp): pixel_values 0, pixel_mask 0, maps ignore_index;
+ *   6. present flags the id values inside the window only.
+ * With flip 0, origin (0, 0) and window (h, w) the outputs equal those of the two calls above.
+ * The tap and index tables are handed over WHOLE, built for the full (H -> h), (W -> w) resize exactly as for the calls
+ * above; the kernels index them at y0 + y and x0 + x.
+ * wm2f_augment_resize_normalize_u8: one launch and no workspace.  A workgroup owns a 16 x 128 output tile, runs the
+ *     horizontal pass for the tile's columns over the source rows its vertical taps reach (64 rows at a time, uint8 in
+ *     LDS, clipped as the workspace bytes of wm2f_resize_normalize_u8 are) and sums the vertical taps in registers; a
+ *     downscale of any ratio takes more 64-row rounds, never a second launch.
+ *       desc   HOST int64 (B, WM2F_AUG_PRE_DESC_LEN): in_off (bytes into images), H, W, h, w, tx, cx, kx, ty, cy, ky,
+ *              flip, y0, x0, ch, cw.
+ * wm2f_augment_nearest_labels: out (B, Hp, Wp) int32, out[y][x] = map[yi[y0 + y]][mirror(xi[x0 + x])] inside the window.
+ *       desc   HOST int64 (B, WM2F_AUG_LAB_DESC_LEN): in_off (elements), H, W, h, w, xi, yi, flip, y0, x0, ch, cw.
+ * Bounds: B <= WM2F_PRE_MAX_IMAGES; H, W, Hp, Wp <= WM2F_PRE_MAX_SIDE; the virtual h, w <= WM2F_AUG_MAX_VIRTUAL; else
+ * WM2F_EUNSUPPORTED.  A window outside its frame or larger than (Hp, Wp) is WM2F_EINVAL. */
+#define WM2F_AUG_MAX_VIRTUAL 65536
+#define WM2F_AUG_PRE_DESC_LEN 16
+#define WM2F_AUG_LAB_DESC_LEN 12
+int wm2f_augment_resize_normalize_u8(const uint8_t* images, int64_t images_bytes, const int64_t* desc,
+                                     const int32_t* tables, int64_t n_table, const float* lut, float* pixel_values,
+                                     int64_t* pixel_mask, int B, int Hp, int Wp, void* stream);
+int wm2f_augment_nearest_labels(const void* maps, int dtype, int64_t n_map_elems, const int64_t* desc,
+                                const int32_t* tables, int64_t n_table, int32_t* out, uint8_t* present, int B, int Hp,
+                                int Wp, int ignore_index, void* stream);
+
 /* ---- connected components of class maps ------------------------------------------------
  * The cv2 steps of the reference's dataset loaders (datasets/pheno_bench/dataset.py:48-135, crop_weed
  * dataset_from_png_annotations.py:48-131): cv2.resize(INTER_NEAREST) of the mask, cv2.connectedComponents per class,

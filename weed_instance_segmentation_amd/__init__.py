@@ -13,3 +13,4 @@ __version__ = "0.1.0"
 from .postprocess import Mask2FormerInstancePostProcessor  # noqa: F401
 from .metrics import MeanAveragePrecision  # noqa: F401
 from .preprocess import Mask2FormerImageProcessor  # noqa: F401
+from .augment import AugmentParams, TrainAugmentation  # noqa: F401

@@ -23,6 +23,8 @@ WM2F_CCL_VALUE, WM2F_CCL_BINARY, WM2F_CCL_RGB = 0, 1, 2
 WM2F_CCL_MAX_COLORS = 16
 WM2F_POLY_MAX_SIDE = 16384
 WM2F_POLY_MAX_COORD = 1 << 24
+WM2F_AUG_MAX_VIRTUAL = 65536
+WM2F_AUG_PRE_DESC_LEN, WM2F_AUG_LAB_DESC_LEN = 16, 12
 # return codes of include/wm2f.h
 WM2F_OK, WM2F_EINVAL, WM2F_EUNSUPPORTED, WM2F_ELAUNCH = 0, -1, -2, -3
 
@@ -116,6 +118,8 @@ SIGNATURES = {
     "wm2f_resize_normalize_u8": (c_int, [_P, c_int64, POINTER(c_int64), _P, c_int64, _P, _P, c_int64, _P, _P, _I, _I, _I,
                                          _P]),
     "wm2f_resize_nearest_labels": (c_int, [_P, _I, c_int64, POINTER(c_int64), _P, c_int64, _P, _P, _I, _I, _I, _I, _P]),
+    "wm2f_augment_resize_normalize_u8": (c_int, [_P, c_int64, POINTER(c_int64), _P, c_int64, _P, _P, _P, _I, _I, _I, _P]),
+    "wm2f_augment_nearest_labels": (c_int, [_P, _I, c_int64, POINTER(c_int64), _P, c_int64, _P, _P, _I, _I, _I, _I, _P]),
     "wm2f_ccl_workspace": (c_int64, [_I, _I]),
     "wm2f_ccl_label": (c_int, [_P, _I, _I, _I, _I, _P, _P, POINTER(ctypes.c_uint8), _I, _I, _I, _P, _P, _P]),
     "wm2f_ccl_keys": (c_int, [_P, _I, _I, _I, _P, _P]),

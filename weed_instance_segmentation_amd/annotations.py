@@ -163,13 +163,14 @@ class _AnnotatedPngDataset(torch.utils.data.Dataset):
     """File pairing and item assembly shared by the two loaders; subclasses give the mask file and the instance map."""
 
     def __init__(self, image_folder_path, annotation_path, processor, label2id: dict, max_input_dim: int = 1024,
-                 max_images=None, device="cuda"):
+                 max_images=None, device="cuda", augment=None, generator=None):
         self.image_folder = image_folder_path
         self.annotation_path = annotation_path
         self.processor = processor
         self.label2id = label2id
         self.max_input_dim = int(max_input_dim)
         self.device = torch.device(device)
+        self.augment, self.generator = augment, generator  # a TrainAugmentation and its CPU torch.Generator, or None
         self.image_files = sorted(glob.glob(os.path.join(self.image_folder, "*.png")))
         self.valid_files = []
         for img_path in self.image_files:
@@ -199,15 +200,27 @@ class _AnnotatedPngDataset(torch.utils.data.Dataset):
             width, height = new_width, new_height
         target_size = (height, width)
         instance_map, id_to_semantic = self._instance_map(torch.from_numpy(mask).to(self.device), dsize)
-        return _assemble_item(self.processor, image, instance_map.cpu().numpy(), id_to_semantic, target_size, file_name)
+        return _assemble_item(self.processor, image, instance_map.cpu().numpy(), id_to_semantic, target_size, file_name,
+                              self.augment, self.generator)
 
 
-def _assemble_item(processor, image, instance_map: np.ndarray, id_to_semantic: dict, target_size, file_name) -> dict:
+def _assemble_item(processor, image, instance_map: np.ndarray, id_to_semantic: dict, target_size, file_name,
+                   augment=None, generator=None) -> dict:
     """The item every reference loader returns: the processor's outputs for one image and its (H, W) int32 instance map
-    (255 = ignore), with the map itself, the id dict, the target size and the file name."""
+    (255 = ignore), with the map itself, the id dict, the target size and the file name.
+    With `augment` (a TrainAugmentation) the parameters are drawn here for the loaded image from
+    `generator`, `target_size` becomes the drawn window and the item also carries the parameters under "augment";
+    `original_map` and `id_to_semantic` still describe the file."""
+    call, extra = {}, {}
+    if augment is not None:
+        params = augment.sample(instance_map.shape[0], instance_map.shape[1], generator)
+        call = {"augment": params, "pad_size": augment.pad_size}
+        extra = {"augment": params}
+        target_size = params.window
     inputs = processor(images=[image], segmentation_maps=[instance_map], instance_id_to_semantic_id=id_to_semantic,
-                       return_tensors="pt", ignore_index=255)
+                       return_tensors="pt", ignore_index=255, **call)
     return {
+        **extra,
         "pixel_values": inputs["pixel_values"][0],
         "mask_labels": inputs["mask_labels"][0],
         "class_labels": inputs["class_labels"][0],
@@ -406,13 +419,14 @@ class SorghumWeedDataset(torch.utils.data.Dataset):
     `max_input_dim` and `max_images` stand for config.MAX_INPUT_DIM and config.MAX_IMAGES."""
 
     def __init__(self, image_folder_path, annotation_path, processor, label2id: dict, max_input_dim: int = 1024,
-                 max_images=None, device="cuda"):
+                 max_images=None, device="cuda", augment=None, generator=None):
         import json
         self.image_folder = image_folder_path
         self.processor = processor
         self.label2id = label2id
         self.max_input_dim = int(max_input_dim)
         self.device = torch.device(device)
+        self.augment, self.generator = augment, generator  # a TrainAugmentation and its CPU torch.Generator, or None
         with open(annotation_path, "r") as f:
             self.data = list(json.load(f).values())
         self.valid_entries = []
@@ -432,7 +446,8 @@ class SorghumWeedDataset(torch.utils.data.Dataset):
         width, height = image.size
         polygons, ids, id_to_semantic = _via_polygons(entry, self.label2id, scale, scale, skip_255=True)
         instance_map = polygons_to_instance_map(polygons, ids, (height, width), 255, self.device).cpu().numpy()
-        return _assemble_item(self.processor, image, instance_map, id_to_semantic, (height, width), entry["filename"])
+        return _assemble_item(self.processor, image, instance_map, id_to_semantic, (height, width), entry["filename"],
+                              self.augment, self.generator)
 
 
 class CropWeedYamlDataset(torch.utils.data.Dataset):
@@ -440,7 +455,7 @@ class CropWeedYamlDataset(torch.utils.data.Dataset):
     GPU.  `annotation_path` is a folder of `*.yaml` files (sorted); each names its image with the 'filename' key."""
 
     def __init__(self, image_folder_path, annotation_path, processor, label2id: dict, max_input_dim: int = 1024,
-                 max_images=None, device="cuda"):
+                 max_images=None, device="cuda", augment=None, generator=None):
         import yaml
         self.image_folder = image_folder_path
         self.annotation_path = annotation_path
@@ -448,6 +463,7 @@ class CropWeedYamlDataset(torch.utils.data.Dataset):
         self.label2id = label2id
         self.max_input_dim = int(max_input_dim)
         self.device = torch.device(device)
+        self.augment, self.generator = augment, generator  # a TrainAugmentation and its CPU torch.Generator, or None
         yaml_files = sorted(glob.glob(os.path.join(self.annotation_path, "*.yaml")))
         self.valid_files = []
         print(f'Scanning {len(yaml_files)} annotation files in "{self.annotation_path}"...')
@@ -482,7 +498,7 @@ class CropWeedYamlDataset(torch.utils.data.Dataset):
         polygons, ids, id_to_semantic = _cwfid_polygons(annotation, self.label2id, scale)
         instance_map = polygons_to_instance_map(polygons, ids, (height, width), 255, self.device).cpu().numpy()
         return _assemble_item(self.processor, image, instance_map, id_to_semantic, (height, width),
-                              os.path.basename(image_path))
+                              os.path.basename(image_path), self.augment, self.generator)
 
 
 def load_ground_truth(image_name: str, target_size: tuple, annotation_file: str, img_dir: str, label2id: dict,

@@ -1782,6 +1782,54 @@ def resize_nearest_labels(maps: torch.Tensor, desc, tables: torch.Tensor, Hp: in
     return out, present
 
 
+# ------------------------------------------------------------- training augmentation
+def augment_resize_normalize_u8(images: torch.Tensor, desc, tables: torch.Tensor, lut: torch.Tensor, Hp: int, Wp: int):
+    """Flip, resize and crop of packed uint8 HWC images (flat, on the device) in one launch
+    (wm2f_augment_resize_normalize_u8): (pixel_values (B, 3, Hp, Wp) float32, pixel_mask (B, Hp, Wp) int64), bit for bit
+    what `resize_normalize_u8` makes of the mirrored image, cut to the window and padded.  `desc` is a host int64 array
+    (B, 16): in_off, H, W, h, w, tx, cx, kx, ty, cy, ky, flip, y0, x0, ch, cw; `tables` holds the whole tables of the
+    (H, W) -> (h, w) resize.  No workspace: the (h, w) frame is never stored."""
+    import numpy as np
+    images, tables, lut = _req(images, "images", torch.uint8), _req(tables, "tables", torch.int32), _req(lut, "lut", torch.float32)
+    d = np.ascontiguousarray(desc, dtype=np.int64)
+    if d.ndim != 2 or d.shape[1] != _lib.WM2F_AUG_PRE_DESC_LEN:
+        raise ValueError(f"desc: expected (B, {_lib.WM2F_AUG_PRE_DESC_LEN}), got {d.shape}")
+    B = int(d.shape[0])
+    dev = images.device
+    pv = torch.empty(B, 3, Hp, Wp, device=dev, dtype=torch.float32)
+    pm = torch.empty(B, Hp, Wp, device=dev, dtype=torch.int64)
+    with torch.cuda.device(dev):
+        check(load().wm2f_augment_resize_normalize_u8(
+            _p(images), images.numel(), d.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _p(tables), tables.numel(),
+            _p(lut), _p(pv), _p(pm), B, Hp, Wp, _stream(images)), "wm2f_augment_resize_normalize_u8")
+    return pv, pm
+
+
+def augment_nearest_labels(maps: torch.Tensor, desc, tables: torch.Tensor, Hp: int, Wp: int, ignore_index: int):
+    """Flip, nearest resize and crop of packed uint8 or int32 id maps (wm2f_augment_nearest_labels): (maps (B, Hp, Wp)
+    int32 padded with `ignore_index`, present (B, 256) uint8 flags of the id values inside each window).  `desc` is a
+    host int64 array (B, 12): in_off, H, W, h, w, xi, yi, flip, y0, x0, ch, cw."""
+    import numpy as np
+    if not maps.is_cuda:
+        raise _lib.Wm2fError(f"maps is on {maps.device}: the wm2f kernels run on a GPU only (no CPU fallback)")
+    if maps.dtype not in (torch.uint8, torch.int32):
+        raise TypeError(f"maps must be uint8 or int32, got {maps.dtype}")
+    dtype = _lib.WM2F_U8 if maps.dtype == torch.uint8 else _lib.WM2F_I32
+    tables = _req(tables, "tables", torch.int32)
+    d = np.ascontiguousarray(desc, dtype=np.int64)
+    if d.ndim != 2 or d.shape[1] != _lib.WM2F_AUG_LAB_DESC_LEN:
+        raise ValueError(f"desc: expected (B, {_lib.WM2F_AUG_LAB_DESC_LEN}), got {d.shape}")
+    B = int(d.shape[0])
+    out = torch.empty(B, Hp, Wp, device=maps.device, dtype=torch.int32)
+    present = torch.empty(B, 256, device=maps.device, dtype=torch.uint8)
+    with torch.cuda.device(maps.device):
+        check(load().wm2f_augment_nearest_labels(
+            _p(maps.contiguous()), dtype, maps.numel(), d.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _p(tables),
+            tables.numel(), _p(out), _p(present), B, Hp, Wp, int(ignore_index), _stream(maps)),
+            "wm2f_augment_nearest_labels")
+    return out, present
+
+
 # ------------------------------------------------------------- connected components of class maps (DESIGN section 16)
 _CCL_DTYPES = {torch.uint8: _lib.WM2F_U8, torch.bool: _lib.WM2F_U8, torch.uint16: _lib.WM2F_U16,
                torch.int32: _lib.WM2F_I32}

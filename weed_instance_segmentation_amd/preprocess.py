@@ -278,7 +278,11 @@ class Mask2FormerImageProcessor(Mask2FormerInstancePostProcessor):
         return self.preprocess(images, segmentation_maps, instance_id_to_semantic_id, **kwargs)
 
     def preprocess(self, images, segmentation_maps=None, instance_id_to_semantic_id=None, return_tensors="pt",
-                   device="cuda", mask_dtype: torch.dtype = torch.float32, **overrides) -> BatchFeature:
+                   device="cuda", mask_dtype: torch.dtype = torch.float32, augment=None, **overrides) -> BatchFeature:
+        """`augment`: None, one `AugmentParams` for every image or a list with one per image.  With
+        parameters each image is mirrored (flip), resized to the parameters' own (h, w) -- `size` and `size_divisor` do
+        not apply -- and cut to the window; `pad_size` defaults to the batch's largest window.  The call stays
+        deterministic: the draws are `TrainAugmentation.sample`'s."""
         unknown = set(overrides) - set(_SETTINGS)
         if unknown:
             raise TypeError(f"unexpected keyword arguments {sorted(unknown)}")
@@ -296,6 +300,14 @@ class Mask2FormerImageProcessor(Mask2FormerInstancePostProcessor):
         if not ims:
             raise ValueError("images is empty")
         ims = [_image_hwc_u8(im, i) for i, im in enumerate(ims)]
+        augs = None
+        if augment is not None:
+            from .augment import AugmentParams
+            augs = list(augment) if isinstance(augment, (list, tuple)) else [augment] * len(ims)
+            if len(augs) != len(ims) or not all(isinstance(a, AugmentParams) for a in augs):
+                raise ValueError(f"augment: expected one AugmentParams or a list of {len(ims)}, one per image")
+            if not s["do_resize"]:
+                raise ValueError("augment needs do_resize=True: the parameters carry the resized size")
         maps = None
         if segmentation_maps is not None:
             maps = list(segmentation_maps) if isinstance(segmentation_maps, (list, tuple)) else [segmentation_maps]
@@ -314,7 +326,12 @@ class Mask2FormerImageProcessor(Mask2FormerInstancePostProcessor):
             dev = torch.device("cuda", torch.cuda.current_device())
 
         sizes_in = [tuple(int(v) for v in im.shape[:2]) for im in ims]
-        sizes_out = [output_size(H, W, s["size"], s["size_divisor"]) if s["do_resize"] else (H, W) for H, W in sizes_in]
+        if augs is not None:
+            frames = [a.size for a in augs]
+            sizes_out = [a.window for a in augs]  # what the image occupies in the padded output
+        else:
+            sizes_out = [output_size(H, W, s["size"], s["size_divisor"]) if s["do_resize"] else (H, W)
+                         for H, W in sizes_in]
         if s["pad_size"] is not None:
             ps = s["pad_size"]
             Hp, Wp = (int(ps["height"]), int(ps["width"])) if isinstance(ps, dict) else (int(ps[0]), int(ps[1]))
@@ -336,12 +353,18 @@ class Mask2FormerImageProcessor(Mask2FormerInstancePostProcessor):
             n_tab += a.size
             return off
 
-        desc = np.zeros((B, 12), dtype=np.int64)
-        ldesc = np.zeros((B, 7), dtype=np.int64)
+        desc = np.zeros((B, 12 if augs is None else 16), dtype=np.int64)
+        ldesc = np.zeros((B, 7 if augs is None else 12), dtype=np.int64)
         ws_off = 0
-        for b, ((H, W), (h, w)) in enumerate(zip(sizes_in, sizes_out)):
+        for b, ((H, W), (h, w)) in enumerate(zip(sizes_in, sizes_out if augs is None else frames)):
             bx, cx = bilinear_tables(W, w)
             by, cy = bilinear_tables(H, h)
+            if augs is not None:  # whole tables of the (h, w) frame; the kernels index them at the window's origin
+                win = [augs[b].flip, *augs[b].origin, *augs[b].window]
+                desc[b, 1:] = [H, W, h, w, put(bx), put(cx), cx.shape[1], put(by), put(cy), cy.shape[1], *win]
+                if maps is not None:
+                    ldesc[b, 1:] = [H, W, h, w, put(nearest_table(W, w)), put(nearest_table(H, h)), *win]
+                continue
             desc[b, 1:] = [ws_off, H, W, h, w, put(bx), put(cx), cx.shape[1], put(by), put(cy), cy.shape[1]]
             ws_off += H * w * 3
             if maps is not None:
@@ -382,7 +405,10 @@ class Mask2FormerImageProcessor(Mask2FormerInstancePostProcessor):
         desc[:, 0] = img_off[:-1]
         t_tab = buf[:tables.nbytes].view(torch.int32)
         t_lut = buf[o_lut:o_lut + lut.nbytes].view(torch.float32)
-        pv, pm = ops.resize_normalize_u8(buf[o_img:o_img + int(img_off[-1])], desc, t_tab, t_lut, Hp, Wp)
+        if augs is None:
+            pv, pm = ops.resize_normalize_u8(buf[o_img:o_img + int(img_off[-1])], desc, t_tab, t_lut, Hp, Wp)
+        else:
+            pv, pm = ops.augment_resize_normalize_u8(buf[o_img:o_img + int(img_off[-1])], desc, t_tab, t_lut, Hp, Wp)
         out = BatchFeature(pixel_values=pv, pixel_mask=pm)
         if maps is None:
             return out
@@ -390,8 +416,9 @@ class Mask2FormerImageProcessor(Mask2FormerInstancePostProcessor):
         # labels: nearest resize + presence flags, one flag copy, masks per image
         ig = s["ignore_index"]
         ldesc[:, 0] = map_off[:-1]
-        lab, present = ops.resize_nearest_labels(buf[o_map:o_map + int(map_off[-1])], ldesc, t_tab, Hp, Wp,
-                                                 255 if ig is None else int(ig))
+        resize_labels = ops.resize_nearest_labels if augs is None else ops.augment_nearest_labels
+        lab, present = resize_labels(buf[o_map:o_map + int(map_off[-1])], ldesc, t_tab, Hp, Wp,
+                                     255 if ig is None else int(ig))
         flags = present.cpu().numpy()
         id_maps = instance_id_to_semantic_id
         mask_labels, class_labels = [], []
