@@ -627,6 +627,29 @@ int wm2f_coco_match(const int32_t* inter, const int32_t* det_area, const int32_t
                     uint8_t* det_ignored, uint8_t* gt_ignored, int B, int D, int G, int T, int A, int max_det,
                     void* stream);
 
+/* ---- per-instance statistics of id maps on device ---------------------------------------
+ * Area, bounding box and coordinate sums of every instance of B id maps, in one read of the maps: what a consumer of
+ * post_process_instance_segmentation's map (counts, targets, box mAP) otherwise takes with one `map == id` pass per
+ * instance.
+ * wm2f_labelmap_instance_stats: map (B, H, W) is WM2F_F32 (ids as floats, -1 background: the post-processor's output;
+ *                         a value counts as the integer it equals, +-0 as 0, and a value that is negative, fractional,
+ *                         not finite or >= 2^24 as no id), WM2F_I32 or WM2F_U8.
+ *                         ids == NULL (then n_ids == NULL): row r of the result is id r, r in [0, N); every other
+ *                         value is ignored.  Otherwise ids (B, N) int32 DEVICE, ascending, n_ids (B) int32 DEVICE of
+ *                         them valid per image (the GT form of wm2f_labelmap_pair_counts): row r is the raw id
+ *                         ids[b][r]; rows at or beyond n_ids[b] are empty, raw ids not listed are ignored.
+ *                         stats (B, N, 8) int64, overwritten: [area, xmin, ymin, xmax, ymax, sum_x, sum_y, 0] with
+ *                         xmax / ymax inclusive pixel indices; an id without a pixel gets [0, W, H, -1, -1, 0, 0, 0].
+ *                         All integer: the result does not depend on the order of accumulation and is bit-identical
+ *                         from run to run.  H, W <= 16384, B <= 32, N <= 4096, else WM2F_EUNSUPPORTED.
+ *                         A workgroup owns a strip of whole rows and keeps its accumulators in LDS while N <= 1024
+ *                         (32 B per id, and 4 B per listed id: 36 KiB at the cap, four workgroups per CU), flushing the
+ *                         ids it saw with 64-bit integer atomics; above that it accumulates into stats directly.  Rows
+ *                         are read four pixels per lane when W % 4 == 0 and the map is 16-byte (uint8: 4-byte) aligned,
+ *                         pixel by pixel otherwise, with the same results. */
+int wm2f_labelmap_instance_stats(const void* map, int dtype, const int32_t* ids, const int32_t* n_ids, int64_t* stats,
+                                 int B, int H, int W, int N, void* stream);
+
 /* ---- image preprocessing on device ---------------------------------------------------
  * The tensor work of Mask2FormerImageProcessorPil._preprocess (image_processing_pil_mask2former.py:485-585), bit-exact.
  * wm2f_resize_normalize_u8: B packed uint8 HWC RGB images of different sizes -> pixel_values (B, 3, Hp, Wp) float32 and

@@ -12,5 +12,6 @@ from .modeling import Mask2FormerForUniversalSegmentation, Mask2FormerForUnivers
 __version__ = "0.1.0"
 from .postprocess import Mask2FormerInstancePostProcessor  # noqa: F401
 from .metrics import MeanAveragePrecision  # noqa: F401
+from .instances import instance_statistics  # noqa: F401
 from .preprocess import Mask2FormerImageProcessor  # noqa: F401
 from .augment import AugmentParams, TrainAugmentation  # noqa: F401

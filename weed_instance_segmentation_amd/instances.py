@@ -1,0 +1,66 @@
+"""Per-instance area, bounding box and centroid of id maps on the GPU.
+
+    from weed_instance_segmentation_amd import instance_statistics
+    area, bbox, centroid = instance_statistics(prediction["segmentation"], n=len(prediction["segments_info"]))
+
+One launch of csrc/instance_stats.hip reads the map once, whatever the number of instances; nothing is copied to the
+host.  `post_process_instance_segmentation(..., return_instance_stats=True)` and the box mAP of `metrics.py` are built
+on the same kernel.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+
+
+def stats_to_boxes(stats: torch.Tensor):
+    """(..., N, 8) int64 rows of `ops.labelmap_instance_stats` -> area (..., N) int64, bbox (..., N, 4) int64 COCO
+    [x, y, w, h] with w = xmax - xmin + 1 (pycocotools' toBbox of the mask; an empty instance [0, 0, 0, 0]), centroid
+    (..., N, 2) float64 (sum_x / area, sum_y / area), NaN for an empty instance.  Works on either device."""
+    area = stats[..., 0]
+    some = (area > 0).unsqueeze(-1)
+    xywh = torch.stack([stats[..., 1], stats[..., 2], stats[..., 3] - stats[..., 1] + 1, stats[..., 4] - stats[..., 2] + 1], -1)
+    bbox = torch.where(some, xywh, torch.zeros_like(xywh))
+    centroid = stats[..., 5:7].to(torch.float64) / area.to(torch.float64).unsqueeze(-1)  # 0 / 0 = NaN
+    return area, bbox, centroid
+
+
+def instance_statistics(segmentation, n: int | None = None, ids=None):
+    """Area, box and centroid of every instance of one (H, W) id map or a (B, H, W) stack -- fp32 with -1 background
+    (the post-processor's map), int32 or uint8, on the device or the host (a host map is moved to the current GPU).
+
+    - `n`: the instances are the ids 0 .. n-1, as the post-processor numbers them.
+    - `ids`: a list of raw ids (one list for every map of a stack), any order; the results follow it.
+    Returns device tensors (area (..., N) int64, bbox (..., N, 4) int64 COCO [x, y, w, h], centroid (..., N, 2) float64):
+    an id without a pixel has area 0, box [0, 0, 0, 0] and a NaN centroid."""
+    if (n is None) == (ids is None):
+        raise ValueError("instance_statistics: give either n (ids 0 .. n-1) or ids")
+    if not torch.cuda.is_available():
+        raise _lib.Wm2fError("instance_statistics runs on a GPU only (no CPU fallback): no device is visible")
+    seg = torch.from_numpy(np.ascontiguousarray(segmentation)) if isinstance(segmentation, np.ndarray) else torch.as_tensor(segmentation)
+    if seg.dim() not in (2, 3):
+        raise ValueError(f"instance_statistics: expected (H, W) or (B, H, W), got {tuple(seg.shape)}")
+    if seg.dtype not in (torch.float32, torch.int32, torch.uint8):
+        raise TypeError(f"instance_statistics: maps fp32 / int32 / uint8, got {seg.dtype}")
+    dev = seg.device if seg.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    maps = seg.to(dev)
+    maps = maps.unsqueeze(0) if seg.dim() == 2 else maps
+    B = maps.shape[0]
+    if ids is None:
+        stats = ops.labelmap_instance_stats(maps, N=int(n))
+    else:
+        raw = [int(v) for v in ids]
+        order = sorted(set(raw))
+        if len(order) != len(raw):
+            raise ValueError("instance_statistics: ids must be distinct")
+        N = max(1, len(order))
+        ids_t = torch.tensor(order + [0] * (N - len(order)), dtype=torch.int32).expand(B, N).contiguous().to(dev)
+        n_ids = torch.full((B,), len(order), dtype=torch.int32).to(dev)
+        stats = ops.labelmap_instance_stats(maps, ids_t, n_ids)
+        back = torch.tensor([order.index(v) for v in raw], dtype=torch.int64).to(dev)  # the caller's order
+        stats = stats[:, back]
+    if seg.dim() == 2:
+        stats = stats[0]
+    return stats_to_boxes(stats)

@@ -11,6 +11,11 @@ Two routes in:
   - `update(preds, target)`: torchmetrics' dictionaries of (N, H, W) mask stacks (bit-packed, AND + popcount);
   - `update_from_maps(...)`: the post-processor's id maps and the dataset's raw GT maps, one joint histogram per
     image -- what `test_with_metrics` uses; no mask stack is ever built.
+
+`iou_type="bbox"` (or both types at once) with `boxes_from_masks=True` evaluates the boxes cut from the same maps -- COCOeval with iouType "bbox" on
+the tight box of every prediction and GT mask -- on the label-map route: one launch of
+csrc/instance_stats.hip per map stack gives the boxes, their integer intersections and areas go through the same
+matching kernel.
 """
 from __future__ import annotations
 
@@ -32,6 +37,39 @@ def _device() -> torch.device:
         raise _lib.Wm2fError("MeanAveragePrecision runs on a GPU only (no CPU fallback): no device is visible")
     _lib.load()
     return torch.device("cuda", torch.cuda.current_device())
+
+
+IOU_TYPES = ("segm", "bbox")
+
+
+def box_pair_counts(pred_stats: torch.Tensor, gt_stats: torch.Tensor):
+    """Box intersections and areas from `ops.labelmap_instance_stats` rows: pred_stats (B, P, 8), gt_stats (B, G, 8) int64
+    -> inter (B, P, G), det_area (B, P), gt_area (B, G) int32.  The boxes have integer corners (xmax / ymax inclusive), so
+    the counts are exact and go to the matching as pixel counts do; an empty instance has area 0 and meets nothing."""
+    def corners(st):
+        return st[..., 1], st[..., 2], st[..., 3] + 1, st[..., 4] + 1  # half-open; empty: x0 = W > x1 = 0
+
+    px0, py0, px1, py1 = (c.unsqueeze(2) for c in corners(pred_stats))
+    gx0, gy0, gx1, gy1 = (c.unsqueeze(1) for c in corners(gt_stats))
+    iw = (torch.minimum(px1, gx1) - torch.maximum(px0, gx0)).clamp(min=0)
+    ih = (torch.minimum(py1, gy1) - torch.maximum(py0, gy0)).clamp(min=0)
+
+    def area(st):
+        x0, y0, x1, y1 = corners(st)
+        return ((x1 - x0).clamp(min=0) * (y1 - y0).clamp(min=0)).to(torch.int32)
+
+    return (iw * ih).to(torch.int32), area(pred_stats), area(gt_stats)
+
+
+def merge_results(per_type: dict) -> dict:
+    """One type: its result as it is.  Several: every name prefixed `bbox_` / `segm_`, `classes` once, unprefixed."""
+    if len(per_type) == 1:
+        return next(iter(per_type.values()))
+    out = {}
+    for kind, res in per_type.items():
+        out.update({f"{kind}_{k}": v for k, v in res.items() if k != "classes"})
+    out["classes"] = next(iter(per_type.values()))["classes"]
+    return out
 
 
 class _Records:
@@ -111,11 +149,21 @@ def summarize(precision, recall, max_dets) -> dict:
 
 
 class MeanAveragePrecision:
-    """torchmetrics.detection.MeanAveragePrecision(iou_type="segm") on the GPU: update / compute / reset."""
+    """torchmetrics.detection.MeanAveragePrecision on the GPU: update / compute / reset.  iou_type "segm", "bbox" or a
+    tuple / list of both.  torchmetrics' "bbox" scores boxes the caller supplies; those are not implemented, so "bbox"
+    alone still raises.  `boxes_from_masks=True` selects what is: the tight box of every prediction and GT mask, cut from
+    the id maps of `update_from_maps`."""
 
-    def __init__(self, iou_type="segm", max_detection_thresholds=None, class_metrics: bool = False):
-        if iou_type != "segm":
-            raise ValueError(f"iou_type={iou_type!r}: only 'segm' is implemented")
+    def __init__(self, iou_type="segm", max_detection_thresholds=None, class_metrics: bool = False,
+                 boxes_from_masks: bool = False):
+        types = (iou_type,) if isinstance(iou_type, str) else tuple(iou_type) if isinstance(iou_type, (tuple, list)) else None
+        if not types or any(t not in IOU_TYPES for t in types) or len(set(types)) != len(types):
+            raise ValueError(f"iou_type={iou_type!r}: expected 'segm', 'bbox' or a tuple of both")
+        if "bbox" in types and not boxes_from_masks:
+            raise ValueError(f"iou_type={iou_type!r}: boxes supplied by the caller are not implemented; pass "
+                             "boxes_from_masks=True to evaluate the tight boxes of the masks (update_from_maps)")
+        self.iou_type = types
+        self.boxes_from_masks = bool(boxes_from_masks)
         md = [1, 10, 100] if max_detection_thresholds is None else [int(v) for v in max_detection_thresholds]
         if len(md) != 3 or sorted(md) != md or md[0] < 1:
             raise ValueError(f"max_detection_thresholds must be a sorted list of three positive ints, got {md}")
@@ -125,7 +173,7 @@ class MeanAveragePrecision:
         self.reset()
 
     def reset(self) -> None:
-        self._batches = []  # device records, one dict per update call
+        self._batches = {t: [] for t in self.iou_type}  # per type the device records, one dict per update call
 
     # ---------------------------------------------------------------------------------------------- update routes
     def _constants(self, dev):
@@ -134,18 +182,21 @@ class MeanAveragePrecision:
             self._rng = torch.tensor(AREA_RANGES, dtype=torch.float64).to(dev)
         return self._thr, self._rng
 
-    def _match(self, dev, inter, det_area, gt_area, det_score, det_label, gt_label, n_det, n_gt):
-        """All (B, D[, G]) device tensors, padded; launches the matching and stores the records."""
+    def _match(self, dev, inter, det_area, gt_area, det_score, det_label, gt_label, n_det, n_gt, kind="segm"):
+        """All (B, D[, G]) device tensors, padded; launches the matching and stores the records of type `kind`."""
         order = torch.sort(det_score, dim=1, descending=True, stable=True).indices.to(torch.int32)
         thr, rng = self._constants(dev)
         rank, matched, ignored, gt_ig = ops.coco_match(inter, det_area, gt_area, det_label, gt_label, order, n_det, n_gt,
                                                        thr, rng, self.max_detection_thresholds[-1])
-        self._batches.append({"n_det": n_det, "n_gt": n_gt, "score": det_score, "label": det_label, "rank": rank,
+        self._batches[kind].append({"n_det": n_det, "n_gt": n_gt, "score": det_score, "label": det_label, "rank": rank,
                               "matched": matched, "ignored": ignored, "gt_label": gt_label, "gt_ignored": gt_ig})
 
     def update(self, preds: list[dict], target: list[dict]) -> None:
         """torchmetrics' format: preds [{"masks" (D, H, W) bool, "scores" (D), "labels" (D)}], target [{"masks" (G, H, W),
         "labels" (G)}].  Host tensors are moved to the GPU."""
+        if "bbox" in self.iou_type:
+            raise ValueError("iou_type 'bbox' evaluates the boxes of id maps: use update_from_maps (free-standing boxes "
+                             "and mask stacks are not implemented for it)")
         if len(preds) != len(target):
             raise ValueError("preds and target must have the same length")
         dev = _device()
@@ -237,9 +288,12 @@ class MeanAveragePrecision:
         n_ids = torch.tensor([len(x) for x in gt_ids], dtype=torch.int32).to(dev)
         n_det = torch.tensor([len(x) for x in scores], dtype=torch.int32).to(dev)
         ids_t, cls_t, score_t, label_t = ids_t.to(dev), cls_t.to(dev), score_t.to(dev), label_t.to(dev)
+        segm, bbox = "segm" in self.iou_type, "bbox" in self.iou_type
         inter = torch.empty(B, P, G, device=dev, dtype=torch.int32)
         det_area = torch.empty(B, P, device=dev, dtype=torch.int32)
         gt_area = torch.empty(B, G, device=dev, dtype=torch.int32)
+        binter, bdet_area, bgt_area = (torch.empty_like(t) for t in (inter, det_area, gt_area))
+        present = torch.empty(B, G, device=dev, dtype=torch.bool)  # the GT id has a pixel in its map
         groups: dict = {}
         for i in range(B):  # one launch per (size, prediction dtype, GT dtype)
             groups.setdefault((tuple(preds[i].shape), preds[i].dtype, gts[i].dtype), []).append(i)
@@ -247,21 +301,32 @@ class MeanAveragePrecision:
             pm = torch.stack([preds[i].to(dev) for i in rows])
             gm = torch.stack([gts[i].to(dev) for i in rows])  # each host map copied once, stacked on the device
             ridx = torch.tensor(rows, device=dev)
-            hist = ops.labelmap_pair_counts(pm, gm, ids_t[ridx].contiguous(), n_ids[ridx].contiguous(), P)
-            inter[ridx] = hist[:, 1:, 1:]
-            det_area[ridx] = hist[:, 1:, :].sum(2, dtype=torch.int32)
-            gt_area[ridx] = hist[:, :, 1:].sum(1, dtype=torch.int32)
-        cls_t = torch.where(gt_area > 0, cls_t, torch.full_like(cls_t, ABSENT))
-        self._match(dev, inter, det_area, gt_area, score_t, label_t, cls_t, n_det, n_ids)
+            gids, gn = ids_t[ridx].contiguous(), n_ids[ridx].contiguous()
+            if segm:
+                hist = ops.labelmap_pair_counts(pm, gm, gids, gn, P)
+                inter[ridx] = hist[:, 1:, 1:]
+                det_area[ridx] = hist[:, 1:, :].sum(2, dtype=torch.int32)
+                gt_area[ridx] = hist[:, :, 1:].sum(1, dtype=torch.int32)
+                present[ridx] = gt_area[ridx] > 0
+            if bbox:  # the boxes of the same masks: ids 0 .. P-1 of the prediction map, the listed raw ids of the GT map
+                gstats = ops.labelmap_instance_stats(gm, gids, gn)
+                binter[ridx], bdet_area[ridx], bgt_area[ridx] = box_pair_counts(ops.labelmap_instance_stats(pm, N=P), gstats)
+                present[ridx] = gstats[:, :, 0] > 0
+        cls_t = torch.where(present, cls_t, torch.full_like(cls_t, ABSENT))
+        if segm:
+            self._match(dev, inter, det_area, gt_area, score_t, label_t, cls_t, n_det, n_ids)
+        if bbox:  # COCOeval with iouType "bbox": the area ranges see box areas on both sides
+            self._match(dev, binter, bdet_area, bgt_area, score_t, label_t, cls_t, n_det, n_ids, kind="bbox")
 
     # ------------------------------------------------------------------------------------------------- compute
-    def _records(self) -> _Records:
-        """The one device-to-host copy of every image's records."""
-        if not self._batches:
+    def _records(self, kind: str | None = None) -> _Records:
+        """The one device-to-host copy of every image's records of one type."""
+        batches = self._batches[self.iou_type[0] if kind is None else kind]
+        if not batches:
             return _Records(*(np.zeros(0, np.int64),) * 4, np.zeros((4, 10, 0), bool), np.zeros((4, 10, 0), bool),
                             np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros((4, 0), bool), 0)
         parts, meta = [], []
-        for r in self._batches:
+        for r in batches:
             for k in ("n_det", "n_gt", "score", "label", "rank", "matched", "ignored", "gt_label", "gt_ignored"):
                 t = r[k].contiguous()
                 meta.append((k, t.dtype, tuple(t.shape), t.numel() * t.element_size()))
@@ -310,12 +375,19 @@ class MeanAveragePrecision:
         return res
 
     def compute(self) -> dict:
-        return self._compute(self._records())
+        return merge_results({kind: self._compute(self._records(kind)) for kind in self.iou_type})
 
-    def compute_per_image(self) -> torch.Tensor:
+    def compute_per_image(self, iou_type: str | None = None) -> torch.Tensor:
         """(N,) float32: entry i is the `map` of a fresh metric updated with image i alone (show_worst_predictions.py's
-        ranking), from the stored records -- nothing is matched again."""
-        rec = self._records()
+        ranking), from the stored records -- nothing is matched again.  With two types, `iou_type` names the one to
+        rank by."""
+        if iou_type is None:
+            if len(self.iou_type) > 1:
+                raise ValueError(f"compute_per_image: name the iou_type to rank by, one of {self.iou_type}")
+            iou_type = self.iou_type[0]
+        if iou_type not in self.iou_type:
+            raise ValueError(f"compute_per_image: iou_type={iou_type!r} is not evaluated by this metric {self.iou_type}")
+        rec = self._records(iou_type)
         out = []
         for i in range(rec.n_images):
             sub = rec.subset(i)
@@ -325,10 +397,12 @@ class MeanAveragePrecision:
 
 
 # --------------------------------------------------------------------------- drop-ins for models/metrics.py
-def test_with_metrics(model, processor, data_loader, device) -> dict:
-    """models/metrics.py::test_with_metrics with the same arguments and result, through the label-map route."""
+def test_with_metrics(model, processor, data_loader, device, iou_type="segm") -> dict:
+    """models/metrics.py::test_with_metrics with the same arguments and result, through the label-map route.
+    `iou_type` (not an argument of the reference) goes to MeanAveragePrecision: "segm", "bbox" or both; the boxes are
+    those of the masks (`boxes_from_masks=True`), as this route has nothing else."""
     model.eval()
-    metric = MeanAveragePrecision(iou_type="segm")
+    metric = MeanAveragePrecision(iou_type=iou_type, boxes_from_masks=iou_type != "segm")
     print("Calculating Metrics...")
     for i, batch in enumerate(data_loader):
         if (i + 1) % 5 == 0:
@@ -359,8 +433,13 @@ def print_metrics_evaluation(metrics_evaluation: dict, model_name: str = "Model"
         v = metrics_evaluation.get(key, torch.tensor(-1))
         return v.item() if v.numel() == 1 else -1
 
-    for label, key in (("mAP:           ", "map"), ("mAP (IoU=0.50):", "map_50"), ("mAP (IoU=0.75):", "map_75")):
-        print(f"  {label} {100 * scalar(key):.2f} %")
+    kinds = [k for k in IOU_TYPES if f"{k}_map" in metrics_evaluation]  # both types: one block each
+    for kind in kinds or [None]:
+        if kind is not None:
+            print(f"  [{kind}]")
+        pre = "" if kind is None else f"{kind}_"
+        for label, key in (("mAP:           ", "map"), ("mAP (IoU=0.50):", "map_50"), ("mAP (IoU=0.75):", "map_75")):
+            print(f"  {label} {100 * scalar(pre + key):.2f} %")
 
 
 def prepare_metrics_for_json(results: dict) -> dict | None:

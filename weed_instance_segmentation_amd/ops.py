@@ -1738,6 +1738,43 @@ def coco_match(inter, det_area, gt_area, det_label, gt_label, det_order, n_det, 
     return det_rank, det_matched, det_ignored, gt_ignored
 
 
+# ------------------------------------------------------------------- per-instance statistics
+def labelmap_instance_stats(maps: torch.Tensor, ids: torch.Tensor | None = None, n_ids: torch.Tensor | None = None,
+                            N: int | None = None) -> torch.Tensor:
+    """(B, H, W) id maps (fp32 with -1 background, int32 or uint8) -> (B, N, 8) int64
+    [area, xmin, ymin, xmax, ymax, sum_x, sum_y, 0] per id (wm2f_labelmap_instance_stats), xmax / ymax inclusive, an id
+    without a pixel [0, W, H, -1, -1, 0, 0, 0].  Without `ids`, row r is id r of [0, N).  With `ids` (B, N) int32
+    ascending and `n_ids` (B) of them valid, row r is the raw id ids[b][r]."""
+    if not isinstance(maps, torch.Tensor):
+        raise TypeError("labelmap_instance_stats: expected tensors")
+    maps = _req(maps, "maps", maps.dtype)
+    dt = {torch.float32: _lib.WM2F_F32, torch.int32: _lib.WM2F_I32, torch.uint8: _lib.WM2F_U8}.get(maps.dtype)
+    if dt is None:
+        raise TypeError(f"labelmap_instance_stats: maps fp32 / int32 / uint8, got {maps.dtype}")
+    if maps.dim() != 3:
+        raise ValueError(f"labelmap_instance_stats: maps must be (B, H, W), got {tuple(maps.shape)}")
+    B, H, W = (int(v) for v in maps.shape)
+    if (ids is None) != (n_ids is None):
+        raise ValueError("labelmap_instance_stats: ids and n_ids go together")
+    if ids is not None:
+        ids, n_ids = _req(ids, "ids", torch.int32), _req(n_ids, "n_ids", torch.int32)
+        if ids.dim() != 2 or ids.shape[0] != B or n_ids.shape != (B,) or (N is not None and int(N) != ids.shape[1]):
+            raise ValueError("labelmap_instance_stats: shapes disagree")
+        N = int(ids.shape[1])
+    elif N is None:
+        raise ValueError("labelmap_instance_stats: N is needed without an id list")
+    N = int(N)
+    if N < 0 or B == 0 or H == 0 or W == 0:
+        raise ValueError("labelmap_instance_stats: bad size")
+    stats = torch.empty(B, N, 8, device=maps.device, dtype=torch.int64)
+    if N == 0:
+        return stats
+    with torch.cuda.device(maps.device):
+        check(_timed("instance_stats", maps, lambda: load().wm2f_labelmap_instance_stats(
+            _p(maps), dt, _p(ids), _p(n_ids), _p(stats), B, H, W, N, _stream(maps))), "wm2f_labelmap_instance_stats")
+    return stats
+
+
 def resize_normalize_u8(images: torch.Tensor, desc, tables: torch.Tensor, lut: torch.Tensor, Hp: int, Wp: int):
     """Packed uint8 HWC images (flat, on the device) -> (pixel_values (B, 3, Hp, Wp) float32, pixel_mask (B, Hp, Wp)
     int64) through Pillow's fixed-point bilinear resample and a (3, 256) float32 lookup table (include/wm2f.h).

@@ -106,7 +106,13 @@ class Mask2FormerInstancePostProcessor:
 
     def post_process_instance_segmentation(self, outputs, threshold: float = 0.5, mask_threshold: float = 0.5,
                                            overlap_mask_area_threshold: float = 0.8, target_sizes=None,
-                                           return_coco_annotation: bool = False, return_binary_maps: bool = False):
+                                           return_coco_annotation: bool = False, return_binary_maps: bool = False,
+                                           return_instance_stats: bool = False):
+        """`return_instance_stats=True` (not an argument of the dependency) adds to every `segments_info` entry
+        "area" (int), "bbox" ([x, y, w, h] ints, COCO) and "centroid" ((cx, cy) floats, None when the area is 0) of the
+        instance's pixels in the returned id map -- after later instances have painted over earlier ones, whatever
+        form `segmentation` is returned in -- from one more launch per distinct target size and one more
+        device-to-host copy."""
         if return_coco_annotation and return_binary_maps:
             raise ValueError("return_coco_annotation and return_binary_maps can not be both set to True.")
         cls = outputs.class_queries_logits
@@ -143,6 +149,7 @@ class Mask2FormerInstancePostProcessor:
         seg_out: list = [None] * B
         keep_all = torch.zeros(B, Q, dtype=torch.bool, device=dev)
         kept_q_all = torch.zeros(B, Q, dtype=torch.int32, device=dev)
+        stats_all = torch.zeros(B, Q, 8, dtype=torch.int64, device=dev) if return_instance_stats else None
         for size in dict.fromkeys(sizes):  # one launch group per distinct target size
             rows = [i for i in range(B) if sizes[i] == size]
             ridx = torch.tensor(rows, device=dev)
@@ -159,16 +166,26 @@ class Mask2FormerInstancePostProcessor:
             seg = ops.instance_segmentation(lg, kept_q, n_kept, size)
             keep_all[ridx] = keep
             kept_q_all[ridx] = kept_q
+            if return_instance_stats:
+                stats_all[ridx] = ops.labelmap_instance_stats(seg, N=Q)
             for j, i in enumerate(rows):
                 seg_out[i] = seg[j]
 
         # ---- the one device-to-host copy
         keep_cpu, score_cpu = keep_all.cpu(), pred_scores.cpu()
+        if return_instance_stats:
+            from .instances import stats_to_boxes
+            area, bbox, centroid = (t.tolist() for t in stats_to_boxes(stats_all.cpu()))
         results = []
         for i in range(B):
             ks = torch.nonzero(keep_cpu[i]).flatten().tolist()
             segments = [{"id": r, "label_id": int(labels_cpu[i, j]), "was_fused": False, "score": round(float(score_cpu[i, j]), 6)}
                         for r, j in enumerate(ks)]
+            if return_instance_stats:
+                for r, seg_info in enumerate(segments):
+                    seg_info["area"] = area[i][r]
+                    seg_info["bbox"] = bbox[i][r]
+                    seg_info["centroid"] = tuple(centroid[i][r]) if area[i][r] > 0 else None
             segmentation = seg_out[i]
             if return_coco_annotation:
                 segmentation = convert_segmentation_to_rle(segmentation)
