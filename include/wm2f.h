@@ -36,6 +36,7 @@ extern "C" {
 #define WM2F_I32 2 /* integer maps of the mAP entry points */
 #define WM2F_U8 3
 #define WM2F_U16 4 /* semantic maps of the CCL entry points */
+#define WM2F_I64 5 /* class maps of wm2f_semantic_confusion */
 
 #define WM2F_OK 0
 #define WM2F_EINVAL (-1)      /* bad argument / unsupported shape */
@@ -649,6 +650,55 @@ int wm2f_coco_match(const int32_t* inter, const int32_t* det_area, const int32_t
  *                         pixel by pixel otherwise, with the same results. */
 int wm2f_labelmap_instance_stats(const void* map, int dtype, const int32_t* ids, const int32_t* n_ids, int64_t* stats,
                                  int B, int H, int W, int N, void* stream);
+
+/* ---- panoptic quality and semantic mIoU on device ---------------------------------------
+ * What scores the maps of post_process_panoptic_segmentation and post_process_semantic_segmentation: the segment
+ * matching of panopticapi's pq_compute (which torchmetrics' PanopticQuality follows) and the confusion matrix mIoU is
+ * made of.  The host keeps the per-class sums (weed_instance_segmentation_amd/panoptic_metrics.py).
+ * wm2f_panoptic_match:     segment matching of B images in one launch, one 256-thread workgroup per image.
+ *                         hist (B, P+1, G+1) int32 in the layout of wm2f_labelmap_pair_counts: row r > 0 is prediction
+ *                         segment r-1, row 0 no prediction; column c > 0 is GT segment c-1, column 0 no listed GT (void).
+ *                         Rows or columns that form one segment (a stuff class, a fused id) are added up by the caller
+ *                         first, in integers.  An image's bins sum to its pixel count, < 2^31.
+ *                         pred_label (B, P), gt_label (B, G), n_pred / n_gt (B) int32.  A row at or beyond n_pred[b], or
+ *                         labelled INT32_MIN, or without a pixel, does not exist; the same for columns.
+ *                         Areas are row and column sums over the whole histogram, taken inside the kernel.
+ *                         pred_void = hist[p][0], or 0 when void_as_background != 0.  For an existing pair of equal
+ *                         label with inter > 0: union = pred_area - pred_void + gt_area - inter, and the pair matches
+ *                         iff 2 * inter > union, decided in int64 (an IoU of exactly 1/2 does not match; no rounding
+ *                         takes part).  Segments being disjoint, a row and a column match at most once.
+ *                         Out, all overwritten: gt_match (B, G) int32 = the matched prediction row, -1 for an existing
+ *                         GT segment without a match (a false negative), -2 for a column that does not exist;
+ *                         gt_iou (B, G) fp64 = (double)inter / (double)union of the match, one division, else 0;
+ *                         pred_state (B, P) uint8 = 0 matched, 1 false positive, 2 dropped because mostly void
+ *                         (unmatched and 2 * pred_void > pred_area; exactly half in void is a false positive),
+ *                         3 does not exist.
+ *                         Rows are walked in the outer loop with the lanes across the GT columns.  LDS: 16 B per row,
+ *                         8 B per column.  P <= 1024 and G <= 4096 (48 KiB), else WM2F_EUNSUPPORTED.
+ * wm2f_semantic_confusion: conf (C, C) int64 += the confusion matrix of B class maps, rows = GT, columns = prediction.
+ *                         pred (B, n_pixels) is WM2F_I64 (post_process_semantic_segmentation's output), WM2F_I32 or
+ *                         WM2F_U8.  gt (B, n_pixels) is WM2F_U8 or WM2F_I32 and holds
+ *                           - classes when gt_ids == NULL (then gt_cls == n_ids == NULL and G == 0), or
+ *                           - raw ids otherwise: gt_ids (B, G) int32 ascending, gt_cls (B, G) int32 their classes,
+ *                             n_ids (B) int32 of them valid per image (the GT form of wm2f_labelmap_pair_counts); a raw
+ *                             id that is not listed has class background_label (pass a negative one to ignore it).
+ *                         A pixel whose GT class equals ignore_index or lies outside [0, C) is ignored (pass INT32_MIN
+ *                         for no ignore_index).  A pixel that is not ignored and whose prediction lies outside [0, C)
+ *                         is counted in n_out_of_range[0] (int64) and in no bin.
+ *                         conf and n_out_of_range are ACCUMULATED INTO, never cleared: a metric keeps its state on the
+ *                         device across calls.  All integer: bit-identical from run to run, and two calls equal one
+ *                         call on the concatenation.  n_pixels < 2^31.  C <= 1024 and G <= 4096, else
+ *                         WM2F_EUNSUPPORTED.  Bins live in LDS per workgroup (int32, 16 KiB at the bound: eight
+ *                         workgroups per CU) while C <= 64, non-zero ones flushed with 64-bit adds; above that every
+ *                         add goes to conf directly.  Four pixels per lane and load when n_pixels % 4 == 0 and both
+ *                         maps are aligned to four elements (16 bytes for int64), pixel by pixel otherwise, with the
+ *                         same results. */
+int wm2f_panoptic_match(const int32_t* hist, const int32_t* pred_label, const int32_t* gt_label, const int32_t* n_pred,
+                        const int32_t* n_gt, int32_t* gt_match, double* gt_iou, uint8_t* pred_state, int B, int P, int G,
+                        int void_as_background, void* stream);
+int wm2f_semantic_confusion(const void* pred, int pred_dtype, const void* gt, int gt_dtype, const int32_t* gt_ids,
+                            const int32_t* gt_cls, const int32_t* n_ids, int64_t* conf, int64_t* n_out_of_range, int B,
+                            int64_t n_pixels, int G, int C, int ignore_index, int background_label, void* stream);
 
 /* ---- image preprocessing on device ---------------------------------------------------
  * The tensor work of Mask2FormerImageProcessorPil._preprocess (image_processing_pil_mask2former.py:485-585), bit-exact.

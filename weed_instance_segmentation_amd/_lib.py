@@ -19,6 +19,7 @@ WM2F_BF16 = 1
 WM2F_I32 = 2
 WM2F_U8 = 3
 WM2F_U16 = 4
+WM2F_I64 = 5
 WM2F_CCL_VALUE, WM2F_CCL_BINARY, WM2F_CCL_RGB = 0, 1, 2
 WM2F_CCL_MAX_COLORS = 16
 WM2F_POLY_MAX_SIDE = 16384
@@ -116,6 +117,8 @@ SIGNATURES = {
     "wm2f_mask_pair_counts": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, c_int64, _P]),
     "wm2f_coco_match": (c_int, [_P] * 14 + [_I, _I, _I, _I, _I, _I, _P]),
     "wm2f_labelmap_instance_stats": (c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "wm2f_panoptic_match": (c_int, [_P] * 8 + [_I, _I, _I, _I, _P]),
+    "wm2f_semantic_confusion": (c_int, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, c_int64, _I, _I, _I, _I, _P]),
     "wm2f_resize_normalize_u8": (c_int, [_P, c_int64, POINTER(c_int64), _P, c_int64, _P, _P, c_int64, _P, _P, _I, _I, _I,
                                          _P]),
     "wm2f_resize_nearest_labels": (c_int, [_P, _I, c_int64, POINTER(c_int64), _P, c_int64, _P, _P, _I, _I, _I, _I, _P]),

@@ -448,3 +448,8 @@ def prepare_metrics_for_json(results: dict) -> dict | None:
         return None
     return {k: ((v.item() if v.numel() == 1 else v.tolist()) if isinstance(v, torch.Tensor) else v)
             for k, v in results.items()}
+
+
+# panoptic quality and semantic mIoU live in panoptic_metrics.py; this is where callers look for metrics
+from .panoptic_metrics import (MeanIoU, PanopticQuality, test_panoptic_with_metrics,  # noqa: E402,F401
+                               test_semantic_with_metrics)

@@ -1775,6 +1775,77 @@ def labelmap_instance_stats(maps: torch.Tensor, ids: torch.Tensor | None = None,
     return stats
 
 
+# --------------------------------------------------- panoptic quality and semantic mIoU
+def panoptic_match(hist, pred_label, gt_label, n_pred, n_gt, void_as_background: bool = False):
+    """PQ's segment matching of B images (wm2f_panoptic_match): hist (B, P+1, G+1), pred_label (B, P), gt_label (B, G),
+    n_pred / n_gt (B) int32.  Returns gt_match (B, G) int32 (matched prediction row, -1 false negative, -2 no such GT),
+    gt_iou (B, G) fp64 and pred_state (B, P) uint8 (0 matched, 1 false positive, 2 dropped as mostly void, 3 none)."""
+    i32 = torch.int32
+    hist, pred_label, gt_label = _req(hist, "hist", i32), _req(pred_label, "pred_label", i32), _req(gt_label, "gt_label", i32)
+    n_pred, n_gt = _req(n_pred, "n_pred", i32), _req(n_gt, "n_gt", i32)
+    if hist.dim() != 3 or pred_label.dim() != 2 or gt_label.dim() != 2:
+        raise ValueError("panoptic_match: hist must be (B, P+1, G+1), the labels (B, P) and (B, G)")
+    B, P, G = int(hist.shape[0]), int(pred_label.shape[1]), int(gt_label.shape[1])
+    if hist.shape != (B, P + 1, G + 1) or pred_label.shape[0] != B or gt_label.shape[0] != B or n_pred.shape != (B,) or n_gt.shape != (B,):
+        raise ValueError("panoptic_match: shapes disagree")
+    dev = hist.device
+    gt_match = torch.empty(B, G, device=dev, dtype=i32)
+    gt_iou = torch.empty(B, G, device=dev, dtype=torch.float64)
+    pred_state = torch.empty(B, P, device=dev, dtype=torch.uint8)
+    if B == 0:
+        return gt_match, gt_iou, pred_state
+    with torch.cuda.device(dev):
+        check(_timed("panoptic_match", hist, lambda: load().wm2f_panoptic_match(
+            _p(hist), _p(pred_label), _p(gt_label), _p(n_pred), _p(n_gt), _p(gt_match), _p(gt_iou), _p(pred_state), B, P, G,
+            int(bool(void_as_background)), _stream(hist))), "wm2f_panoptic_match")
+    return gt_match, gt_iou, pred_state
+
+
+def semantic_confusion_(conf: torch.Tensor, n_out_of_range: torch.Tensor, pred: torch.Tensor, gt: torch.Tensor,
+                        ignore_index: int | None = None, gt_ids: torch.Tensor | None = None,
+                        gt_cls: torch.Tensor | None = None, n_ids: torch.Tensor | None = None,
+                        background_label: int | None = None) -> None:
+    """conf (C, C) int64 += the confusion matrix (rows GT, columns prediction) of pred (B, ...) int64 / int32 / uint8
+    against gt (B, ...) uint8 / int32 (wm2f_semantic_confusion); n_out_of_range (1) int64 += the non-ignored pixels whose
+    prediction is outside [0, C).  gt holds classes, or raw ids when gt_ids (B, G) ascending, gt_cls (B, G) and n_ids (B)
+    int32 are given; an unlisted raw id then has class `background_label`, or is ignored without one.  In place, no
+    synchronisation."""
+    for name, t in (("conf", conf), ("n_out_of_range", n_out_of_range), ("pred", pred), ("gt", gt)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"semantic_confusion_: {name} must be a tensor")
+    if not conf.is_contiguous() or not n_out_of_range.is_contiguous():
+        raise ValueError("semantic_confusion_: conf and n_out_of_range must be contiguous (they are updated in place)")
+    conf, n_out = _req(conf, "conf", torch.int64), _req(n_out_of_range, "n_out_of_range", torch.int64)
+    pred, gt = _req(pred, "pred", pred.dtype), _req(gt, "gt", gt.dtype)
+    pdt = {torch.int64: _lib.WM2F_I64, torch.int32: _lib.WM2F_I32, torch.uint8: _lib.WM2F_U8}.get(pred.dtype)
+    gdt = {torch.uint8: _lib.WM2F_U8, torch.int32: _lib.WM2F_I32}.get(gt.dtype)
+    if pdt is None or gdt is None:
+        raise TypeError(f"semantic_confusion_: prediction maps int64 / int32 / uint8 and GT maps uint8 / int32, got "
+                        f"{pred.dtype} / {gt.dtype}")
+    if conf.dim() != 2 or conf.shape[0] != conf.shape[1] or n_out.numel() != 1:
+        raise ValueError("semantic_confusion_: conf must be (C, C) and n_out_of_range one element")
+    if pred.shape != gt.shape or pred.dim() < 2:
+        raise ValueError(f"semantic_confusion_: maps must be (B, ...) of one shape, got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    B, C = int(pred.shape[0]), int(conf.shape[0])
+    G = 0
+    if (gt_ids is None) != (gt_cls is None) or (gt_ids is None) != (n_ids is None):
+        raise ValueError("semantic_confusion_: gt_ids, gt_cls and n_ids go together")
+    if gt_ids is not None:
+        gt_ids, gt_cls, n_ids = _req(gt_ids, "gt_ids", torch.int32), _req(gt_cls, "gt_cls", torch.int32), _req(n_ids, "n_ids", torch.int32)
+        G = int(gt_ids.shape[1]) if gt_ids.dim() == 2 else -1
+        if gt_ids.shape != (B, G) or gt_cls.shape != (B, G) or n_ids.shape != (B,):
+            raise ValueError("semantic_confusion_: shapes disagree")
+    if B == 0 or pred[0].numel() == 0 or C == 0:
+        return
+    n = pred[0].numel()
+    ign = -2 ** 31 if ignore_index is None else int(ignore_index)
+    bg = -1 if background_label is None else int(background_label)
+    with torch.cuda.device(pred.device):
+        check(_timed("semantic_confusion", pred, lambda: load().wm2f_semantic_confusion(
+            _p(pred), pdt, _p(gt), gdt, _p(gt_ids), _p(gt_cls), _p(n_ids), _p(conf), _p(n_out), B, n, G, C, ign, bg,
+            _stream(pred))), "wm2f_semantic_confusion")
+
+
 def resize_normalize_u8(images: torch.Tensor, desc, tables: torch.Tensor, lut: torch.Tensor, Hp: int, Wp: int):
     """Packed uint8 HWC images (flat, on the device) -> (pixel_values (B, 3, Hp, Wp) float32, pixel_mask (B, Hp, Wp)
     int64) through Pillow's fixed-point bilinear resample and a (3, 256) float32 lookup table (include/wm2f.h).
