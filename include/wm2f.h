@@ -700,6 +700,41 @@ int wm2f_semantic_confusion(const void* pred, int pred_dtype, const void* gt, in
                             const int32_t* gt_cls, const int32_t* n_ids, int64_t* conf, int64_t* n_out_of_range, int B,
                             int64_t n_pixels, int G, int C, int ignore_index, int background_label, void* stream);
 
+/* ---- segmentation overlays and contours on device ----------------------------------------
+ * What models/model_utils.py::plot_segmentation and the dataset visualisers draw with one `segmentation == id` pass
+ * per segment on the host: every listed segment filled at its alpha and outlined at full colour, in one read of the
+ * picture and the map whatever the number of segments.
+ * wm2f_labelmap_overlay:   image and out (B, H, W, 3) uint8; out is overwritten and must not overlap image (neighbours
+ *                         are read), else WM2F_EINVAL.  map (B, H, W) is WM2F_F32, WM2F_I32 or WM2F_U8; a float value
+ *                         is an id by the rule of wm2f_labelmap_instance_stats (negative, fractional, not finite or
+ *                         >= 2^24: no id).  ids (B, N) int32, ascending, n_ids (B) int32 of them valid per image;
+ *                         rgba (B, N, 4) uint8 (4-byte aligned) and order (B, N) int32 belong to the listed entry.
+ *                         N == 0 is legal (the four pointers may then be NULL): every pixel takes the default.
+ *                         default_rgba = r | g << 8 | b << 16 | a << 24, for every pixel whose value is not listed.
+ *                         0 <= inner, outer <= 4, else WM2F_EINVAL.
+ *                         Write e(p) for the listed entry of pixel p's value, or none.  Distances are |dx| + |dy|;
+ *                         pixels outside the picture are no neighbours.
+ *                         Fill: (r, g, b, a) = rgba[e(p)], or the default when e(p) is none;
+ *                           out_c = (image_c * (255 - a) + col_c * a + 127) / 255 in integers
+ *                         (a == 0 copies the picture's byte, a == 255 gives the colour).
+ *                         Contour, opaque, over the fill: the candidates of p are
+ *                           - e(p), if some q within `inner` has e(q) != e(p),
+ *                           - e(q) for every q within `outer` with e(q) != e(p),
+ *                         none and entries of negative order left out; p takes the rgb of the candidate of greatest
+ *                         order (painter's order; of equal orders the later entry wins), and its fill when there is no
+ *                         candidate.  So entry s outlines itself `inner` pixels inwards and `outer` pixels outwards,
+ *                         never along the picture's border, and inner == outer == 0 draws no contour.
+ *                         All integer and nothing accumulated: bit-identical from run to run.
+ *                         H, W <= 16384, B <= 32, N <= 4096, else WM2F_EUNSUPPORTED.
+ *                         A workgroup owns a tile of 32 x 128 pixels; the entries of the tile and its halo live in LDS
+ *                         as int16 (11 KiB).  e(p) is a binary search of the image's id list, which with order and
+ *                         rgba lives in LDS while N <= 1024 (12 B per entry) and is read from global memory above
+ *                         that.  Four pixels per lane and load when W % 4 == 0 and image, out (4-byte) and map
+ *                         (16-byte, uint8: 4-byte) are aligned, pixel by pixel otherwise, with the same results. */
+int wm2f_labelmap_overlay(const uint8_t* image, const void* map, int dtype, const int32_t* ids, const int32_t* n_ids,
+                          const uint8_t* rgba, const int32_t* order, uint32_t default_rgba, int inner, int outer,
+                          uint8_t* out, int B, int H, int W, int N, void* stream);
+
 /* ---- image preprocessing on device ---------------------------------------------------
  * The tensor work of Mask2FormerImageProcessorPil._preprocess (image_processing_pil_mask2former.py:485-585), bit-exact.
  * wm2f_resize_normalize_u8: B packed uint8 HWC RGB images of different sizes -> pixel_values (B, 3, Hp, Wp) float32 and

@@ -15,3 +15,5 @@ from .metrics import MeanAveragePrecision  # noqa: F401
 from .instances import instance_statistics  # noqa: F401
 from .preprocess import Mask2FormerImageProcessor  # noqa: F401
 from .augment import AugmentParams, TrainAugmentation  # noqa: F401
+from .visualize import (build_overlay_tables, convert_gt_map_to_result, render_label_overlay,  # noqa: F401
+                        render_segmentation, render_segmentations, save_comparison)

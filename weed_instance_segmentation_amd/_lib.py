@@ -119,6 +119,7 @@ SIGNATURES = {
     "wm2f_labelmap_instance_stats": (c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     "wm2f_panoptic_match": (c_int, [_P] * 8 + [_I, _I, _I, _I, _P]),
     "wm2f_semantic_confusion": (c_int, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, c_int64, _I, _I, _I, _I, _P]),
+    "wm2f_labelmap_overlay": (c_int, [_P, _P, _I, _P, _P, _P, _P, ctypes.c_uint32, _I, _I, _P, _I, _I, _I, _I, _P]),
     "wm2f_resize_normalize_u8": (c_int, [_P, c_int64, POINTER(c_int64), _P, c_int64, _P, _P, c_int64, _P, _P, _I, _I, _I,
                                          _P]),
     "wm2f_resize_nearest_labels": (c_int, [_P, _I, c_int64, POINTER(c_int64), _P, c_int64, _P, _P, _I, _I, _I, _I, _P]),

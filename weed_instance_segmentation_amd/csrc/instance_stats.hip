@@ -42,22 +42,6 @@ struct IsAcc {
 };
 static_assert(sizeof(IsAcc) == 32, "IsAcc layout");
 
-// the integer a float's bits stand for: +-0 and exact integers in [1, 2^24); anything else is no id
-__device__ __forceinline__ bool f32_bits_to_int(uint32_t u, int& out) {
-  if ((u << 1) == 0u) {
-    out = 0;
-    return true;
-  }
-  if (u >> 31) return false;
-  const int e = (int)(u >> 23) - 127;
-  if (e < 0 || e > 23) return false;
-  const uint32_t m = (u & 0x7fffffu) | 0x800000u;
-  const int sh = 23 - e;
-  if (m & ((1u << sh) - 1u)) return false;
-  out = (int)(m >> sh);
-  return true;
-}
-
 // result row of a raw map value, -1 for none.  ids == nullptr: the value itself when in [0, N); else its position in
 // the image's ascending list (n of them, in LDS)
 template <int DT>
