@@ -411,6 +411,41 @@ def test_k1_backward_deterministic_form(ops, shapes, B, scale):
         torch.use_deterministic_algorithms(prev)
 
 
+def test_k1_backward_deterministic_warn_only_takes_the_other_kernel(ops):
+    """A shape without a fixed-point form (head_dim 16) under the deterministic switch in warn-only mode: the library answers
+    "unsupported", and the float-atomic backward runs behind the same call.  Against the oracle's autograd, at the
+    tolerances of test_k1_backward."""
+    shapes, B, H, D = [(2, 2), (4, 4)], 1, 2, 16
+    value, loc, w = _rand_k1(B, shapes, H, D, 5, spread=1.1)
+    go = torch.randn(B, value.shape[1], H * D, generator=torch.Generator().manual_seed(6))
+    v0, l0, w0 = value.clone().requires_grad_(), loc.clone().requires_grad_(), w.clone().requires_grad_()
+    O.msdeform_attn_core(v0, shapes, l0, w0).backward(go)
+    prev, prev_warn = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()
+    torch.use_deterministic_algorithms(True, warn_only=True)
+    try:
+        gv, gl, gw = ops.ms_deform_attn_bwd(dev(value), shapes, dev(loc), dev(w), dev(go))
+    finally:
+        torch.use_deterministic_algorithms(prev, warn_only=prev_warn)
+    torch.testing.assert_close(gv.cpu(), v0.grad, rtol=1e-4, atol=1e-5)
+    torch.testing.assert_close(gw.cpu(), w0.grad, rtol=1e-4, atol=1e-5)
+    torch.testing.assert_close(gl.cpu(), l0.grad, rtol=1e-3, atol=1e-4)
+
+
+def test_k1_rows_applies_follows_the_package_flag(ops):
+    """The rows kernels have no deterministic form: ops.K1_BWD_DETERMINISTIC = True, assigned on the package, turns
+    k1_rows_applies off at the smallest shape those kernels accept.  No launch."""
+    shapes, B, H = [(1, 1), (2, 2), (4, 4)], 1, 2
+    value = torch.zeros(B, 21, H, 32, device="cuda")
+    rows = torch.zeros(B, 21, H * 36, device="cuda")
+    assert ops.k1_rows_applies(value, rows, shapes, H) is True
+    prev = ops.K1_BWD_DETERMINISTIC
+    ops.K1_BWD_DETERMINISTIC = True
+    try:
+        assert ops.k1_rows_applies(value, rows, shapes, H) is False
+    finally:
+        ops.K1_BWD_DETERMINISTIC = prev
+
+
 # ----------------------------------------------------------------------------------------- K3
 def test_k3_golden(ops):
     g = load_golden("k3_mask_predictor.npz")

@@ -1,0 +1,48 @@
+"""Python face of the libwm2f kernels: argument checking, pointer plumbing, autograd glue.
+
+PyTorch is used for device memory, streams and autograd bookkeeping only.  Every function here launches hand-written HIP
+through the C ABI (include/wm2f.h) on the caller's current stream and RAISES if the tensors are not on a GPU or the library
+is missing -- there is no eager fallback.  One module per kernel family; each launch goes through `_core._launch`.  This
+package re-exports them all and owns the three switches below: callers assign and read them as `ops.<FLAG>`.
+"""
+from __future__ import annotations
+
+# K1 backward flavour: None = follow torch.are_deterministic_algorithms_enabled(); True / False force it.
+K1_BWD_DETERMINISTIC: bool | None = None
+
+# The inference routes of the 1x1 convolutions (ResNet bottlenecks, pixel-decoder projections) take the split kernel while
+# this is True; False sends them through conv1x1(..., split=False), the library convolution plus bias_act_ (the accuracy
+# reference of the tests).
+CONV1X1_SPLIT = True
+
+# The inference routes of the 3x3 convolutions (ResNet conv2, the pixel decoder's FPN layer_1) take the split kernel while
+# this is True; False sends them through conv3x3(..., split=False), the library convolution plus bias_act_ (the accuracy
+# reference of the tests).
+CONV3X3_SPLIT = True
+
+# The flags come first: k1 reads K1_BWD_DETERMINISTIC off this package.
+from .._lib import check
+from ._core import KernelTimer, _p, _stream, set_kernel_timer
+from .ccl import label_components, resize_nearest_tables
+from .fused import (add_broadcast, bias_act_, bias_relu_maxpool, group_norm_act_, group_norm_tokens_, resize_bilinear,
+                    resize_pyramid, tokens_to_nchw)
+from .gemm import (conv1x1, conv1x1_applies, conv3x3, conv3x3_applies, linear_tokens, split_weight, split_weight_3x3,
+                   split_weight_cached, token_linear, token_linear_applies, token_wgrad, token_wgrad_applies)
+from .k1 import (k1_bwd_deterministic, k1_lane_order, k1_lane_rows, k1_lanes_applies, k1_rows_applies, ms_deform_attn,
+                 ms_deform_attn_bwd, ms_deform_attn_fused, ms_deform_attn_fused_lanes, ms_deform_attn_fused_packed,
+                 ms_deform_attn_rows, ms_deform_attn_variant)
+from .k2 import masked_xattn, masked_xattn_bf16_applies
+from .k3 import (attn_mask_build, mask_einsum, mask_einsum_attn_mask, mask_einsum_bf16, mask_einsum_bf16_bwd,
+                 mask_einsum_bf16_bwd_applies, mask_einsum_bwd, mask_einsum_bwd_applies, nchw_to_pixel_major_bf16)
+from .labelmaps import (coco_match, labelmap_instance_stats, labelmap_pair_counts, labelmap_to_masks, mask_pair_counts,
+                        panoptic_match, semantic_confusion_)
+from .layernorm import add_layernorm, add_layernorm_train, add_layernorm_train_applies
+from .loss import mask_loss_rows, point_sample, point_sample_levels, select_top_points
+from .matcher import lsa_batched, matcher_cost
+from .overlay import labelmap_overlay
+from .polygons import fill_polygons
+from .postprocess import (_GRID, instance_any, instance_maps, instance_scores, instance_segmentation, panoptic_probs,
+                          panoptic_relabel_, panoptic_segments, semantic_resize_argmax, semantic_scores)
+from .preprocess import augment_nearest_labels, augment_resize_normalize_u8, resize_nearest_labels, resize_normalize_u8
+from .swin import (SWIN_HEAD_DIMS, SWIN_WINDOW_SIZES, swin_window_attention, swin_window_attention_applies,
+                   swin_window_attention_train)

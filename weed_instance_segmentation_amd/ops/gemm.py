@@ -1,0 +1,279 @@
+"""The split-bf16 GEMMs and convolutions, and the token Linears' weight gradient."""
+from __future__ import annotations
+
+import weakref
+
+import torch
+
+from .._lib import load
+from ._core import _launch, _p, _req
+from .fused import bias_act_
+
+
+def token_linear_applies(x: torch.Tensor, weight: torch.Tensor) -> bool:
+    """Shapes token_linear is built for: fp32 on a GPU, N in {256, 288, 512, 768, 1024}, K a multiple of 32, x / out below
+    2 GiB (the fp32-MFMA kernel, split=False, additionally needs N in {256, 288} and K a multiple of 64)."""
+    N, K = weight.shape
+    M = x.numel() // max(K, 1)
+    return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and N in (256, 288, 512, 768, 1024)
+            and K % 32 == 0 and x.shape[-1] == K and M * K * 4 < (1 << 31) and M * N * 4 < (1 << 31)
+            and N * K * 6 < (1 << 31))
+
+
+def split_weight(weight: torch.Tensor) -> torch.Tensor:
+    """The three bf16 pieces of an fp32 weight (N, K) in wm2f_token_linear_split_fwd's fragment order (N * K * 6 bytes,
+    returned as a uint8 tensor).  Callers that reuse a weight cache this per weight version (split_weight_cached)."""
+    weight = _req(weight, "weight")
+    N, K = weight.shape
+    ws = torch.empty(N * K * 6, device=weight.device, dtype=torch.uint8)
+    _launch("wm2f_token_linear_split_weight", weight, _p(weight), _p(ws), N, K)
+    return ws
+
+
+def split_weight_cached(owner, name: str, weight: torch.Tensor, base: torch.Tensor | None = None,
+                        tap_major: bool = False) -> torch.Tensor:
+    """split_weight(weight), kept in owner.__dict__ under `name` and redone when the weight changes: another tensor (held by
+    weak reference: `base` when weight is a fresh view of it each call), another version, storage or device.
+    tap_major=True: weight is a 3x3 kernel (N, Cin, 3, 3), split as conv3x3 reads it (split_weight_3x3)."""
+    ident = weight if base is None else base
+    c = owner.__dict__.setdefault("_wm2f_split", {})
+    key = (ident._version, weight.data_ptr(), weight.device, tuple(weight.shape))
+    hit = c.get(name)
+    if hit is None or hit[0]() is not ident or hit[1] != key:
+        hit = (weakref.ref(ident), key, split_weight_3x3(weight) if tap_major else split_weight(weight))
+        c[name] = hit
+    return hit[2]
+
+
+def split_weight_3x3(weight: torch.Tensor) -> torch.Tensor:
+    """The split of a 3x3 kernel (N, Cin, 3, 3) for wm2f_conv3x3_split_fwd: split_weight of its tap-major reorder
+    (N, 3, 3, Cin) seen as (N, 9 Cin), so that column (3 dy + dx) Cin + c is tap (dy, dx) of channel c."""
+    N = int(weight.shape[0])
+    return split_weight(weight.permute(0, 2, 3, 1).reshape(N, -1).contiguous())
+
+
+def token_linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, relu: bool = False, residual: torch.Tensor | None = None,
+                 ln: tuple | None = None, pos: torch.Tensor | None = None, out_group: int = 0, split: bool = True,
+                 w_split: torch.Tensor | None = None):
+    """Linear over tokens with its epilogue fused (inference, no autograd): x (..., K) @ weight (N, K)^T + bias, then
+    optional ReLU, optional LayerNorm(value + residual) with ln = (gamma, beta, eps), and with `pos` (rows_per_image, N)
+    additionally out + pos broadcast over the batch.  Returns out, or (out, out + pos).
+    out_group = G > 0: the result comes back feature-group major, (N // G, *x.shape[:-1], G) -- with G = 36 K1's operand rows
+    head-major (ms_deform_attn_fused_lanes(..., head_major=True)).
+    split=True (default): the split-bf16 kernel (wm2f_token_linear_split_fwd, fp32 accuracy on the bf16 matrix cores), with
+    `w_split` = split_weight(weight) if the caller keeps one; split=False: the fp32-MFMA kernel (wm2f_token_linear_fwd)."""
+    x, weight, bias = _req(x, "x"), _req(weight, "weight"), _req(bias, "bias")
+    N, K = weight.shape
+    if x.shape[-1] != K or bias.shape != (N,):
+        raise ValueError(f"token_linear: x {tuple(x.shape)} weight {tuple(weight.shape)} bias {tuple(bias.shape)}")
+    M = x.numel() // K
+    if out_group and (out_group % 4 or N % out_group or ln is not None):
+        raise ValueError("token_linear: out_group must divide N, be a multiple of 4 and exclude the LayerNorm epilogue")
+    out = (torch.empty(N // out_group, *x.shape[:-1], out_group, device=x.device, dtype=torch.float32) if out_group
+           else torch.empty(*x.shape[:-1], N, device=x.device, dtype=torch.float32))
+    gamma = beta = None
+    eps = 0.0
+    if ln is not None:
+        gamma, beta, eps = _req(ln[0], "gamma"), _req(ln[1], "beta"), float(ln[2])
+    if residual is not None:
+        residual = _req(residual, "residual")
+        if residual.numel() != M * N:
+            raise ValueError("token_linear: residual shape")
+    out_pos, pos_rows = None, 0
+    if pos is not None:
+        pos = _req(pos, "pos")
+        pos_rows = pos.numel() // N
+        if M % pos_rows:
+            raise ValueError("token_linear: pos rows do not divide the token count")
+        out_pos = torch.empty_like(out)
+    tag = f"token_linear_K{K}_N{N}" + ("_ln" if ln is not None else "")
+    if split:
+        if w_split is None:
+            w_split = split_weight(weight)
+        elif w_split.dtype != torch.uint8 or w_split.numel() != N * K * 6 or w_split.device != x.device:
+            raise ValueError("token_linear: w_split is not split_weight(weight)")
+        _launch("wm2f_token_linear_split_fwd", x, _p(x), _p(w_split), _p(bias), _p(residual), _p(gamma), _p(beta), _p(pos),
+                _p(out), _p(out_pos), M, K, N, 1 if relu else 0, pos_rows, eps, int(out_group), tag=tag + "_split")
+    else:
+        _launch("wm2f_token_linear_fwd", x, _p(x), _p(weight), _p(bias), _p(residual), _p(gamma), _p(beta), _p(pos), _p(out),
+                _p(out_pos), M, K, N, 1 if relu else 0, pos_rows, eps, int(out_group), tag=tag)
+    return (out, out_pos) if pos is not None else out
+
+
+def conv1x1_applies(x: torch.Tensor, weight: torch.Tensor, stride: int = 1) -> bool:
+    """Shapes wm2f_conv1x1_split_fwd is built for: fp32 NCHW on a GPU, weight (N, K, 1, 1) or (N, K) with K % 32 == 0 and
+    N % 64 == 0, stride 1 or 2, one image of x / out below 2 GiB, the split weight below 2 GiB."""
+    if x.dim() != 4 or weight.dim() not in (2, 4) or (weight.dim() == 4 and weight.shape[2:] != (1, 1)):
+        return False
+    N, K = int(weight.shape[0]), int(weight.shape[1])
+    _, C, H, W = x.shape
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and C == K and K % 32 == 0
+            and N % 64 == 0 and stride in (1, 2) and K * H * W * 4 < (1 << 31) and N * Ho * Wo * 4 < (1 << 31)
+            and N * K * 6 < (1 << 31))
+
+
+def conv1x1(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None, residual: torch.Tensor | None = None,
+            relu: bool = False, stride: int = 1, split: bool = True, w_split: torch.Tensor | None = None,
+            config: int = -1) -> torch.Tensor:
+    """1x1 convolution without padding, epilogue fused (inference, no autograd): act(conv(x, weight, stride) + bias
+    (+ residual)), x (B, K, H, W) fp32.  The residual epilogue needs bias and relu.
+    split=True: wm2f_conv1x1_split_fwd (fp32 accuracy on the bf16 matrix cores), with `w_split` = split_weight of the
+    weight seen as (N, K) if the caller keeps one; shapes outside conv1x1_applies take the split=False path.  config >= 0
+    forces an entry of the kernel's tile table (tests, tuning; the same bits), -1 lets the kernel choose.
+    split=False: F.conv2d, then bias_act_ (or the same in torch ops when Ho * Wo is not a multiple of 4)."""
+    if residual is not None and (bias is None or not relu):
+        raise ValueError("conv1x1: the residual epilogue is bias + residual + ReLU")
+    if relu and bias is None:
+        raise ValueError("conv1x1: the ReLU epilogues carry a bias")
+    N, K = int(weight.shape[0]), int(weight.shape[1])
+    if not split or not conv1x1_applies(x, weight, stride):
+        w4 = weight if weight.dim() == 4 else weight.view(N, K, 1, 1)
+        y = torch.nn.functional.conv2d(x, w4, None, stride)
+        if bias is None:
+            return y
+        if (y.shape[-1] * y.shape[-2]) % 4 == 0:
+            return bias_act_(y, bias, residual, relu)
+        y = y + bias[None, :, None, None]
+        if residual is not None:
+            y = y + residual
+        return torch.relu(y) if relu else y
+    x = _req(x, "x")
+    w2 = _req(weight.reshape(N, K), "weight")
+    B, _, H, W = x.shape
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if bias is not None:
+        bias = _req(bias, "bias")
+        if bias.shape != (N,):
+            raise ValueError(f"conv1x1: bias {tuple(bias.shape)} for {N} channels")
+    if residual is not None:
+        residual = _req(residual, "residual")
+        if residual.shape != (B, N, Ho, Wo):
+            raise ValueError(f"conv1x1: residual {tuple(residual.shape)}, output ({B}, {N}, {Ho}, {Wo})")
+    if w_split is None:
+        w_split = split_weight(w2)
+    elif w_split.dtype != torch.uint8 or w_split.numel() != N * K * 6 or w_split.device != x.device:
+        raise ValueError("conv1x1: w_split is not split_weight(weight)")
+    out = torch.empty(B, N, Ho, Wo, device=x.device, dtype=torch.float32)
+    _launch("wm2f_conv1x1_split_fwd", x, _p(x), _p(w_split), _p(bias), _p(residual), _p(out), B, K, N, H, W, int(stride),
+            1 if relu else 0, int(config), tag=f"conv1x1_K{K}_N{N}_P{Ho * Wo}")
+    return out
+
+
+def conv3x3_applies(x: torch.Tensor, weight: torch.Tensor, stride: int = 1) -> bool:
+    """Shapes wm2f_conv3x3_split_fwd is built for: fp32 NCHW on a GPU, weight (N, Cin, 3, 3) with Cin % 32 == 0 and
+    N % 64 == 0, stride 1 or 2 (padding 1, dilation 1, one group), one image of x / out below 2 GiB, the split weight
+    below 2 GiB."""
+    if x.dim() != 4 or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        return False
+    N, C = int(weight.shape[0]), int(weight.shape[1])
+    _, K, H, W = x.shape
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and C == K and K % 32 == 0
+            and N % 64 == 0 and stride in (1, 2) and K * H * W * 4 < (1 << 31) and N * Ho * Wo * 4 < (1 << 31)
+            and N * 9 * K * 6 < (1 << 31))
+
+
+def conv3x3(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None, relu: bool = False, stride: int = 1,
+            split: bool = True, w_split: torch.Tensor | None = None, config: int = -1) -> torch.Tensor:
+    """3x3 convolution with padding 1, epilogue fused (inference, no autograd): act(conv(x, weight, stride) + bias),
+    x (B, Cin, H, W) fp32, weight (N, Cin, 3, 3).  The ReLU epilogue needs a bias.
+    split=True: wm2f_conv3x3_split_fwd (fp32 accuracy on the bf16 matrix cores), with `w_split` = split_weight_3x3(weight)
+    if the caller keeps one; shapes outside conv3x3_applies take the split=False path.  config >= 0 forces an entry of the
+    kernel's tile table (tests, tuning; the same bits), -1 lets the kernel choose.
+    split=False: F.conv2d, then bias_act_ (or the same in torch ops when Ho * Wo is not a multiple of 4)."""
+    if relu and bias is None:
+        raise ValueError("conv3x3: the ReLU epilogue carries a bias")
+    if not split or not conv3x3_applies(x, weight, stride):
+        y = torch.nn.functional.conv2d(x, weight, None, stride, 1)
+        if bias is None:
+            return y
+        if (y.shape[-1] * y.shape[-2]) % 4 == 0:
+            return bias_act_(y, bias, None, relu)
+        y = y + bias[None, :, None, None]
+        return torch.relu(y) if relu else y
+    x = _req(x, "x")
+    N, Cin = int(weight.shape[0]), int(weight.shape[1])
+    B, _, H, W = x.shape
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if bias is not None:
+        bias = _req(bias, "bias")
+        if bias.shape != (N,):
+            raise ValueError(f"conv3x3: bias {tuple(bias.shape)} for {N} channels")
+    if w_split is None:
+        w_split = split_weight_3x3(_req(weight, "weight"))
+    elif w_split.dtype != torch.uint8 or w_split.numel() != N * 9 * Cin * 6 or w_split.device != x.device:
+        raise ValueError("conv3x3: w_split is not split_weight_3x3(weight)")
+    out = torch.empty(B, N, Ho, Wo, device=x.device, dtype=torch.float32)
+    _launch("wm2f_conv3x3_split_fwd", x, _p(x), _p(w_split), _p(bias), _p(out), B, Cin, N, H, W, int(stride), 1 if relu else 0,
+            int(config), tag=f"conv3x3_C{Cin}_N{N}_P{Ho * Wo}")
+    return out
+
+
+def token_wgrad_applies(dy: torch.Tensor, x: torch.Tensor) -> bool:
+    """Shapes wm2f_token_wgrad_bf16 / _f32 are built for: both operands bf16 or both fp32 on a GPU, feature counts multiples
+    of 8, operands below 2 GiB."""
+    N, K = dy.shape[-1], x.shape[-1]
+    M = x.numel() // max(K, 1)
+    es = x.element_size()
+    return (dy.is_cuda and x.is_cuda and dy.dtype == x.dtype and x.dtype in (torch.bfloat16, torch.float32) and N % 8 == 0
+            and K % 8 == 0 and dy.numel() == M * N and M * N * es < 0x7fffffff and M * K * es < 0x7fffffff)
+
+
+def token_wgrad(dy: torch.Tensor, x: torch.Tensor, want_bias: bool = True):
+    """Weight (and bias) gradient of a Linear over tokens: dy (..., N), x (..., K), both bf16 or both fp32 -> dw (N, K) fp32 =
+    dy^T x and db (N) fp32 = column sums of dy (None without `want_bias`).  fp32 accumulation, deterministic (include/wm2f.h)."""
+    if x.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"token_wgrad: {x.dtype}")
+    dy, x = _req(dy, "dy", x.dtype), _req(x, "x", x.dtype)
+    N, K = dy.shape[-1], x.shape[-1]
+    M = x.numel() // K
+    if dy.numel() != M * N:
+        raise ValueError(f"token_wgrad: dy {tuple(dy.shape)} x {tuple(x.shape)}")
+    dw = torch.empty(N, K, device=x.device, dtype=torch.float32)
+    db = torch.empty(N, device=x.device, dtype=torch.float32) if want_bias else None
+    bf = x.dtype == torch.bfloat16
+    ws = torch.empty(max(16, int(load().wm2f_token_wgrad_workspace(M, N, K))), device=x.device, dtype=torch.uint8)
+    _launch("wm2f_token_wgrad_bf16" if bf else "wm2f_token_wgrad_f32", x, _p(dy), _p(x), _p(dw), _p(db), _p(ws), M, N, K,
+            tag=f"token_wgrad_{'bf16' if bf else 'f32'}_N{N}_K{K}", what="wm2f_token_wgrad")
+    return dw, db
+
+
+class _TokenLinear(torch.autograd.Function):
+    """nn.Linear over tokens with the weight gradient on wm2f_token_wgrad_*: forward and input gradient are the library's GEMMs
+    (in bf16 under bf16 autocast, as autocast runs F.linear; in fp32 otherwise), dW / db come back in fp32 -- the parameters'
+    dtype -- from ONE pass over dy and x."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, bf16):
+        cdt = torch.bfloat16 if bf16 else torch.float32
+        xc, wc = x.to(cdt), weight.to(cdt)
+        ctx.save_for_backward(xc, wc)
+        ctx.x_dtype, ctx.has_bias, ctx.cdt = x.dtype, bias is not None, cdt
+        return torch.nn.functional.linear(xc, wc, None if bias is None else bias.to(cdt))
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        xc, wc = ctx.saved_tensors
+        g = grad_out.to(ctx.cdt).contiguous()
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.matmul(g, wc).to(ctx.x_dtype)
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            gw, gb = token_wgrad(g, xc.contiguous(), want_bias=ctx.has_bias)
+        return gx, gw, gb, None
+
+
+def linear_tokens(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None) -> torch.Tensor:
+    """F.linear for the token matrices of the pixel decoder's encoder layers.  In training on a GPU (fp32, or under bf16
+    autocast) the weight-gradient product -- a 256 x 256 output with a contraction over every token of the batch, which a
+    library GEMM runs on 16 of 256 CUs -- goes to wm2f_token_wgrad_*.  Everything else is plain F.linear."""
+    amp = torch.is_autocast_enabled("cuda")
+    bf16 = amp and torch.get_autocast_dtype("cuda") == torch.bfloat16
+    if (torch.is_grad_enabled() and x.is_cuda and weight.requires_grad and weight.dtype == torch.float32
+            and (bf16 or (not amp and x.dtype == torch.float32))
+            and weight.shape[0] % 8 == 0 and weight.shape[1] % 8 == 0
+            and x.numel() // weight.shape[1] * max(weight.shape) * (2 if bf16 else 4) < 0x7fffffff):
+        with torch.autocast("cuda", enabled=False):
+            return _TokenLinear.apply(x, weight, bias, bf16)
+    return torch.nn.functional.linear(x, weight, bias)

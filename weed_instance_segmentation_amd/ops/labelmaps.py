@@ -1,0 +1,190 @@
+"""Label-map metrics: label expansion, pair counts and COCO matching, per-instance statistics
+(section 21), panoptic matching and the semantic confusion matrix (section 22)."""
+from __future__ import annotations
+
+import torch
+
+from .._lib import load
+from ._core import _dtype_code, _launch, _p, _req
+
+
+def labelmap_to_masks(label_map: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+    """(H, W) int32 id map, (T,) int32 ids -> (T, H, W) uint8 masks `label_map == ids[t]` on the device."""
+    label_map, ids = _req(label_map, "label_map", torch.int32), _req(ids, "ids", torch.int32)
+    H, W = label_map.shape
+    T = int(ids.shape[0])
+    out = torch.empty(T, H, W, device=label_map.device, dtype=torch.uint8)
+    if T == 0:
+        return out
+    if (H * W) % 4:
+        raise ValueError("labelmap_to_masks: H * W must be divisible by 4")
+    _launch("wm2f_labelmap_to_masks", label_map, _p(label_map), _p(ids), _p(out), H * W, T)
+    return out
+
+
+def labelmap_pair_counts(pred_maps: torch.Tensor, gt_maps: torch.Tensor, gt_ids: torch.Tensor, n_ids: torch.Tensor,
+                         P: int) -> torch.Tensor:
+    """(B, H, W) prediction id maps (fp32 with -1 background, or int32), (B, H, W) GT raw-id maps (uint8 or int32),
+    (B, G) ascending accepted GT ids with n_ids (B) valid -> (B, P+1, G+1) int32 joint histogram (row 0: no prediction,
+    column 0: no accepted GT id)."""
+    if not isinstance(pred_maps, torch.Tensor) or not isinstance(gt_maps, torch.Tensor):
+        raise TypeError("labelmap_pair_counts: expected tensors")
+    pred_maps = _req(pred_maps, "pred_maps", pred_maps.dtype)
+    gt_maps = _req(gt_maps, "gt_maps", gt_maps.dtype)
+    gt_ids, n_ids = _req(gt_ids, "gt_ids", torch.int32), _req(n_ids, "n_ids", torch.int32)
+    error = f"labelmap_pair_counts: prediction maps fp32 / int32 and GT maps uint8 / int32, got {pred_maps.dtype} / {gt_maps.dtype}"
+    pdt = _dtype_code(pred_maps, (torch.float32, torch.int32), error)
+    gdt = _dtype_code(gt_maps, (torch.uint8, torch.int32), error)
+    B = pred_maps.shape[0]
+    if gt_maps.shape != pred_maps.shape or gt_ids.dim() != 2 or gt_ids.shape[0] != B or n_ids.shape != (B,):
+        raise ValueError("labelmap_pair_counts: shapes disagree")
+    n = pred_maps[0].numel()
+    G = int(gt_ids.shape[1])
+    hist = torch.empty(B, P + 1, G + 1, device=pred_maps.device, dtype=torch.int32)
+    _launch("wm2f_labelmap_pair_counts", pred_maps, _p(pred_maps), pdt, _p(gt_maps), gdt, _p(gt_ids), _p(n_ids), _p(hist), B, n,
+            P, G, tag="labelmap_pair_counts")
+    return hist
+
+
+def mask_pair_counts(det_masks: torch.Tensor, gt_masks: torch.Tensor):
+    """(D, H, W) and (G, H, W) bool / uint8 mask stacks (may overlap) -> inter (D, G), det_area (D), gt_area (G) int32."""
+    det_masks = _req(det_masks, "det_masks", det_masks.dtype if det_masks.dtype in (torch.bool, torch.uint8) else torch.uint8)
+    gt_masks = _req(gt_masks, "gt_masks", gt_masks.dtype if gt_masks.dtype in (torch.bool, torch.uint8) else torch.uint8)
+    if det_masks.shape[1:] != gt_masks.shape[1:]:
+        raise ValueError(f"mask_pair_counts: mask sizes differ: {tuple(det_masks.shape)} vs {tuple(gt_masks.shape)}")
+    D, G = int(det_masks.shape[0]), int(gt_masks.shape[0])
+    n = det_masks[0].numel() if D else gt_masks[0].numel()
+    dev = det_masks.device
+    inter = torch.zeros(D, G, device=dev, dtype=torch.int32)
+    det_area = torch.zeros(D, device=dev, dtype=torch.int32)
+    gt_area = torch.zeros(G, device=dev, dtype=torch.int32)
+    if D + G == 0 or n == 0:
+        return inter, det_area, gt_area
+    ws = torch.empty(int(load().wm2f_mask_pair_counts_workspace(D, G, n)), device=dev, dtype=torch.uint8)
+    a, g = det_masks.view(torch.uint8), gt_masks.view(torch.uint8)
+    _launch("wm2f_mask_pair_counts", a, _p(a) if D else None, _p(g) if G else None, _p(inter), _p(det_area), _p(gt_area), _p(ws),
+            D, G, n, tag="mask_pair_counts")
+    return inter, det_area, gt_area
+
+
+def coco_match(inter, det_area, gt_area, det_label, gt_label, det_order, n_det, n_gt, iou_thresholds, area_ranges,
+               max_det: int):
+    """Greedy COCO matching of B images (wm2f_coco_match): inter (B, D, G), det_* (B, D), gt_* (B, G), n_det / n_gt (B)
+    int32; iou_thresholds (T), area_ranges (A, 2) fp64.  Returns det_rank (B, D) int32, det_matched / det_ignored
+    (B, A, T, D) uint8, gt_ignored (B, A, G) uint8."""
+    i32 = torch.int32
+    inter, det_area, gt_area = _req(inter, "inter", i32), _req(det_area, "det_area", i32), _req(gt_area, "gt_area", i32)
+    det_label, gt_label = _req(det_label, "det_label", i32), _req(gt_label, "gt_label", i32)
+    det_order, n_det, n_gt = _req(det_order, "det_order", i32), _req(n_det, "n_det", i32), _req(n_gt, "n_gt", i32)
+    thr, rng = _req(iou_thresholds, "iou_thresholds", torch.float64), _req(area_ranges, "area_ranges", torch.float64)
+    B, D, G = (int(v) for v in inter.shape)
+    T, A = int(thr.shape[0]), int(rng.shape[0])
+    if (det_area.shape != (B, D) or det_label.shape != (B, D) or det_order.shape != (B, D) or gt_area.shape != (B, G)
+            or gt_label.shape != (B, G) or n_det.shape != (B,) or n_gt.shape != (B,) or rng.shape != (A, 2)):
+        raise ValueError("coco_match: shapes disagree")
+    dev = inter.device
+    det_rank = torch.empty(B, D, device=dev, dtype=i32)
+    det_matched = torch.empty(B, A, T, D, device=dev, dtype=torch.uint8)
+    det_ignored = torch.empty(B, A, T, D, device=dev, dtype=torch.uint8)
+    gt_ignored = torch.empty(B, A, G, device=dev, dtype=torch.uint8)
+    _launch("wm2f_coco_match", inter, _p(inter), _p(det_area), _p(gt_area), _p(det_label), _p(gt_label), _p(det_order), _p(n_det),
+            _p(n_gt), _p(thr), _p(rng), _p(det_rank), _p(det_matched), _p(det_ignored), _p(gt_ignored), B, D, G, T, A,
+            int(max_det), tag="coco_match")
+    return det_rank, det_matched, det_ignored, gt_ignored
+
+
+def labelmap_instance_stats(maps: torch.Tensor, ids: torch.Tensor | None = None, n_ids: torch.Tensor | None = None,
+                            N: int | None = None) -> torch.Tensor:
+    """(B, H, W) id maps (fp32 with -1 background, int32 or uint8) -> (B, N, 8) int64
+    [area, xmin, ymin, xmax, ymax, sum_x, sum_y, 0] per id (wm2f_labelmap_instance_stats), xmax / ymax inclusive, an id
+    without a pixel [0, W, H, -1, -1, 0, 0, 0].  Without `ids`, row r is id r of [0, N).  With `ids` (B, N) int32
+    ascending and `n_ids` (B) of them valid, row r is the raw id ids[b][r]."""
+    if not isinstance(maps, torch.Tensor):
+        raise TypeError("labelmap_instance_stats: expected tensors")
+    maps = _req(maps, "maps", maps.dtype)
+    dt = _dtype_code(maps, (torch.float32, torch.int32, torch.uint8),
+                     f"labelmap_instance_stats: maps fp32 / int32 / uint8, got {maps.dtype}")
+    if maps.dim() != 3:
+        raise ValueError(f"labelmap_instance_stats: maps must be (B, H, W), got {tuple(maps.shape)}")
+    B, H, W = (int(v) for v in maps.shape)
+    if (ids is None) != (n_ids is None):
+        raise ValueError("labelmap_instance_stats: ids and n_ids go together")
+    if ids is not None:
+        ids, n_ids = _req(ids, "ids", torch.int32), _req(n_ids, "n_ids", torch.int32)
+        if ids.dim() != 2 or ids.shape[0] != B or n_ids.shape != (B,) or (N is not None and int(N) != ids.shape[1]):
+            raise ValueError("labelmap_instance_stats: shapes disagree")
+        N = int(ids.shape[1])
+    elif N is None:
+        raise ValueError("labelmap_instance_stats: N is needed without an id list")
+    N = int(N)
+    if N < 0 or B == 0 or H == 0 or W == 0:
+        raise ValueError("labelmap_instance_stats: bad size")
+    stats = torch.empty(B, N, 8, device=maps.device, dtype=torch.int64)
+    if N == 0:
+        return stats
+    _launch("wm2f_labelmap_instance_stats", maps, _p(maps), dt, _p(ids), _p(n_ids), _p(stats), B, H, W, N, tag="instance_stats")
+    return stats
+
+
+def panoptic_match(hist, pred_label, gt_label, n_pred, n_gt, void_as_background: bool = False):
+    """PQ's segment matching of B images (wm2f_panoptic_match): hist (B, P+1, G+1), pred_label (B, P), gt_label (B, G),
+    n_pred / n_gt (B) int32.  Returns gt_match (B, G) int32 (matched prediction row, -1 false negative, -2 no such GT),
+    gt_iou (B, G) fp64 and pred_state (B, P) uint8 (0 matched, 1 false positive, 2 dropped as mostly void, 3 none)."""
+    i32 = torch.int32
+    hist, pred_label, gt_label = _req(hist, "hist", i32), _req(pred_label, "pred_label", i32), _req(gt_label, "gt_label", i32)
+    n_pred, n_gt = _req(n_pred, "n_pred", i32), _req(n_gt, "n_gt", i32)
+    if hist.dim() != 3 or pred_label.dim() != 2 or gt_label.dim() != 2:
+        raise ValueError("panoptic_match: hist must be (B, P+1, G+1), the labels (B, P) and (B, G)")
+    B, P, G = int(hist.shape[0]), int(pred_label.shape[1]), int(gt_label.shape[1])
+    if hist.shape != (B, P + 1, G + 1) or pred_label.shape[0] != B or gt_label.shape[0] != B or n_pred.shape != (B,) or n_gt.shape != (B,):
+        raise ValueError("panoptic_match: shapes disagree")
+    dev = hist.device
+    gt_match = torch.empty(B, G, device=dev, dtype=i32)
+    gt_iou = torch.empty(B, G, device=dev, dtype=torch.float64)
+    pred_state = torch.empty(B, P, device=dev, dtype=torch.uint8)
+    if B == 0:
+        return gt_match, gt_iou, pred_state
+    _launch("wm2f_panoptic_match", hist, _p(hist), _p(pred_label), _p(gt_label), _p(n_pred), _p(n_gt), _p(gt_match), _p(gt_iou),
+            _p(pred_state), B, P, G, int(bool(void_as_background)), tag="panoptic_match")
+    return gt_match, gt_iou, pred_state
+
+
+def semantic_confusion_(conf: torch.Tensor, n_out_of_range: torch.Tensor, pred: torch.Tensor, gt: torch.Tensor,
+                        ignore_index: int | None = None, gt_ids: torch.Tensor | None = None,
+                        gt_cls: torch.Tensor | None = None, n_ids: torch.Tensor | None = None,
+                        background_label: int | None = None) -> None:
+    """conf (C, C) int64 += the confusion matrix (rows GT, columns prediction) of pred (B, ...) int64 / int32 / uint8
+    against gt (B, ...) uint8 / int32 (wm2f_semantic_confusion); n_out_of_range (1) int64 += the non-ignored pixels whose
+    prediction is outside [0, C).  gt holds classes, or raw ids when gt_ids (B, G) ascending, gt_cls (B, G) and n_ids (B)
+    int32 are given; an unlisted raw id then has class `background_label`, or is ignored without one.  In place, no
+    synchronisation."""
+    for name, t in (("conf", conf), ("n_out_of_range", n_out_of_range), ("pred", pred), ("gt", gt)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"semantic_confusion_: {name} must be a tensor")
+    if not conf.is_contiguous() or not n_out_of_range.is_contiguous():
+        raise ValueError("semantic_confusion_: conf and n_out_of_range must be contiguous (they are updated in place)")
+    conf, n_out = _req(conf, "conf", torch.int64), _req(n_out_of_range, "n_out_of_range", torch.int64)
+    pred, gt = _req(pred, "pred", pred.dtype), _req(gt, "gt", gt.dtype)
+    error = f"semantic_confusion_: prediction maps int64 / int32 / uint8 and GT maps uint8 / int32, got {pred.dtype} / {gt.dtype}"
+    pdt = _dtype_code(pred, (torch.int64, torch.int32, torch.uint8), error)
+    gdt = _dtype_code(gt, (torch.uint8, torch.int32), error)
+    if conf.dim() != 2 or conf.shape[0] != conf.shape[1] or n_out.numel() != 1:
+        raise ValueError("semantic_confusion_: conf must be (C, C) and n_out_of_range one element")
+    if pred.shape != gt.shape or pred.dim() < 2:
+        raise ValueError(f"semantic_confusion_: maps must be (B, ...) of one shape, got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    B, C = int(pred.shape[0]), int(conf.shape[0])
+    G = 0
+    if (gt_ids is None) != (gt_cls is None) or (gt_ids is None) != (n_ids is None):
+        raise ValueError("semantic_confusion_: gt_ids, gt_cls and n_ids go together")
+    if gt_ids is not None:
+        gt_ids, gt_cls, n_ids = _req(gt_ids, "gt_ids", torch.int32), _req(gt_cls, "gt_cls", torch.int32), _req(n_ids, "n_ids", torch.int32)
+        G = int(gt_ids.shape[1]) if gt_ids.dim() == 2 else -1
+        if gt_ids.shape != (B, G) or gt_cls.shape != (B, G) or n_ids.shape != (B,):
+            raise ValueError("semantic_confusion_: shapes disagree")
+    if B == 0 or pred[0].numel() == 0 or C == 0:
+        return
+    n = pred[0].numel()
+    ign = -2 ** 31 if ignore_index is None else int(ignore_index)
+    bg = -1 if background_label is None else int(background_label)
+    _launch("wm2f_semantic_confusion", pred, _p(pred), pdt, _p(gt), gdt, _p(gt_ids), _p(gt_cls), _p(n_ids), _p(conf), _p(n_out),
+            B, n, G, C, ign, bg, tag="semantic_confusion")
