@@ -861,6 +861,49 @@ int wm2f_poly_fill(int32_t* out, int H, int W, const int32_t* verts, int n_verts
                    int n_contours, const int32_t* call_offsets, const int32_t* values, const int32_t* call_row0,
                    const int32_t* item_offsets, int n_calls, int n_items, void* workspace, void* stream);
 
+/* ---- run-length encoding and decoding of id maps -------------------------------------------
+ * Scan order: `order` 0 flattens a (H, W) map row-major, v[y * W + x]; 1 column-major, v[x * H + y] (COCO's).
+ * Slots: map (B, H, W) is WM2F_F32 (-1.0 background, otherwise an id by the rule of wm2f_labelmap_instance_stats),
+ * WM2F_I32 or WM2F_U8; ids lie in [-1, N); slot 0 is id -1 and slot k + 1 is id k.  N <= WM2F_RLE_MAX_IDS.
+ * Toggles: slot k toggles at position t of the flattened image v[0 .. HW) when
+ *   - 0 < t < HW and exactly one of v[t - 1], v[t] has slot k, or
+ *   - t == 0 and v[0] has slot k, or
+ *   - t == HW and v[HW - 1] has slot k.
+ * A slot's toggle list is every such t, ascending; its length is even; runs cross line ends (the first pixel of a line
+ * is compared with the last pixel of the line before).  The runs of slot k are [t_0, t_1), [t_2, t_3), ...
+ * wm2f_labelmap_toggle_counts: counts (B, N + 1) int32 <- the length of every slot's toggle list;
+ *                         out_of_range (B) int32 <- the pixels whose value is outside [-1, N).  Such a pixel belongs to
+ *                         no slot (its neighbours still toggle against it); a caller treats a non-zero word as an error.
+ *                         workspace: wm2f_rle_workspace(B, H, W, N, order) bytes (-1 for a bad size), which the call
+ *                         fills with the per-group prefixes the write launch needs: it must reach
+ *                         wm2f_labelmap_toggles unchanged, with the same map and arguments.
+ * wm2f_labelmap_toggles:   offsets (B * (N + 1) + 1) int32 DEVICE = the exclusive prefix sums of counts, image-major
+ *                         then slot (CSR), the total last (< 2^31); positions (total) int32 <- every slot's toggle
+ *                         list at offsets[b * (N + 1) + slot].  Every place is computed from the counts: no float and
+ *                         no atomic takes part, and the result is bit-identical from run to run.  A position is stored
+ *                         only inside its slot's range, whatever offsets and workspace hold.  Consumes the workspace.
+ * Both read the map once, whatever N is.  Row-major: one wave per group of whole rows, 64 positions per step, ranks
+ * by ballot and popcount per distinct slot of the step, cursors in LDS (4 B per slot).  Column-major: one lane per
+ * column, a wave reading 64 adjacent pixels of a row per load; the workspace holds 4 B per (column, slot).
+ * wm2f_rle_paint:          runs (R, 4) int32 DEVICE: (image, start, length, value), positions in scan order `order`;
+ *                         out (B, H, W) int32, painted in place: value over [start, start + length), a later run over
+ *                         an earlier one (painter's order, whatever the schedule); pixels no run covers keep their
+ *                         value.  status (1) int32 DEVICE <- INT32_MAX, or the index of the first run with image
+ *                         outside [0, B), start < 0, length < 0 or start + length > HW: then the WHOLE call is
+ *                         refused and nothing is painted (a run is never clipped).  The call does not wait for the
+ *                         device; the caller reads status.  workspace: wm2f_rle_paint_workspace(B, H, W) bytes, a rank
+ *                         map.
+ * H, W <= 16384, B <= 32, else WM2F_EUNSUPPORTED. */
+#define WM2F_RLE_MAX_IDS 1024
+int64_t wm2f_rle_workspace(int B, int H, int W, int N, int order);
+int wm2f_labelmap_toggle_counts(const void* map, int dtype, int32_t* counts, int32_t* out_of_range, void* workspace,
+                                int B, int H, int W, int N, int order, void* stream);
+int wm2f_labelmap_toggles(const void* map, int dtype, const int32_t* offsets, int32_t* positions, void* workspace, int B,
+                          int H, int W, int N, int order, void* stream);
+int64_t wm2f_rle_paint_workspace(int B, int H, int W);
+int wm2f_rle_paint(int32_t* out, const int32_t* runs, int R, int32_t* status, void* workspace, int B, int H, int W,
+                   int order, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

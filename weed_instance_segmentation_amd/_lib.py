@@ -24,6 +24,7 @@ WM2F_CCL_VALUE, WM2F_CCL_BINARY, WM2F_CCL_RGB = 0, 1, 2
 WM2F_CCL_MAX_COLORS = 16
 WM2F_POLY_MAX_SIDE = 16384
 WM2F_POLY_MAX_COORD = 1 << 24
+WM2F_RLE_MAX_IDS = 1024
 WM2F_AUG_MAX_VIRTUAL = 65536
 WM2F_AUG_PRE_DESC_LEN, WM2F_AUG_LAB_DESC_LEN = 16, 12
 # return codes of include/wm2f.h
@@ -132,6 +133,11 @@ SIGNATURES = {
     "wm2f_resize_nearest": (c_int, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P]),
     "wm2f_poly_workspace": (c_int64, [_I, _I, _I]),
     "wm2f_poly_fill": (c_int, [_P, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P]),
+    "wm2f_rle_workspace": (c_int64, [_I, _I, _I, _I, _I]),
+    "wm2f_labelmap_toggle_counts": (c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "wm2f_labelmap_toggles": (c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "wm2f_rle_paint_workspace": (c_int64, [_I, _I, _I]),
+    "wm2f_rle_paint": (c_int, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
 }
 
 # additions of the profiling library (include/wm2f_prof.h)

@@ -343,6 +343,27 @@ def polygons_to_instance_map(polygons, ids, size, background: int = 255, device=
     return _fill_calls(out, [[p] for p in polygons], [int(i) for i in ids])
 
 
+def rle_to_instance_map(rles, ids, size=None, background: int = 255, device="cuda") -> torch.Tensor:
+    """`polygons_to_instance_map` for annotations stored as COCO RLE (crowd regions, exported datasets): an (H, W) int32
+    map of `background`, then RLE i (compressed or plain counts) painted with ids[i] in order, later ones over earlier
+    ones -- the caller numbers the ids as for polygons (1, 2, ..., skipping 255 where the loader does).  `size` = (H, W)
+    must agree with the RLEs' own; without it theirs is taken.  Returns the map on the device."""
+    from .rle import decode_rle
+    rles = list(rles)
+    if len(rles) != len(ids):
+        raise ValueError(f"{len(rles)} RLEs but {len(ids)} ids")
+    if size is not None:
+        h, w = int(size[0]), int(size[1])
+        if h <= 0 or w <= 0:
+            raise ValueError(f"size must be positive (H, W), got {size}")
+        for k, r in enumerate(rles):
+            if tuple(int(v) for v in r["size"]) != (h, w):
+                raise ValueError(f"RLE {k} has size {list(r['size'])}, the map {[h, w]}")
+        if not rles:
+            return torch.full((h, w), int(background), dtype=torch.int32, device=device)
+    return decode_rle(rles, size=size, format="coco", values=[int(i) for i in ids], background=background, device=device)
+
+
 # ---- host-side annotation parsing (the reference loaders' rules; no GPU involved)
 def _via_polygons(entry: dict, label2id: dict, scale_x: float, scale_y: float, skip_255: bool):
     """The polygons of one VIA-JSON entry (Sorghum, inference.py's ground truth): 'polygon' shapes whose 'classname'

@@ -397,12 +397,16 @@ class MeanAveragePrecision:
 
 
 # --------------------------------------------------------------------------- drop-ins for models/metrics.py
-def test_with_metrics(model, processor, data_loader, device, iou_type="segm") -> dict:
+def test_with_metrics(model, processor, data_loader, device, iou_type="segm", results_json=None) -> dict:
     """models/metrics.py::test_with_metrics with the same arguments and result, through the label-map route.
     `iou_type` (not an argument of the reference) goes to MeanAveragePrecision: "segm", "bbox" or both; the boxes are
-    those of the masks (`boxes_from_masks=True`), as this route has nothing else."""
+    those of the masks (`boxes_from_masks=True`), as this route has nothing else.
+    `results_json` (not an argument of the reference either): a path that receives the evaluated predictions as a COCO
+    results file (`rle.save_coco_results`), the images named by the batches' `file_names`, or numbered without them."""
     model.eval()
     metric = MeanAveragePrecision(iou_type=iou_type, boxes_from_masks=iou_type != "segm")
+    dumped: list = []
+    n_seen = 0
     print("Calculating Metrics...")
     for i, batch in enumerate(data_loader):
         if (i + 1) % 5 == 0:
@@ -411,10 +415,20 @@ def test_with_metrics(model, processor, data_loader, device, iou_type="segm") ->
         with torch.no_grad():
             outputs = model(pixel_values=pixel_values)
         predictions = processor.post_process_instance_segmentation(outputs=outputs, target_sizes=batch["target_sizes"],
-                                                                   threshold=0.5, mask_threshold=0.5)
+                                                                   threshold=0.5, mask_threshold=0.5,
+                                                                   **({} if results_json is None else {"return_instance_stats": True}))
         metric.update_from_maps([p["segmentation"] for p in predictions], [p["segments_info"] for p in predictions],
                                 batch["original_maps"], batch["id_mappings"])
+        if results_json is not None:
+            from .rle import coco_results
+            names = batch.get("file_names") or list(range(n_seen, n_seen + len(predictions)))
+            dumped += coco_results(predictions, names)
+            n_seen += len(predictions)
     results = metric.compute()
+    if results_json is not None:
+        import json
+        with open(results_json, "w") as f:
+            json.dump(dumped, f)
     model.train()
     return results
 

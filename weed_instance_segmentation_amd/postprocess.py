@@ -147,6 +147,7 @@ class Mask2FormerInstancePostProcessor:
 
         sizes = [tuple(int(v) for v in t) for t in target_sizes] if target_sizes is not None else [ops._GRID] * B
         seg_out: list = [None] * B
+        rle_out: list = [None] * B
         keep_all = torch.zeros(B, Q, dtype=torch.bool, device=dev)
         kept_q_all = torch.zeros(B, Q, dtype=torch.int32, device=dev)
         stats_all = torch.zeros(B, Q, 8, dtype=torch.int64, device=dev) if return_instance_stats else None
@@ -168,6 +169,10 @@ class Mask2FormerInstancePostProcessor:
             kept_q_all[ridx] = kept_q
             if return_instance_stats:
                 stats_all[ridx] = ops.labelmap_instance_stats(seg, N=Q)
+            if return_coco_annotation:  # one encode per distinct target size, whatever the number of instances
+                from .rle import encode_label_maps
+                for i, rles in zip(rows, encode_label_maps(seg, n=Q, format="hf")):
+                    rle_out[i] = list(rles.values())  # ascending ids, -1 first, only ids that still own a pixel
             for j, i in enumerate(rows):
                 seg_out[i] = seg[j]
 
@@ -188,7 +193,7 @@ class Mask2FormerInstancePostProcessor:
                     seg_info["centroid"] = tuple(centroid[i][r]) if area[i][r] > 0 else None
             segmentation = seg_out[i]
             if return_coco_annotation:
-                segmentation = convert_segmentation_to_rle(segmentation)
+                segmentation = rle_out[i]
             if return_binary_maps and ks:
                 segmentation = ops.instance_maps(logits[i], kept_q_all[i], len(ks), sizes[i])
             results.append({"segmentation": segmentation, "segments_info": segments})
