@@ -615,7 +615,15 @@ int wm2f_labelmap_to_masks(const int32_t* label_map, const int32_t* ids, uint8_t
  *                         max_det); gt_ignored (B, A, G) uint8.  Only the first max_det detections per (image, category)
  *                         are matched.  LDS holds the image's detections (16 B each), its GT (20 B each), and a flag
  *                         per (lane, GT): D <= 1024 and G <= 512 per image (46 KiB at both bounds and A * T = 40), else
- *                         WM2F_EUNSUPPORTED. */
+ *                         WM2F_EUNSUPPORTED.
+ * wm2f_coco_match_min:     wm2f_coco_match with a second triple inter2 (B, D, G), det_area2 (B, D), gt_area2 (B, G) int32:
+ *                         the IoU of a pair is min(inter / union, inter2 / union2), each quotient in fp64 and 0 where its
+ *                         intersection is 0 (Boundary AP, DESIGN section 25: the first triple counts mask pixels, the
+ *                         second the pixels of the boundary bands).  Area ranges, labels, order, ranks and every output are
+ *                         as in wm2f_coco_match, taken from the first triple; with a second triple equal to the first the
+ *                         outputs are those of wm2f_coco_match bit for bit.  The same kernel body (a template flag): the
+ *                         second intersection row sits in registers next to the first, the second areas add 4 B per
+ *                         detection and per GT to LDS -- 52 KiB at D = 1024, G = 512, A * T = 40.  Same bounds. */
 int wm2f_labelmap_pair_counts(const void* pred_map, int pred_dtype, const void* gt_map, int gt_dtype,
                               const int32_t* gt_ids, const int32_t* n_ids, int32_t* hist, int B, int64_t n_pixels, int P,
                               int G, void* stream);
@@ -627,6 +635,12 @@ int wm2f_coco_match(const int32_t* inter, const int32_t* det_area, const int32_t
                     const double* iou_thresholds, const double* area_ranges, int32_t* det_rank, uint8_t* det_matched,
                     uint8_t* det_ignored, uint8_t* gt_ignored, int B, int D, int G, int T, int A, int max_det,
                     void* stream);
+int wm2f_coco_match_min(const int32_t* inter, const int32_t* det_area, const int32_t* gt_area, const int32_t* inter2,
+                        const int32_t* det_area2, const int32_t* gt_area2, const int32_t* det_label,
+                        const int32_t* gt_label, const int32_t* det_order, const int32_t* n_det, const int32_t* n_gt,
+                        const double* iou_thresholds, const double* area_ranges, int32_t* det_rank,
+                        uint8_t* det_matched, uint8_t* det_ignored, uint8_t* gt_ignored, int B, int D, int G, int T,
+                        int A, int max_det, void* stream);
 
 /* ---- per-instance statistics of id maps on device ---------------------------------------
  * Area, bounding box and coordinate sums of every instance of B id maps, in one read of the maps: what a consumer of
@@ -650,6 +664,34 @@ int wm2f_coco_match(const int32_t* inter, const int32_t* det_area, const int32_t
  *                         pixel by pixel otherwise, with the same results. */
 int wm2f_labelmap_instance_stats(const void* map, int dtype, const int32_t* ids, const int32_t* n_ids, int64_t* stats,
                                  int B, int H, int W, int N, void* stream);
+
+/* ---- boundary bands of id maps on device ------------------------------------------------
+ * The pixel work of Boundary IoU (Cheng et al., CVPR 2021) for every instance of B id maps at once.  For a mask M the
+ * band is M minus its erosion by a (2d+1) x (2d+1) square, pixels beyond the image counting as outside M; on an id map
+ * a pixel with id k is INTERIOR iff that square around it lies inside the image and every pixel of it has id k, and is
+ * in the band of k otherwise.
+ * wm2f_labelmap_boundary:  map (B, H, W) is WM2F_F32, WM2F_I32 or WM2F_U8.  Which float is which id follows
+ *                         wm2f_labelmap_instance_stats (negative, fractional, not finite or >= 2^24: no id); a negative
+ *                         int32 is no id either.  A pixel without an id equals no id, so it ends every run it touches.
+ *                         out (B, H, W) int32, overwritten: the pixel's id where the pixel is in its instance's band,
+ *                         -1 where it is interior or has no id -- again an id map with -1 background.
+ *                         workspace: wm2f_labelmap_boundary_workspace(B, H, W) bytes = B * H * W, one byte per pixel,
+ *                         4-byte aligned for the four-pixel path; it needs no clearing and holds nothing afterwards.
+ *                         1 <= d <= 16384 (a d larger than both sides leaves no interior), H, W <= 16384, B <= 32, else
+ *                         WM2F_EUNSUPPORTED; sizes or d below 1 are WM2F_EINVAL.
+ *                         Two launches, each reading the map once, whatever d and the number of instances:
+ *                         rows -- a wave per row; the run of equal ids ending at x has length x - lastchange(x) + 1 and
+ *                         lastchange is a max-scan (in the lane, across the wave by shuffles, across 64- or 256-pixel
+ *                         steps by a carry); plane[y][x] = 1 iff that run has at least 2d+1 pixels, so the row segment
+ *                         centred at x passes iff x + d < W and plane[y][x + d].  Four pixels per lane when W % 4 == 0
+ *                         and map and workspace are aligned (16 B, uint8: 4 B), one otherwise, with the same results.
+ *                         columns -- a lane per column marching down a chunk of rows (at least 64 and 2d of them) with
+ *                         the count of consecutive rows that pass and carry one id in a register; at 2d+1 the pixel d
+ *                         rows up is interior.  A chunk walks d rows beyond each end of the rows it owns.
+ *                         All integer, bit-identical from run to run. */
+int64_t wm2f_labelmap_boundary_workspace(int B, int H, int W);
+int wm2f_labelmap_boundary(const void* map, int dtype, int32_t* out, void* workspace, int B, int H, int W, int d,
+                           void* stream);
 
 /* ---- panoptic quality and semantic mIoU on device ---------------------------------------
  * What scores the maps of post_process_panoptic_segmentation and post_process_semantic_segmentation: the segment

@@ -117,6 +117,9 @@ SIGNATURES = {
     "wm2f_mask_pair_counts_workspace": (c_int64, [_I, _I, c_int64]),
     "wm2f_mask_pair_counts": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, c_int64, _P]),
     "wm2f_coco_match": (c_int, [_P] * 14 + [_I, _I, _I, _I, _I, _I, _P]),
+    "wm2f_coco_match_min": (c_int, [_P] * 17 + [_I, _I, _I, _I, _I, _I, _P]),
+    "wm2f_labelmap_boundary_workspace": (c_int64, [_I, _I, _I]),
+    "wm2f_labelmap_boundary": (c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _P]),
     "wm2f_labelmap_instance_stats": (c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     "wm2f_panoptic_match": (c_int, [_P] * 8 + [_I, _I, _I, _I, _P]),
     "wm2f_semantic_confusion": (c_int, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, c_int64, _I, _I, _I, _I, _P]),

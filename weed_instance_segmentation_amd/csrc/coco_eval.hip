@@ -8,6 +8,8 @@
 //   pack_bits / mask_pairs : the same intersections and areas for (D, H, W) and (G, H, W) mask stacks, which may
 //                    overlap: pack to bits (one wave ballot per 64 pixels), then AND + popcount over 8 x 8 pair tiles.
 //   coco_match     : the greedy COCO matching, one 64-lane workgroup per image, a lane per (area range, IoU threshold).
+//                    coco_match_min is the same walk with a second (inter, area, area) triple: the IoU of a pair is the
+//                    smaller of the two quotients (Boundary AP: mask IoU and boundary IoU).
 #include "common.h"
 
 namespace wm2f {
@@ -191,13 +193,19 @@ struct MatchArgs {
   uint8_t* det_ignored;      // (B, A, T, D)
   uint8_t* gt_ignored;       // (B, A, G)
   int D, G, T, A, max_det;
+  const int32_t* inter2;     // kMin only: the second triple, shapes as the first
+  const int32_t* det_area2;
+  const int32_t* gt_area2;
 };
 
 // one 64-lane workgroup per image.  LDS: the image's detections (score order, label, area, rank), its GT sorted by
 // (label, index) -- each category's GT contiguous and in input order -- one fp64 IoU row, and a matched flag per
 // (lane, GT).  The walk is latency-bound, so nothing on its path reads global memory: the next detection's intersection
 // row is loaded into registers while the current one is walked.
+// kMin: a second intersection row in registers and the second areas of the GT and the detections in LDS (4 B each); the
+// IoU row holds min(inter / union, inter2 / union2).  Area ranges, labels, order and ranks come from the first triple.
 constexpr int kRowRegs = kMatchMaxG / 64;
+template <bool kMin>
 __global__ __launch_bounds__(64) void coco_match_kernel(MatchArgs p) {
   extern __shared__ __align__(8) unsigned char msmem[];
   const int b = blockIdx.x, lane = threadIdx.x;
@@ -211,7 +219,9 @@ __global__ __launch_bounds__(64) void coco_match_kernel(MatchArgs p) {
   int32_t* d_label = d_order + D;
   int32_t* d_area = d_label + D;
   int32_t* d_rank = d_area + D;
-  uint8_t* matched = reinterpret_cast<uint8_t*>(d_rank + D);
+  int32_t* s_area2 = d_rank + D;                 // kMin only: G
+  int32_t* d_area2 = s_area2 + (kMin ? G : 0);   // kMin only: D
+  uint8_t* matched = reinterpret_cast<uint8_t*>(d_area2 + (kMin ? D : 0));
   const int32_t* glab = p.gt_label + (int64_t)b * G;
   const int32_t* garea = p.gt_area + (int64_t)b * G;
   const int32_t* order = p.det_order + (int64_t)b * D;
@@ -228,6 +238,7 @@ __global__ __launch_bounds__(64) void coco_match_kernel(MatchArgs p) {
     s_area[pos] = garea[g];
     s_label[pos] = lg;
     s_idx[pos] = g;
+    if (kMin) s_area2[pos] = p.gt_area2[(int64_t)b * G + g];
   }
   for (int j = lane; j < AT * ng; j += 64) matched[j] = 0;
   for (int j = lane; j < A * G; j += 64) {
@@ -246,6 +257,7 @@ __global__ __launch_bounds__(64) void coco_match_kernel(MatchArgs p) {
       d_order[k] = d;
       d_label[k] = p.det_label[(int64_t)b * D + d];
       d_area[k] = p.det_area[(int64_t)b * D + d];
+      if (kMin) d_area2[k] = p.det_area2[(int64_t)b * D + d];
     }
     nv += __popcll(m);
   }
@@ -270,17 +282,20 @@ __global__ __launch_bounds__(64) void coco_match_kernel(MatchArgs p) {
     }
   __syncthreads();
   int row[kRowRegs];
+  int row2[kMin ? kRowRegs : 1];
   auto load_row = [&](int k) {
-    const int32_t* irow = p.inter + ((int64_t)b * D + d_order[k]) * G;
+    const int64_t off = ((int64_t)b * D + d_order[k]) * G;
 #pragma unroll
     for (int j = 0; j < kRowRegs; ++j) {
       const int pos = lane + 64 * j;
-      row[j] = pos < ng ? irow[s_idx[pos]] : 0;
+      row[j] = pos < ng ? p.inter[off + s_idx[pos]] : 0;
+      if constexpr (kMin) row2[j] = pos < ng ? p.inter2[off + s_idx[pos]] : 0;
     }
   };
   if (nv > 0 && ng > 0) load_row(0);
   for (int k = 0; k < nv; ++k) {
     const int d = d_order[k], r = d_rank[k], lab = d_label[k], ad = d_area[k];
+    const int ad2 = kMin ? d_area2[k] : 0;
     if (lane == 0) p.det_rank[(int64_t)b * D + d] = r;
     if (r >= p.max_det) {
       if (active) {
@@ -296,7 +311,13 @@ __global__ __launch_bounds__(64) void coco_match_kernel(MatchArgs p) {
       const int pos = lane + 64 * j;
       if (pos < ng) {
         const int x = row[j];
-        iou[pos] = x == 0 ? 0.0 : (double)x / ((double)ad + (double)s_area[pos] - (double)x);
+        double q = x == 0 ? 0.0 : (double)x / ((double)ad + (double)s_area[pos] - (double)x);
+        if constexpr (kMin) {
+          const int x2 = row2[j];
+          const double q2 = x2 == 0 ? 0.0 : (double)x2 / ((double)ad2 + (double)s_area2[pos] - (double)x2);
+          q = q2 < q ? q2 : q;
+        }
+        iou[pos] = q;
       }
     }
     if (k + 1 < nv && ng > 0) load_row(k + 1);  // in flight during the walk
@@ -454,16 +475,19 @@ extern "C" int wm2f_mask_pair_counts(const uint8_t* det_masks, const uint8_t* gt
   return WM2F_OK;
 }
 
-extern "C" int wm2f_coco_match(const int32_t* inter, const int32_t* det_area, const int32_t* gt_area,
-                               const int32_t* det_label, const int32_t* gt_label, const int32_t* det_order,
-                               const int32_t* n_det, const int32_t* n_gt, const double* iou_thresholds,
-                               const double* area_ranges, int32_t* det_rank, uint8_t* det_matched, uint8_t* det_ignored,
-                               uint8_t* gt_ignored, int B, int D, int G, int T, int A, int max_det, void* stream) {
-  const char* who = "wm2f_coco_match";
+// both entry points; inter2 == nullptr selects the plain kernel
+static int coco_match_launch(const char* who, bool two, const int32_t* inter, const int32_t* det_area,
+                             const int32_t* gt_area, const int32_t* inter2, const int32_t* det_area2,
+                             const int32_t* gt_area2, const int32_t* det_label, const int32_t* gt_label,
+                             const int32_t* det_order, const int32_t* n_det, const int32_t* n_gt,
+                             const double* iou_thresholds, const double* area_ranges, int32_t* det_rank,
+                             uint8_t* det_matched, uint8_t* det_ignored, uint8_t* gt_ignored, int B, int D, int G, int T,
+                             int A, int max_det, void* stream) {
   WM2F_REQUIRE(det_area && det_label && det_order && n_det && n_gt && iou_thresholds && area_ranges && det_rank &&
                    det_matched && det_ignored,
                "%s: null pointer", who);
   WM2F_REQUIRE(G == 0 || (inter && gt_area && gt_label && gt_ignored), "%s: null GT pointer", who);
+  WM2F_REQUIRE(!two || (det_area2 && (G == 0 || (inter2 && gt_area2))), "%s: null pointer in the second triple", who);
   WM2F_REQUIRE(B > 0 && B < 65536 && D > 0 && G >= 0 && T > 0 && A > 0 && max_det > 0, "%s: bad size", who);
   if (A * T > kMatchMaxLanes || G > kMatchMaxG || D > kMatchMaxD) {
     set_error("%s: needs area ranges x thresholds <= %d, at most %d GT and %d detections per image (got %d x %d, %d, %d)",
@@ -471,9 +495,33 @@ extern "C" int wm2f_coco_match(const int32_t* inter, const int32_t* det_area, co
     return WM2F_EUNSUPPORTED;
   }
   MatchArgs a{inter, det_area, gt_area, det_label, gt_label, det_order, n_det, n_gt, iou_thresholds, area_ranges,
-              det_rank, det_matched, det_ignored, gt_ignored, D, G, T, A, max_det};
-  const size_t shm = (size_t)G * (sizeof(double) + 3 * sizeof(int32_t)) + (size_t)D * 4 * sizeof(int32_t) + (size_t)A * T * G;
-  hipLaunchKernelGGL(coco_match_kernel, dim3(B), dim3(64), shm, (hipStream_t)stream, a);
+              det_rank, det_matched, det_ignored, gt_ignored, D, G, T, A, max_det, inter2, det_area2, gt_area2};
+  const size_t shm = (size_t)G * (sizeof(double) + 3 * sizeof(int32_t)) + (size_t)D * 4 * sizeof(int32_t) + (size_t)A * T * G +
+                     (two ? (size_t)(G + D) * sizeof(int32_t) : 0);
+  if (two) hipLaunchKernelGGL(coco_match_kernel<true>, dim3(B), dim3(64), shm, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(coco_match_kernel<false>, dim3(B), dim3(64), shm, (hipStream_t)stream, a);
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;
+}
+
+extern "C" int wm2f_coco_match(const int32_t* inter, const int32_t* det_area, const int32_t* gt_area,
+                               const int32_t* det_label, const int32_t* gt_label, const int32_t* det_order,
+                               const int32_t* n_det, const int32_t* n_gt, const double* iou_thresholds,
+                               const double* area_ranges, int32_t* det_rank, uint8_t* det_matched, uint8_t* det_ignored,
+                               uint8_t* gt_ignored, int B, int D, int G, int T, int A, int max_det, void* stream) {
+  return coco_match_launch("wm2f_coco_match", false, inter, det_area, gt_area, nullptr, nullptr, nullptr, det_label, gt_label,
+                           det_order, n_det, n_gt, iou_thresholds, area_ranges, det_rank, det_matched, det_ignored, gt_ignored,
+                           B, D, G, T, A, max_det, stream);
+}
+
+extern "C" int wm2f_coco_match_min(const int32_t* inter, const int32_t* det_area, const int32_t* gt_area,
+                                   const int32_t* inter2, const int32_t* det_area2, const int32_t* gt_area2,
+                                   const int32_t* det_label, const int32_t* gt_label, const int32_t* det_order,
+                                   const int32_t* n_det, const int32_t* n_gt, const double* iou_thresholds,
+                                   const double* area_ranges, int32_t* det_rank, uint8_t* det_matched,
+                                   uint8_t* det_ignored, uint8_t* gt_ignored, int B, int D, int G, int T, int A,
+                                   int max_det, void* stream) {
+  return coco_match_launch("wm2f_coco_match_min", true, inter, det_area, gt_area, inter2, det_area2, gt_area2, det_label,
+                           gt_label, det_order, n_det, n_gt, iou_thresholds, area_ranges, det_rank, det_matched, det_ignored,
+                           gt_ignored, B, D, G, T, A, max_det, stream);
 }

@@ -6,6 +6,12 @@
 One launch of csrc/instance_stats.hip reads the map once, whatever the number of instances; nothing is copied to the
 host.  `post_process_instance_segmentation(..., return_instance_stats=True)` and the box mAP of `metrics.py` are built
 on the same kernel.
+
+    from weed_instance_segmentation_amd import boundary_maps
+    bands = boundary_maps(prediction["segmentation"])          # the boundary band of every instance, as an id map
+
+`boundary_maps` is the pixel work of Boundary IoU: two launches of csrc/boundary.hip whatever the
+number of instances and the width of the band.
 """
 from __future__ import annotations
 
@@ -64,3 +70,38 @@ def instance_statistics(segmentation, n: int | None = None, ids=None):
     if seg.dim() == 2:
         stats = stats[0]
     return stats_to_boxes(stats)
+
+
+def boundary_dilation(height: int, width: int, dilation_ratio: float = 0.02) -> int:
+    """The width in pixels of Boundary IoU's band for an image of this size: dilation_ratio of the diagonal, rounded as
+    Python rounds, at least 1."""
+    height, width = int(height), int(width)
+    if height < 1 or width < 1 or not dilation_ratio > 0:
+        raise ValueError(f"boundary_dilation: bad size {height} x {width} or ratio {dilation_ratio}")
+    return max(1, int(round(dilation_ratio * float(np.sqrt(height ** 2 + width ** 2)))))
+
+
+def boundary_maps(maps, dilation_ratio: float = 0.02, dilation: int | None = None) -> torch.Tensor:
+    """The boundary band (Boundary IoU, Cheng et al. 2021) of every instance of one (H, W) id map or a (B, H, W) stack
+    -- fp32 with -1 background, int32 or uint8, on the device or the host (a host map is moved to the current GPU).
+
+    A mask's band is the mask minus its erosion by a (2d+1) x (2d+1) square, nothing beyond the image counting as mask;
+    d = `boundary_dilation(H, W, dilation_ratio)`, or `dilation` pixels when that is given.  Returns an int32 device
+    tensor of the input's shape: the pixel's id inside its instance's band, -1 in the interior and where the input has no
+    id.  That is again an id map with -1 background: `render_label_overlay`, `instance_statistics` and
+    `encode_label_maps` take it as it is."""
+    if not torch.cuda.is_available():
+        raise _lib.Wm2fError("boundary_maps runs on a GPU only (no CPU fallback): no device is visible")
+    seg = torch.from_numpy(np.ascontiguousarray(maps)) if isinstance(maps, np.ndarray) else torch.as_tensor(maps)
+    if seg.dim() not in (2, 3):
+        raise ValueError(f"boundary_maps: expected (H, W) or (B, H, W), got {tuple(seg.shape)}")
+    if seg.dtype not in (torch.float32, torch.int32, torch.uint8):
+        raise TypeError(f"boundary_maps: maps fp32 / int32 / uint8, got {seg.dtype}")
+    H, W = int(seg.shape[-2]), int(seg.shape[-1])
+    d = boundary_dilation(H, W, dilation_ratio) if dilation is None else int(dilation)
+    if d < 1:
+        raise ValueError(f"boundary_maps: dilation must be at least 1, got {d}")
+    dev = seg.device if seg.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    stack = seg.to(dev)
+    out = ops.labelmap_boundary(stack.unsqueeze(0) if seg.dim() == 2 else stack, d)
+    return out[0] if seg.dim() == 2 else out

@@ -16,6 +16,11 @@ Two routes in:
 the tight box of every prediction and GT mask -- on the label-map route: one launch of
 csrc/instance_stats.hip per map stack gives the boxes, their integer intersections and areas go through the same
 matching kernel.
+
+`iou_type="boundary"` (alone or next to the others) is Boundary AP (Cheng et al., CVPR 2021) on the
+label-map route: the IoU of a pair is the smaller of its mask IoU and the IoU of the two masks' boundary bands, the area
+ranges still see mask areas.  The bands of a whole id map come from two launches of csrc/boundary.hip, their
+intersections from the same joint histogram, and the matching kernel takes both triples (`ops.coco_match_min`).
 """
 from __future__ import annotations
 
@@ -23,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .instances import boundary_dilation, boundary_maps  # noqa: F401  (re-exported: where callers look for metrics)
 
 IOU_THRESHOLDS = np.linspace(0.5, 0.95, 10)
 REC_THRESHOLDS = np.linspace(0.0, 1.0, 101)
@@ -39,7 +45,7 @@ def _device() -> torch.device:
     return torch.device("cuda", torch.cuda.current_device())
 
 
-IOU_TYPES = ("segm", "bbox")
+IOU_TYPES = ("segm", "bbox", "boundary")
 
 
 def box_pair_counts(pred_stats: torch.Tensor, gt_stats: torch.Tensor):
@@ -149,16 +155,21 @@ def summarize(precision, recall, max_dets) -> dict:
 
 
 class MeanAveragePrecision:
-    """torchmetrics.detection.MeanAveragePrecision on the GPU: update / compute / reset.  iou_type "segm", "bbox" or a
-    tuple / list of both.  torchmetrics' "bbox" scores boxes the caller supplies; those are not implemented, so "bbox"
-    alone still raises.  `boxes_from_masks=True` selects what is: the tight box of every prediction and GT mask, cut from
-    the id maps of `update_from_maps`."""
+    """torchmetrics.detection.MeanAveragePrecision on the GPU: update / compute / reset.  iou_type "segm", "bbox",
+    "boundary" or a tuple / list of them.  torchmetrics' "bbox" scores boxes the caller supplies; those are not
+    implemented, so "bbox" alone still raises.  `boxes_from_masks=True` selects what is: the tight box of every
+    prediction and GT mask, cut from the id maps of `update_from_maps`.  "boundary" is Boundary AP on the same route:
+    a pair's IoU is min(mask IoU, boundary IoU), the bands `dilation_ratio` of the image diagonal wide
+    (`boundary_dilation`), the area ranges on mask areas."""
 
     def __init__(self, iou_type="segm", max_detection_thresholds=None, class_metrics: bool = False,
-                 boxes_from_masks: bool = False):
+                 boxes_from_masks: bool = False, dilation_ratio: float = 0.02):
         types = (iou_type,) if isinstance(iou_type, str) else tuple(iou_type) if isinstance(iou_type, (tuple, list)) else None
         if not types or any(t not in IOU_TYPES for t in types) or len(set(types)) != len(types):
-            raise ValueError(f"iou_type={iou_type!r}: expected 'segm', 'bbox' or a tuple of both")
+            raise ValueError(f"iou_type={iou_type!r}: expected 'segm', 'bbox', 'boundary' or a tuple of them")
+        if not (isinstance(dilation_ratio, (int, float)) and 0 < dilation_ratio < 1):
+            raise ValueError(f"dilation_ratio={dilation_ratio!r}: expected a fraction of the image diagonal in (0, 1)")
+        self.dilation_ratio = float(dilation_ratio)
         if "bbox" in types and not boxes_from_masks:
             raise ValueError(f"iou_type={iou_type!r}: boxes supplied by the caller are not implemented; pass "
                              "boxes_from_masks=True to evaluate the tight boxes of the masks (update_from_maps)")
@@ -182,12 +193,18 @@ class MeanAveragePrecision:
             self._rng = torch.tensor(AREA_RANGES, dtype=torch.float64).to(dev)
         return self._thr, self._rng
 
-    def _match(self, dev, inter, det_area, gt_area, det_score, det_label, gt_label, n_det, n_gt, kind="segm"):
-        """All (B, D[, G]) device tensors, padded; launches the matching and stores the records of type `kind`."""
+    def _match(self, dev, inter, det_area, gt_area, det_score, det_label, gt_label, n_det, n_gt, kind="segm", second=None):
+        """All (B, D[, G]) device tensors, padded; launches the matching and stores the records of type `kind`.
+        `second`: another (inter, det_area, gt_area) triple -- the pair's IoU is the smaller of the two."""
         order = torch.sort(det_score, dim=1, descending=True, stable=True).indices.to(torch.int32)
         thr, rng = self._constants(dev)
-        rank, matched, ignored, gt_ig = ops.coco_match(inter, det_area, gt_area, det_label, gt_label, order, n_det, n_gt,
-                                                       thr, rng, self.max_detection_thresholds[-1])
+        if second is None:
+            rank, matched, ignored, gt_ig = ops.coco_match(inter, det_area, gt_area, det_label, gt_label, order, n_det,
+                                                           n_gt, thr, rng, self.max_detection_thresholds[-1])
+        else:
+            rank, matched, ignored, gt_ig = ops.coco_match_min(inter, det_area, gt_area, *second, det_label, gt_label,
+                                                               order, n_det, n_gt, thr, rng,
+                                                               self.max_detection_thresholds[-1])
         self._batches[kind].append({"n_det": n_det, "n_gt": n_gt, "score": det_score, "label": det_label, "rank": rank,
                               "matched": matched, "ignored": ignored, "gt_label": gt_label, "gt_ignored": gt_ig})
 
@@ -197,6 +214,9 @@ class MeanAveragePrecision:
         if "bbox" in self.iou_type:
             raise ValueError("iou_type 'bbox' evaluates the boxes of id maps: use update_from_maps (free-standing boxes "
                              "and mask stacks are not implemented for it)")
+        if "boundary" in self.iou_type:
+            raise ValueError("iou_type 'boundary' takes its bands from id maps: use update_from_maps (mask stacks, which "
+                             "may overlap, would need one erosion per mask and are not implemented for it)")
         if len(preds) != len(target):
             raise ValueError("preds and target must have the same length")
         dev = _device()
@@ -288,11 +308,12 @@ class MeanAveragePrecision:
         n_ids = torch.tensor([len(x) for x in gt_ids], dtype=torch.int32).to(dev)
         n_det = torch.tensor([len(x) for x in scores], dtype=torch.int32).to(dev)
         ids_t, cls_t, score_t, label_t = ids_t.to(dev), cls_t.to(dev), score_t.to(dev), label_t.to(dev)
-        segm, bbox = "segm" in self.iou_type, "bbox" in self.iou_type
+        segm, bbox, boundary = "segm" in self.iou_type, "bbox" in self.iou_type, "boundary" in self.iou_type
         inter = torch.empty(B, P, G, device=dev, dtype=torch.int32)
         det_area = torch.empty(B, P, device=dev, dtype=torch.int32)
         gt_area = torch.empty(B, G, device=dev, dtype=torch.int32)
         binter, bdet_area, bgt_area = (torch.empty_like(t) for t in (inter, det_area, gt_area))
+        einter, edet_area, egt_area = (torch.empty_like(t) for t in (inter, det_area, gt_area))  # the boundary bands'
         present = torch.empty(B, G, device=dev, dtype=torch.bool)  # the GT id has a pixel in its map
         groups: dict = {}
         for i in range(B):  # one launch per (size, prediction dtype, GT dtype)
@@ -302,7 +323,7 @@ class MeanAveragePrecision:
             gm = torch.stack([gts[i].to(dev) for i in rows])  # each host map copied once, stacked on the device
             ridx = torch.tensor(rows, device=dev)
             gids, gn = ids_t[ridx].contiguous(), n_ids[ridx].contiguous()
-            if segm:
+            if segm or boundary:
                 hist = ops.labelmap_pair_counts(pm, gm, gids, gn, P)
                 inter[ridx] = hist[:, 1:, 1:]
                 det_area[ridx] = hist[:, 1:, :].sum(2, dtype=torch.int32)
@@ -312,11 +333,20 @@ class MeanAveragePrecision:
                 gstats = ops.labelmap_instance_stats(gm, gids, gn)
                 binter[ridx], bdet_area[ridx], bgt_area[ridx] = box_pair_counts(ops.labelmap_instance_stats(pm, N=P), gstats)
                 present[ridx] = gstats[:, :, 0] > 0
+            if boundary:  # the bands of both stacks as id maps of their own, then the same histogram on them
+                d = boundary_dilation(pm.shape[1], pm.shape[2], self.dilation_ratio)
+                ehist = ops.labelmap_pair_counts(ops.labelmap_boundary(pm, d), ops.labelmap_boundary(gm, d), gids, gn, P)
+                einter[ridx] = ehist[:, 1:, 1:]
+                edet_area[ridx] = ehist[:, 1:, :].sum(2, dtype=torch.int32)
+                egt_area[ridx] = ehist[:, :, 1:].sum(1, dtype=torch.int32)
         cls_t = torch.where(present, cls_t, torch.full_like(cls_t, ABSENT))
         if segm:
             self._match(dev, inter, det_area, gt_area, score_t, label_t, cls_t, n_det, n_ids)
         if bbox:  # COCOeval with iouType "bbox": the area ranges see box areas on both sides
             self._match(dev, binter, bdet_area, bgt_area, score_t, label_t, cls_t, n_det, n_ids, kind="bbox")
+        if boundary:  # Boundary AP: min(mask IoU, boundary IoU) per pair, the area ranges on mask areas
+            self._match(dev, inter, det_area, gt_area, score_t, label_t, cls_t, n_det, n_ids, kind="boundary",
+                        second=(einter, edet_area, egt_area))
 
     # ------------------------------------------------------------------------------------------------- compute
     def _records(self, kind: str | None = None) -> _Records:
@@ -399,12 +429,13 @@ class MeanAveragePrecision:
 # --------------------------------------------------------------------------- drop-ins for models/metrics.py
 def test_with_metrics(model, processor, data_loader, device, iou_type="segm", results_json=None) -> dict:
     """models/metrics.py::test_with_metrics with the same arguments and result, through the label-map route.
-    `iou_type` (not an argument of the reference) goes to MeanAveragePrecision: "segm", "bbox" or both; the boxes are
-    those of the masks (`boxes_from_masks=True`), as this route has nothing else.
+    `iou_type` (not an argument of the reference) goes to MeanAveragePrecision: "segm", "bbox", "boundary" or a tuple of
+    them; the boxes are those of the masks (`boxes_from_masks=True`), as this route has nothing else.
     `results_json` (not an argument of the reference either): a path that receives the evaluated predictions as a COCO
     results file (`rle.save_coco_results`), the images named by the batches' `file_names`, or numbered without them."""
     model.eval()
-    metric = MeanAveragePrecision(iou_type=iou_type, boxes_from_masks=iou_type != "segm")
+    types = (iou_type,) if isinstance(iou_type, str) else tuple(iou_type) if isinstance(iou_type, (tuple, list)) else ()
+    metric = MeanAveragePrecision(iou_type=iou_type, boxes_from_masks="bbox" in types)
     dumped: list = []
     n_seen = 0
     print("Calculating Metrics...")

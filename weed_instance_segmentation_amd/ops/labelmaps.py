@@ -1,5 +1,6 @@
 """Label-map metrics: label expansion, pair counts and COCO matching, per-instance statistics
-(section 21), panoptic matching and the semantic confusion matrix (section 22)."""
+(section 21), panoptic matching and the semantic confusion matrix (section 22), boundary bands and the matching on the
+smaller of two IoUs (section 25)."""
 from __future__ import annotations
 
 import torch
@@ -67,21 +68,31 @@ def mask_pair_counts(det_masks: torch.Tensor, gt_masks: torch.Tensor):
     return inter, det_area, gt_area
 
 
-def coco_match(inter, det_area, gt_area, det_label, gt_label, det_order, n_det, n_gt, iou_thresholds, area_ranges,
-               max_det: int):
-    """Greedy COCO matching of B images (wm2f_coco_match): inter (B, D, G), det_* (B, D), gt_* (B, G), n_det / n_gt (B)
-    int32; iou_thresholds (T), area_ranges (A, 2) fp64.  Returns det_rank (B, D) int32, det_matched / det_ignored
-    (B, A, T, D) uint8, gt_ignored (B, A, G) uint8."""
+def _match_args(name, inter, det_area, gt_area, det_label, gt_label, det_order, n_det, n_gt, iou_thresholds, area_ranges):
+    """The checked arguments and sizes the two matching entry points share."""
     i32 = torch.int32
     inter, det_area, gt_area = _req(inter, "inter", i32), _req(det_area, "det_area", i32), _req(gt_area, "gt_area", i32)
     det_label, gt_label = _req(det_label, "det_label", i32), _req(gt_label, "gt_label", i32)
     det_order, n_det, n_gt = _req(det_order, "det_order", i32), _req(n_det, "n_det", i32), _req(n_gt, "n_gt", i32)
     thr, rng = _req(iou_thresholds, "iou_thresholds", torch.float64), _req(area_ranges, "area_ranges", torch.float64)
+    if inter.dim() != 3:
+        raise ValueError(f"{name}: inter must be (B, D, G)")
     B, D, G = (int(v) for v in inter.shape)
     T, A = int(thr.shape[0]), int(rng.shape[0])
     if (det_area.shape != (B, D) or det_label.shape != (B, D) or det_order.shape != (B, D) or gt_area.shape != (B, G)
             or gt_label.shape != (B, G) or n_det.shape != (B,) or n_gt.shape != (B,) or rng.shape != (A, 2)):
-        raise ValueError("coco_match: shapes disagree")
+        raise ValueError(f"{name}: shapes disagree")
+    return (inter, det_area, gt_area, det_label, gt_label, det_order, n_det, n_gt, thr, rng), (B, D, G, T, A)
+
+
+def coco_match(inter, det_area, gt_area, det_label, gt_label, det_order, n_det, n_gt, iou_thresholds, area_ranges,
+               max_det: int):
+    """Greedy COCO matching of B images (wm2f_coco_match): inter (B, D, G), det_* (B, D), gt_* (B, G), n_det / n_gt (B)
+    int32; iou_thresholds (T), area_ranges (A, 2) fp64.  Returns det_rank (B, D) int32, det_matched / det_ignored
+    (B, A, T, D) uint8, gt_ignored (B, A, G) uint8."""
+    (inter, det_area, gt_area, det_label, gt_label, det_order, n_det, n_gt, thr, rng), (B, D, G, T, A) = _match_args(
+        "coco_match", inter, det_area, gt_area, det_label, gt_label, det_order, n_det, n_gt, iou_thresholds, area_ranges)
+    i32 = torch.int32
     dev = inter.device
     det_rank = torch.empty(B, D, device=dev, dtype=i32)
     det_matched = torch.empty(B, A, T, D, device=dev, dtype=torch.uint8)
@@ -91,6 +102,50 @@ def coco_match(inter, det_area, gt_area, det_label, gt_label, det_order, n_det, 
             _p(n_gt), _p(thr), _p(rng), _p(det_rank), _p(det_matched), _p(det_ignored), _p(gt_ignored), B, D, G, T, A,
             int(max_det), tag="coco_match")
     return det_rank, det_matched, det_ignored, gt_ignored
+
+
+def coco_match_min(inter, det_area, gt_area, inter2, det_area2, gt_area2, det_label, gt_label, det_order, n_det, n_gt,
+                   iou_thresholds, area_ranges, max_det: int):
+    """`coco_match` on the smaller of two IoUs (wm2f_coco_match_min): the second triple inter2 (B, D, G), det_area2 (B, D),
+    gt_area2 (B, G) int32 next to the first; a pair's IoU is min(inter / union, inter2 / union2).  Area ranges, labels,
+    order, ranks and the four results are `coco_match`'s, taken from the first triple."""
+    (inter, det_area, gt_area, det_label, gt_label, det_order, n_det, n_gt, thr, rng), (B, D, G, T, A) = _match_args(
+        "coco_match_min", inter, det_area, gt_area, det_label, gt_label, det_order, n_det, n_gt, iou_thresholds, area_ranges)
+    i32 = torch.int32
+    inter2, det_area2, gt_area2 = _req(inter2, "inter2", i32), _req(det_area2, "det_area2", i32), _req(gt_area2, "gt_area2", i32)
+    if inter2.shape != (B, D, G) or det_area2.shape != (B, D) or gt_area2.shape != (B, G):
+        raise ValueError("coco_match_min: the second triple must have the shapes of the first")
+    dev = inter.device
+    det_rank = torch.empty(B, D, device=dev, dtype=i32)
+    det_matched = torch.empty(B, A, T, D, device=dev, dtype=torch.uint8)
+    det_ignored = torch.empty(B, A, T, D, device=dev, dtype=torch.uint8)
+    gt_ignored = torch.empty(B, A, G, device=dev, dtype=torch.uint8)
+    _launch("wm2f_coco_match_min", inter, _p(inter), _p(det_area), _p(gt_area), _p(inter2), _p(det_area2), _p(gt_area2),
+            _p(det_label), _p(gt_label), _p(det_order), _p(n_det), _p(n_gt), _p(thr), _p(rng), _p(det_rank), _p(det_matched),
+            _p(det_ignored), _p(gt_ignored), B, D, G, T, A, int(max_det), tag="coco_match_min")
+    return det_rank, det_matched, det_ignored, gt_ignored
+
+
+def labelmap_boundary(maps: torch.Tensor, d: int) -> torch.Tensor:
+    """(B, H, W) id maps (fp32 with -1 background, int32 or uint8) -> (B, H, W) int32 band maps
+    (wm2f_labelmap_boundary): a pixel keeps its id where the (2d+1) x (2d+1) square around it leaves the image or meets
+    another id -- the boundary band of its instance -- and is -1 where it is interior or has no id."""
+    if not isinstance(maps, torch.Tensor):
+        raise TypeError("labelmap_boundary: expected a tensor")
+    maps = _req(maps, "maps", maps.dtype)
+    dt = _dtype_code(maps, (torch.float32, torch.int32, torch.uint8),
+                     f"labelmap_boundary: maps fp32 / int32 / uint8, got {maps.dtype}")
+    if maps.dim() != 3:
+        raise ValueError(f"labelmap_boundary: maps must be (B, H, W), got {tuple(maps.shape)}")
+    B, H, W = (int(v) for v in maps.shape)
+    d = int(d)
+    if B == 0 or H == 0 or W == 0 or d < 1:
+        raise ValueError(f"labelmap_boundary: bad size {tuple(maps.shape)}, d = {d}")
+    out = torch.empty(B, H, W, device=maps.device, dtype=torch.int32)
+    nbytes = int(load().wm2f_labelmap_boundary_workspace(B, H, W))
+    ws = torch.empty(max(nbytes, 1), device=maps.device, dtype=torch.uint8)  # an unsupported size: the launch reports it
+    _launch("wm2f_labelmap_boundary", maps, _p(maps), dt, _p(out), _p(ws), B, H, W, d, tag="labelmap_boundary")
+    return out
 
 
 def labelmap_instance_stats(maps: torch.Tensor, ids: torch.Tensor | None = None, n_ids: torch.Tensor | None = None,
