@@ -447,6 +447,23 @@ int wm2f_conv3x3_split_fwd(const void* x, const void* w_split, const void* bias,
                            int Wi, int stride, int relu, int config, void* stream);
 int wm2f_conv3x3_split_config(int N, int P, int B, int n_cu);
 
+/* wm2f_stem7x7_pool_fwd: the ResNet stem in one kernel, NCHW fp32, at fp32 accuracy on the bf16 matrix cores (the split
+ *                        arithmetic of wm2f_conv1x1_split_fwd):  out (B, N, Hp, Wp) = MaxPool2d(3, stride 2,
+ *                        pad 1)(ReLU(conv7x7(x (B, Cin, Hi, Wi), W (N, Cin, 7, 7), stride 2, pad 3) + bias[N])),
+ *                        Hc = (Hi - 1) / 2 + 1, Hp = (Hc - 1) / 2 + 1, likewise W -- transformers' ResNetEmbeddings with
+ *                        BatchNorm folded into W and bias by the caller.  The raw convolution never reaches memory.
+ *                        w_split = wm2f_token_linear_split_weight of the (N, 160) matrix whose column 8 G + i, i < 7, is tap
+ *                        (c, ky, kx) = (G / 7, G % 7, i) for G < min(7 Cin, 20), whose column 8 G + 7, G < 7, is tap
+ *                        (2, 6, G) when Cin = 3, and which is zero elsewhere (ops.stem_weight_matrix).  Any Hi, Wi >= 1;
+ *                        Cin in {1, 2, 3} (49 Cin <= 160), N = 64, one image of x / out below 2 GiB; anything else is
+ *                        refused before any launch.  Conv pixels outside the conv map take no part in a pool window,
+ *                        input pixels outside the image are zero.  An output is non-finite exactly where its pool o conv
+ *                        receptive field holds a non-finite input.  Deterministic, no split-K, no atomics: an output does
+ *                        not depend on B, on the other images or on grid.  grid <= 0: one workgroup per CU, capped by the
+ *                        work; > 0: that many workgroups (the same bits, another speed). */
+int wm2f_stem7x7_pool_fwd(const void* x, const void* w_split, const void* bias, void* out, int B, int Cin, int N, int Hi,
+                          int Wi, int grid, void* stream);
+
 /* wm2f_token_wgrad_bf16: the weight / bias gradient of such a Linear (the backward autograd derives for nn.Linear; train
  *                        step of HF:1036-1103 under bf16 autocast):  dw (N, K) fp32 = dy (M, N)^T . x (M, K),
  *                        db (N) fp32 = column sums of dy (NULL: skipped); dy, x bf16 row-major, fp32 accumulation on the bf16

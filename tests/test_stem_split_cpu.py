@@ -1,0 +1,74 @@
+"""Host side of the one-kernel ResNet stem (csrc/stem_split.hip): the tests' reference against integer
+arithmetic, the K order the kernel is told, and the CPU route of the embedder."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+import stem_reference as S
+from weed_instance_segmentation_amd import ops
+
+
+@pytest.mark.parametrize("cin", S.CINS)
+@pytest.mark.parametrize("H,W", [(1, 1), (5, 4), (16, 16), (33, 31)])
+def test_stem_ref_on_integers_is_integer_arithmetic(H, W, cin):
+    x, w, b, ref, _ = S.case("ints", 2, cin, H, W)
+    y = F.conv2d(x.long(), w.long(), None, 2, 3) + b.long()[None, :, None, None]
+    want = F.max_pool2d(y.clamp_min(0).double(), 3, 2, 1)  # max pool has no integer kernel; the values are exact
+    assert ref.shape == (2, S.N, *S.out_hw(H, W))
+    assert torch.equal(ref, want)
+    assert torch.equal(S.stem_fp32(x, w, b).double(), ref)
+
+
+@pytest.mark.parametrize("cin", [1, 2, 3])
+def test_padded_weight_matrix_reproduces_the_convolution(cin):
+    """The (64, 160) matrix and the column order the kernel reads: W160 . unfold(x)[columns] is the convolution."""
+    g = torch.Generator().manual_seed(cin)
+    x = torch.randint(-3, 4, (2, cin, 9, 11), generator=g).double()
+    w = torch.randint(-3, 4, (S.N, cin, 7, 7), generator=g).double()
+    cols = ops.stem_weight_columns(cin)
+    assert cols.shape == (160,)
+    taps = cols[cols >= 0]
+    assert sorted(taps.tolist()) == list(range(49 * cin))  # every tap once
+    for G in range(min(7 * cin, 20)):  # a lane's eight columns: one kernel row, kx ascending
+        assert cols[8 * G:8 * G + 7].tolist() == list(range(7 * G, 7 * G + 7))
+    if cin == 3:
+        assert cols[7::8][:7].tolist() == list(range(140, 147)) and (cols[7::8][7:] == -1).all()
+    else:
+        assert (cols[7::8] == -1).all()
+    m = ops.stem_weight_matrix(w.float()).double()
+    assert m.shape == (S.N, 160)
+    assert (m[:, cols < 0] == 0).all()
+    u = F.unfold(x, 7, padding=3, stride=2)  # (B, 49 Cin, P), rows in (c, ky, kx) order
+    u160 = torch.cat([u, torch.zeros_like(u[:, :1])], 1)[:, torch.where(cols < 0, 49 * cin, cols)]
+    want = F.conv2d(x, w, None, 2, 3)
+    assert torch.equal(torch.matmul(m, u160).view_as(want), want)
+
+
+def test_stem_conv_pool_applies_only_to_built_shapes():
+    w = torch.zeros(64, 3, 7, 7)
+    assert not ops.stem_conv_pool_applies(torch.zeros(1, 3, 8, 8), w)  # on the host
+    meta = torch.empty(1, 3, 8, 8, device="meta")
+    assert not ops.stem_conv_pool_applies(meta, w)
+    assert not ops.stem_conv_pool_applies(meta, torch.zeros(64, 3, 3, 3))
+    assert not ops.stem_conv_pool_applies(torch.empty(1, 4, 8, 8, device="meta"), torch.zeros(64, 4, 7, 7))
+    assert not ops.stem_conv_pool_applies(meta, torch.zeros(32, 3, 7, 7))
+    with pytest.raises(ValueError):
+        ops.stem_weight_columns(4)
+
+
+@pytest.mark.parametrize("H,W", [(16, 16), (33, 31)])
+def test_embedder_on_cpu_takes_the_eager_route(H, W):
+    from weed_instance_segmentation_amd.backbone_resnet import _Embedder
+    torch.manual_seed(0)
+    emb = _Embedder(3, 64).eval()
+    emb.embedder.normalization.running_mean.uniform_(-0.2, 0.2)
+    emb.embedder.normalization.running_var.uniform_(0.5, 1.5)
+    x = torch.randn(2, 3, H, W)
+    with torch.no_grad():
+        got = emb(x)
+        want = emb.pooler(emb.embedder(x))
+    assert torch.equal(got, want)
+    assert "_wm2f_split" not in emb.embedder.__dict__
+    # ops.stem_conv_pool itself: a host tensor takes the split=False chain in torch ops
+    w, b = torch.randn(64, 3, 7, 7), torch.randn(64)
+    assert torch.equal(ops.stem_conv_pool(x, w, b), F.max_pool2d(F.relu(F.conv2d(x, w, b, 2, 3)), 3, 2, 1))

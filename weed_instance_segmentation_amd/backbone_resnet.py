@@ -161,6 +161,11 @@ class _Embedder(nn.Module):
             # inference: bias + ReLU + 3x3 / 2 max pool in one pass over the raw convolution output
             c = e.convolution
             w, b = _folded(c, e.normalization, e._fold)
+            if ((c.stride, c.padding, c.dilation, c.groups) == ((2, 2), (3, 3), (1, 1), 1)
+                    and ops.stem_conv_pool_applies(x, w)):
+                # 7x7 / 2 convolution, bias, ReLU and pool in one split-bf16 kernel; the folded w is the cache's identity,
+                # so a new fold (weight or BatchNorm version) re-splits
+                return ops.stem_conv_pool(x, w, b, w_split=ops.split_weight_cached(e, "stem", w, tap_major=True))
             y = torch.nn.functional.conv2d(x, w, None, c.stride, c.padding)
             if y.shape[-2] % 2 == 0 and y.shape[-1] % 8 == 0:
                 return ops.bias_relu_maxpool(y, b)

@@ -27,7 +27,8 @@ from .ccl import label_components, resize_nearest_tables
 from .fused import (add_broadcast, bias_act_, bias_relu_maxpool, group_norm_act_, group_norm_tokens_, resize_bilinear,
                     resize_pyramid, tokens_to_nchw)
 from .gemm import (conv1x1, conv1x1_applies, conv3x3, conv3x3_applies, linear_tokens, split_weight, split_weight_3x3,
-                   split_weight_cached, token_linear, token_linear_applies, token_wgrad, token_wgrad_applies)
+                   split_weight_cached, split_weight_stem, stem_conv_pool, stem_conv_pool_applies, stem_weight_columns,
+                   stem_weight_matrix, token_linear, token_linear_applies, token_wgrad, token_wgrad_applies)
 from .k1 import (k1_bwd_deterministic, k1_lane_order, k1_lane_rows, k1_lanes_applies, k1_rows_applies, ms_deform_attn,
                  ms_deform_attn_bwd, ms_deform_attn_fused, ms_deform_attn_fused_lanes, ms_deform_attn_fused_packed,
                  ms_deform_attn_rows, ms_deform_attn_variant)

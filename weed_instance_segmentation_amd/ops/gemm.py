@@ -7,7 +7,7 @@ import torch
 
 from .._lib import load
 from ._core import _launch, _p, _req
-from .fused import bias_act_
+from .fused import bias_act_, bias_relu_maxpool
 
 
 def token_linear_applies(x: torch.Tensor, weight: torch.Tensor) -> bool:
@@ -34,13 +34,18 @@ def split_weight_cached(owner, name: str, weight: torch.Tensor, base: torch.Tens
                         tap_major: bool = False) -> torch.Tensor:
     """split_weight(weight), kept in owner.__dict__ under `name` and redone when the weight changes: another tensor (held by
     weak reference: `base` when weight is a fresh view of it each call), another version, storage or device.
-    tap_major=True: weight is a 3x3 kernel (N, Cin, 3, 3), split as conv3x3 reads it (split_weight_3x3)."""
+    tap_major=True: weight is a convolution kernel, split in the K order its kernel reads: (N, Cin, 3, 3) as conv3x3 does
+    (split_weight_3x3), (64, Cin, 7, 7) as stem_conv_pool does (split_weight_stem)."""
     ident = weight if base is None else base
     c = owner.__dict__.setdefault("_wm2f_split", {})
     key = (ident._version, weight.data_ptr(), weight.device, tuple(weight.shape))
     hit = c.get(name)
     if hit is None or hit[0]() is not ident or hit[1] != key:
-        hit = (weakref.ref(ident), key, split_weight_3x3(weight) if tap_major else split_weight(weight))
+        if not tap_major:
+            ws = split_weight(weight)
+        else:
+            ws = split_weight_stem(weight) if tuple(weight.shape[2:]) == (7, 7) else split_weight_3x3(weight)
+        hit = (weakref.ref(ident), key, ws)
         c[name] = hit
     return hit[2]
 
@@ -207,6 +212,79 @@ def conv3x3(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = N
     out = torch.empty(B, N, Ho, Wo, device=x.device, dtype=torch.float32)
     _launch("wm2f_conv3x3_split_fwd", x, _p(x), _p(w_split), _p(bias), _p(out), B, Cin, N, H, W, int(stride), 1 if relu else 0,
             int(config), tag=f"conv3x3_C{Cin}_N{N}_P{Ho * Wo}")
+    return out
+
+
+STEM_K = 160  # K of the stem's split weight: five k-steps of 32
+
+
+def stem_weight_columns(cin: int) -> torch.Tensor:
+    """The K order wm2f_stem7x7_pool_fwd reads (csrc/stem_split.hip): for each of the 160 columns of its weight matrix the
+    index of the tap it holds in the flat (c, ky, kx) order of a (Cin, 7, 7) kernel, or -1 for a column of padding.
+    Column 8 G + i, i < 7, is tap (G // 7, G % 7, i) for the first min(7 Cin, 20) kernel rows G -- a lane's 8 consecutive
+    columns are one kernel row, 7 consecutive floats of one input row; with Cin = 3 the 21st kernel row (2, 6) rides in
+    the eighth columns, column 8 G + 7 holding its tap kx = G for G < 7."""
+    if cin not in (1, 2, 3):
+        raise ValueError(f"stem_weight_columns: Cin = {cin} (1, 2 and 3 are built)")
+    cols = torch.full((STEM_K,), -1, dtype=torch.long)
+    rows = 7 * cin
+    for G in range(min(rows, STEM_K // 8)):
+        cols[8 * G:8 * G + 7] = torch.arange(7 * G, 7 * G + 7)
+    if rows > STEM_K // 8:
+        cols[7:8 * 7:8] = torch.arange(7 * 20, 7 * 21)
+    return cols
+
+
+def stem_weight_matrix(weight: torch.Tensor) -> torch.Tensor:
+    """The stem's (64, Cin, 7, 7) kernel as the (64, 160) matrix of stem_weight_columns, zero in the padding columns."""
+    N, cin = int(weight.shape[0]), int(weight.shape[1])
+    cols = stem_weight_columns(cin).to(weight.device)
+    flat = torch.cat([weight.reshape(N, -1), weight.new_zeros(N, 1)], 1)
+    return flat[:, torch.where(cols < 0, torch.full_like(cols, 49 * cin), cols)].contiguous()
+
+
+def split_weight_stem(weight: torch.Tensor) -> torch.Tensor:
+    """The split of the stem's kernel (64, Cin, 7, 7) for wm2f_stem7x7_pool_fwd: split_weight of stem_weight_matrix."""
+    return split_weight(stem_weight_matrix(_req(weight, "weight")))
+
+
+def stem_conv_pool_applies(x: torch.Tensor, weight: torch.Tensor) -> bool:
+    """Shapes wm2f_stem7x7_pool_fwd is built for: fp32 NCHW on a GPU, weight (64, Cin, 7, 7) with Cin in {1, 2, 3}, one
+    image of x / out below 2 GiB (any map size)."""
+    if x.dim() != 4 or weight.dim() != 4 or tuple(weight.shape[2:]) != (7, 7):
+        return False
+    N, C = int(weight.shape[0]), int(weight.shape[1])
+    _, K, H, W = x.shape
+    Hp, Wp = ((H - 1) // 2) // 2 + 1, ((W - 1) // 2) // 2 + 1
+    return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and C == K and C in (1, 2, 3)
+            and N == 64 and H >= 1 and W >= 1 and K * H * W * 4 < (1 << 31) and N * Hp * Wp * 4 < (1 << 31))
+
+
+def stem_conv_pool(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, w_split: torch.Tensor | None = None,
+                   split: bool = True, grid: int = 0) -> torch.Tensor:
+    """The ResNet stem (inference, no autograd): MaxPool2d(3, 2, 1)(ReLU(conv2d(x, weight, stride 2, padding 3) + bias)),
+    x (B, Cin, H, W) fp32, weight (N, Cin, 7, 7) with BatchNorm folded in by the caller.
+    split=True: wm2f_stem7x7_pool_fwd, one kernel at fp32 accuracy on the bf16 matrix cores (the raw convolution never
+    reaches memory), with `w_split` = split_weight_stem(weight) if the caller keeps one; shapes outside
+    stem_conv_pool_applies take the split=False path.  grid > 0 forces that many workgroups (tests; the same bits), 0 lets
+    the kernel choose.
+    split=False: F.conv2d, then bias_relu_maxpool (or the same in torch ops where its map conditions fail)."""
+    if not split or not stem_conv_pool_applies(x, weight):
+        y = torch.nn.functional.conv2d(x, weight, None, 2, 3)
+        if y.is_cuda and y.dtype == torch.float32 and y.shape[-2] % 2 == 0 and y.shape[-1] % 8 == 0:
+            return bias_relu_maxpool(y, bias)
+        return torch.nn.functional.max_pool2d(torch.relu_(y.add_(bias[None, :, None, None])), 3, 2, 1)
+    x, bias = _req(x, "x"), _req(bias, "bias")
+    N, Cin = int(weight.shape[0]), int(weight.shape[1])
+    B, _, H, W = x.shape
+    if bias.shape != (N,):
+        raise ValueError(f"stem_conv_pool: bias {tuple(bias.shape)} for {N} channels")
+    if w_split is None:
+        w_split = split_weight_stem(weight)
+    elif w_split.dtype != torch.uint8 or w_split.numel() != N * STEM_K * 6 or w_split.device != x.device:
+        raise ValueError("stem_conv_pool: w_split is not split_weight_stem(weight)")
+    out = torch.empty(B, N, ((H - 1) // 2) // 2 + 1, ((W - 1) // 2) // 2 + 1, device=x.device, dtype=torch.float32)
+    _launch("wm2f_stem7x7_pool_fwd", x, _p(x), _p(w_split), _p(bias), _p(out), B, Cin, N, H, W, int(grid), tag="stem7x7_pool")
     return out
 
 
