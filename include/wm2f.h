@@ -963,6 +963,68 @@ int64_t wm2f_rle_paint_workspace(int B, int H, int W);
 int wm2f_rle_paint(int32_t* out, const int32_t* runs, int R, int32_t* status, void* workspace, int B, int H, int W,
                    int order, void* stream);
 
+/* ---- tracing id maps into polygons ---------------------------------------------------------
+ * The inverse of wm2f_poly_fill.  map (B, H, W) is WM2F_F32 (-1.0 background), WM2F_I32 or WM2F_U8 as above; ids lie in
+ * [-1, N), N <= WM2F_RLE_MAX_IDS; id -1 is never traced.  4 * B * H * W < 2^31 and B <= 4096, else WM2F_EUNSUPPORTED.
+ * Edges: a side of a pixel (y, x) with id k >= 0 is a boundary side when the pixel across it has another value or lies
+ *   outside the map.  Sides: 0 top, 1 right, 2 bottom, 3 left.  A boundary side is a directed unit edge on the corner
+ *   lattice (x in [0, W], y in [0, H], y down): top (x, y) -> (x + 1, y), right (x + 1, y) -> (x + 1, y + 1), bottom
+ *   (x + 1, y + 1) -> (x, y + 1), left (x, y + 1) -> (x, y); the segment lies on the right of the heading, so outer loops
+ *   run clockwise on screen.  The key of an edge is 4 * (y * W + x) + side; edges are numbered by (image, key).
+ * Successor: at the head vertex of an edge of heading d, with L the pixel ahead-left and R the pixel ahead-right: L has
+ *   id k -> turn left (side (d + 3) % 4 of L); else R has id k -> straight (side d of R); else turn right (side
+ *   (d + 1) % 4 of the edge's own pixel).  Left first makes a segment 8-connected at a saddle vertex.  Every edge has one
+ *   successor and one predecessor: the edges of an id are disjoint closed loops.
+ * Loops: a loop's leader is its edge of lowest key, rank 0; ranks grow along successors.  Loops are ordered by image, then
+ *   id, then leader key.
+ * Points, coords 0 (crack): an edge emits its tail vertex -- always, or with simplify only when its heading differs from
+ *   its predecessor's.  Exact: the even-odd interior of an id's loops at pixel centres is the id's mask.
+ * Points, coords 1 (pixel): an edge emits its own pixel (x, y) iff that pixel differs from its predecessor's pixel; a loop
+ *   in which no edge does (round a single pixel) emits that pixel once, at its leader.  With simplify, a loop of more
+ *   than two such points drops every point b whose cyclic neighbours a, c satisfy b - a == c - b.
+ * A loop's point list starts at its emitting edge of lowest rank.
+ * twice_area of a loop: the sum over its edges tail (xa, ya) -> head (xb, yb) of xa * yb - xb * ya; > 0 for an outer loop,
+ *   < 0 for a hole, and an id's loops sum to twice its pixel count.
+ * The chain (every array is DEVICE memory; no call waits for the device):
+ * wm2f_trace_count:   counts (B + 1) int32 <- [E, the number of edges of the whole stack; then per image the pixels whose
+ *                     value is outside [-1, N) (they are never traced; a caller treats a non-zero word as an error)].
+ *                     workspace: wm2f_trace_workspace(B, H, W, N) bytes (-1 for a bad size): a word per pixel (the side
+ *                     mask and the prefix of the edge count inside its block of 256 pixels) and a word per block.  It
+ *                     must reach wm2f_trace_link unchanged, with the same map and arguments.
+ * wm2f_trace_link:    E as read back from counts[0].  edge_workspace: wm2f_trace_edge_workspace(E) bytes, nine int32
+ *                     arrays of E: key (4 * pixel index in the stack + side), next, prev, leader, rank, and four the
+ *                     pointer jumping uses.  Fills key, next and prev.
+ * wm2f_trace_rank:    leader and rank of every edge, by wm2f_trace_rounds(E) = max(1, ceil(log2 E)) launches of pointer
+ *                     jumping along prev.
+ * wm2f_trace_flags:   flag (E) int32 <- 1 where the edge emits a point under (coords, simplify); lead (E) int32 <- 1 at
+ *                     leaders.  sum(lead) is the number of loops, sum(flag) of points.
+ * wm2f_trace_loops:   lead_prefix (E) = the inclusive prefix sums of lead.  Loop j (leader order) stores
+ *                     loop_key[j] = (image * N + id) << 32 | leader and loop_len[j] = its number of edges.
+ * wm2f_trace_scatter: loop_place (n_loops): the place of loop j in (image, id, leader) order; loop_base (n_loops + 1): the
+ *                     exclusive prefix sums of the lengths in that order.  Edge e goes to pos = loop_base[place] + rank:
+ *                     flag_sorted[pos] <- flag[e], edge_sorted[pos] <- e, term_sorted[pos] <- its twice_area term.
+ * wm2f_trace_emit:    flag_prefix (E) = the inclusive prefix sums of flag_sorted; points (P, 2) int32 (x, y) <- the point
+ *                     of every flagged place at flag_prefix - 1.
+ * No float and no atomic decides a place; every store is guarded by the range of its own array, whatever the tables
+ * hold; the number of launches depends on the bit length of E alone. */
+int64_t wm2f_trace_workspace(int B, int H, int W, int N);
+int64_t wm2f_trace_edge_workspace(int64_t E);
+int wm2f_trace_rounds(int64_t E);
+int wm2f_trace_count(const void* map, int dtype, int32_t* counts, void* workspace, int B, int H, int W, int N,
+                     void* stream);
+int wm2f_trace_link(const void* map, int dtype, const void* workspace, void* edge_workspace, int E, int B, int H, int W,
+                    int N, void* stream);
+int wm2f_trace_rank(void* edge_workspace, int E, void* stream);
+int wm2f_trace_flags(const void* edge_workspace, int32_t* flag, int32_t* lead, int E, int H, int W, int coords,
+                     int simplify, void* stream);
+int wm2f_trace_loops(const void* map, int dtype, const void* edge_workspace, const int32_t* lead_prefix,
+                     int64_t* loop_key, int32_t* loop_len, int E, int n_loops, int B, int H, int W, int N, void* stream);
+int wm2f_trace_scatter(const void* edge_workspace, const int32_t* flag, const int32_t* lead_prefix,
+                       const int32_t* loop_place, const int32_t* loop_base, int32_t* flag_sorted, int32_t* edge_sorted,
+                       int32_t* term_sorted, int E, int n_loops, int H, int W, void* stream);
+int wm2f_trace_emit(const void* edge_workspace, const int32_t* flag_sorted, const int32_t* edge_sorted,
+                    const int32_t* flag_prefix, int32_t* points, int E, int P, int H, int W, int coords, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@ from .metrics import MeanAveragePrecision  # noqa: F401
 from .instances import boundary_dilation, boundary_maps, instance_statistics  # noqa: F401
 from .rle import (coco_results, decode_rle, encode_label_maps, rle_from_string, rle_to_string,  # noqa: F401
                   save_coco_results)
+from .contours import (instance_polygons, save_via_annotations, trace_label_maps, via_annotations)  # noqa: F401
 from .preprocess import Mask2FormerImageProcessor  # noqa: F401
 from .augment import AugmentParams, TrainAugmentation  # noqa: F401
 from .visualize import (build_overlay_tables, convert_gt_map_to_result, render_label_overlay,  # noqa: F401

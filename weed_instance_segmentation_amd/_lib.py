@@ -142,6 +142,16 @@ SIGNATURES = {
     "wm2f_labelmap_toggles": (c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "wm2f_rle_paint_workspace": (c_int64, [_I, _I, _I]),
     "wm2f_rle_paint": (c_int, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
+    "wm2f_trace_workspace": (c_int64, [_I, _I, _I, _I]),
+    "wm2f_trace_edge_workspace": (c_int64, [c_int64]),
+    "wm2f_trace_rounds": (c_int, [c_int64]),
+    "wm2f_trace_count": (c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _P]),
+    "wm2f_trace_link": (c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "wm2f_trace_rank": (c_int, [_P, _I, _P]),
+    "wm2f_trace_flags": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "wm2f_trace_loops": (c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "wm2f_trace_scatter": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "wm2f_trace_emit": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
 }
 
 # additions of the profiling library (include/wm2f_prof.h)

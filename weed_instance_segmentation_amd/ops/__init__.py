@@ -45,6 +45,7 @@ from .polygons import fill_polygons
 from .postprocess import (_GRID, instance_any, instance_maps, instance_scores, instance_segmentation, panoptic_probs,
                           panoptic_relabel_, panoptic_segments, semantic_resize_argmax, semantic_scores)
 from .rle import labelmap_toggle_counts, labelmap_toggles, rle_paint_
+from .trace import labelmap_trace
 from .preprocess import augment_nearest_labels, augment_resize_normalize_u8, resize_nearest_labels, resize_normalize_u8
 from .swin import (SWIN_HEAD_DIMS, SWIN_WINDOW_SIZES, swin_window_attention, swin_window_attention_applies,
                    swin_window_attention_train)

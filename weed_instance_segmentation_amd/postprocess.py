@@ -107,8 +107,12 @@ class Mask2FormerInstancePostProcessor:
     def post_process_instance_segmentation(self, outputs, threshold: float = 0.5, mask_threshold: float = 0.5,
                                            overlap_mask_area_threshold: float = 0.8, target_sizes=None,
                                            return_coco_annotation: bool = False, return_binary_maps: bool = False,
-                                           return_instance_stats: bool = False):
-        """`return_instance_stats=True` (not an argument of the dependency) adds to every `segments_info` entry
+                                           return_instance_stats: bool = False, return_polygons: bool = False):
+        """`return_polygons=True` (not an argument of the dependency) adds "polygons" to every `segments_info` entry that
+        still owns a pixel of the returned id map: its boundary loops `{"points": (P, 2) int32 x, y, "hole": bool}` in
+        pixel coordinates, as `contours.trace_label_maps` gives them, from one trace per distinct target size (DESIGN
+        section 27).
+        `return_instance_stats=True` (not an argument of the dependency) adds to every `segments_info` entry
         "area" (int), "bbox" ([x, y, w, h] ints, COCO) and "centroid" ((cx, cy) floats, None when the area is 0) of the
         instance's pixels in the returned id map -- after later instances have painted over earlier ones, whatever
         form `segmentation` is returned in -- from one more launch per distinct target size and one more
@@ -197,6 +201,9 @@ class Mask2FormerInstancePostProcessor:
             if return_binary_maps and ks:
                 segmentation = ops.instance_maps(logits[i], kept_q_all[i], len(ks), sizes[i])
             results.append({"segmentation": segmentation, "segments_info": segments})
+        if return_polygons:
+            from .contours import _add_polygons
+            _add_polygons(results, maps=seg_out)
         return results
 
     def post_process_semantic_segmentation(self, outputs, target_sizes=None, return_segmentation_scores: bool = False):
