@@ -1025,6 +1025,68 @@ int wm2f_trace_scatter(const void* edge_workspace, const int32_t* flag, const in
 int wm2f_trace_emit(const void* edge_workspace, const int32_t* flag_sorted, const int32_t* edge_sorted,
                     const int32_t* flag_prefix, int32_t* points, int E, int P, int H, int W, int coords, void* stream);
 
+/* ---- merging the instances of overlapping tiles ---------------------------------------------
+ * An image larger than the model's input is cut into T overlapping tiles of one size (th, tw); every tile is segmented
+ * on its own; these calls decide which instances of neighbouring tiles are the same object, give them one id and write
+ * one (H, W) id map.  tests/tile_merge_reference.py restates the contract in numpy.
+ * Inputs (every array is DEVICE memory; no call waits for the device):
+ *   tiles (T, th, tw): id maps, WM2F_F32 (-1.0 background: the post-processor's output) or WM2F_I32.  A value is an id
+ *     by the rule of wm2f_labelmap_instance_stats (negative, fractional, not finite: no id; +-0 is id 0), and a value
+ *     outside [0, n_ids[t]) is no id either.
+ *   n_ids (T) int32, clamped to [0, N]; labels (T, N) int32.  Node g = t * N + i stands for instance i of tile t.
+ *   geom (T, 6) int32: (oy, ox, cy0, cy1, cx0, cx1) -- the tile's origin in the image and its CELL, the half-open
+ *     rectangle of output pixels it owns, in image coordinates.  The cells of a grid partition the image and each lies
+ *     inside its tile (tiling.tile_windows: the cut between two neighbours is the midpoint of their overlap).
+ *   pairs (P, 8) int32: (a, b, ay, ax, by, bx, h, w) -- tiles a < b whose windows intersect, and the intersection
+ *     rectangle (h, w) at (ay, ax) of tile a and (by, bx) of tile b.
+ * wm2f_tile_pair_counts:  hist (P, N+1, N+1) int32, overwritten: hist[p][i+1][j+1] = pixels of the rectangle with id i in
+ *                         tile a and id j in tile b; row / column 0 is "no id" (the whole array is cleared first, 4 P (N+1)^2
+ *                         bytes, and wm2f_tile_link reads it once).  area_a[i], the pixels of i inside the
+ *                         rectangle, is a row sum; area_b[j] a column sum.  The tiles are read in place.  Bins live in
+ *                         LDS while (N+1)^2 <= 16384 (N <= 127, 64 KiB) and are flushed once per workgroup; above that
+ *                         every add is a global integer atomic.  A wave inside one id pair adds its lane count once; the
+ *                         (none, none) bin is added once per workgroup.  Four pixels per lane when the rectangle's width
+ *                         and tw are multiples of 4 and both row starts are 16-byte aligned, pixel by pixel otherwise,
+ *                         with the same results.
+ * wm2f_tile_owned_counts: owned (T, N) int32, overwritten: owned[t][i] = pixels of id i inside tile t's cell.
+ * wm2f_tile_link:         LINK: i of tile a and j of tile b of pair p are the same object iff
+ *                           inter = hist[p][i+1][j+1] > 0, labels[a][i] == labels[b][j] and
+ *                           inter * den >= num * min(area_a[i], area_b[j])   (64-bit integers; equality links):
+ *                         the intersection over the smaller of the two areas inside the overlap, so a view cut off by a
+ *                         tile border still matches the whole view.  num >= 0, den >= 1.  Links are closed transitively
+ *                         (union-find; the root of a set is its smallest node), so two instances of ONE tile may end
+ *                         up in one set, joined through a neighbour.
+ *                         NUMBERING: sets in which some node owns a pixel (owned > 0) are numbered 0, 1, ... in
+ *                         ascending root order; remap (T, N) int32 <- the number of the node's set, -1 for a node of
+ *                         a set that owns nothing and for i >= n_ids[t]; n_merged (1) int32 <- the number of sets.
+ *                         workspace: wm2f_tile_merge_workspace(T, N, P) bytes (-1 for a bad size), no clearing needed.
+ *                         Five launches (init, link, flatten + owner marks, numbering scan, remap): a phase that needs
+ *                         every workgroup of the one before is its own launch.
+ * wm2f_tile_compose:      out (H, W) int32, written once and inside the cells only (the cells must partition the image: a
+ *                         pixel no cell covers is left as it was): pixel (y, x) of tile t's cell with local value v becomes
+ *                         remap[t][v] when v is an id and -1 otherwise.  Inside every cell the output is the owner
+ *                         tile's prediction, relabelled; an instance seen only where a neighbour owns the pixels, and
+ *                         not linked, is not reported.  remap of the owner tile sits in LDS; four pixels per lane when
+ *                         aligned as above.
+ * All integer: no float and no float atomic takes part, every result is independent of the schedule and bit-identical
+ * from run to run.  P == 0 (one tile, or no overlap) and N == 0 (out all -1) are legal.  Indices read from geom and pairs
+ * are clipped to the arrays they address.  th, tw, H, W <= WM2F_TILE_MAX_SIDE, N <= WM2F_TILE_MAX_IDS,
+ * T <= WM2F_TILE_MAX_TILES, P <= WM2F_TILE_MAX_PAIRS, else WM2F_EUNSUPPORTED. */
+#define WM2F_TILE_MAX_SIDE 16384
+#define WM2F_TILE_MAX_IDS 256
+#define WM2F_TILE_MAX_TILES 1024
+#define WM2F_TILE_MAX_PAIRS 16384
+int64_t wm2f_tile_merge_workspace(int T, int N, int P);
+int wm2f_tile_pair_counts(const void* tiles, int dtype, const int32_t* n_ids, const int32_t* pairs, int32_t* hist, int T,
+                          int th, int tw, int N, int P, void* stream);
+int wm2f_tile_owned_counts(const void* tiles, int dtype, const int32_t* n_ids, const int32_t* geom, int32_t* owned, int T,
+                           int th, int tw, int N, void* stream);
+int wm2f_tile_link(const int32_t* hist, const int32_t* pairs, const int32_t* labels, const int32_t* n_ids,
+                   const int32_t* owned, int32_t* remap, int32_t* n_merged, void* workspace, int T, int N, int P, int num,
+                   int den, void* stream);
+int wm2f_tile_compose(const void* tiles, int dtype, const int32_t* n_ids, const int32_t* geom, const int32_t* remap,
+                      int32_t* out, int T, int th, int tw, int N, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

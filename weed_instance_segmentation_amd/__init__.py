@@ -20,3 +20,4 @@ from .preprocess import Mask2FormerImageProcessor  # noqa: F401
 from .augment import AugmentParams, TrainAugmentation  # noqa: F401
 from .visualize import (build_overlay_tables, convert_gt_map_to_result, render_label_overlay,  # noqa: F401
                         render_segmentation, render_segmentations, save_comparison)
+from .tiling import TileGrid, merge_tile_results, segment_tiled, tile_windows  # noqa: F401

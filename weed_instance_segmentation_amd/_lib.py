@@ -26,6 +26,7 @@ WM2F_POLY_MAX_SIDE = 16384
 WM2F_POLY_MAX_COORD = 1 << 24
 WM2F_RLE_MAX_IDS = 1024
 WM2F_AUG_MAX_VIRTUAL = 65536
+WM2F_TILE_MAX_SIDE, WM2F_TILE_MAX_IDS, WM2F_TILE_MAX_TILES, WM2F_TILE_MAX_PAIRS = 16384, 256, 1024, 16384
 WM2F_AUG_PRE_DESC_LEN, WM2F_AUG_LAB_DESC_LEN = 16, 12
 # return codes of include/wm2f.h
 WM2F_OK, WM2F_EINVAL, WM2F_EUNSUPPORTED, WM2F_ELAUNCH = 0, -1, -2, -3
@@ -152,6 +153,11 @@ SIGNATURES = {
     "wm2f_trace_loops": (c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_trace_scatter": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "wm2f_trace_emit": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "wm2f_tile_merge_workspace": (c_int64, [_I, _I, _I]),
+    "wm2f_tile_pair_counts": (c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "wm2f_tile_owned_counts": (c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "wm2f_tile_link": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "wm2f_tile_compose": (c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
 }
 
 # additions of the profiling library (include/wm2f_prof.h)

@@ -1,0 +1,242 @@
+"""Tiled inference for images larger than the model's input.
+
+    from weed_instance_segmentation_amd import segment_tiled
+    result = segment_tiled(image, model, processor, tile=1024, overlap=256)      # a 6000 x 4000 field photograph
+    result["segmentation"]     # (H, W) int32 on the device, -1 background
+    result["segments_info"]    # one entry per plant, with the (tile, id) views it was merged from
+
+The image is cut into overlapping tiles at native resolution, every tile goes through the processor, the model and
+`post_process_instance_segmentation` as a single image would, and `merge_tile_results` decides which instances of
+neighbouring tiles are the same object, gives them one id and writes one id map -- four calls into csrc/tiles.hip that
+read each tile once, whatever the number of tiles, pairs and instances.  The contract of the merge is written out in
+include/wm2f.h.  Two instances of one tile may end up merged when a neighbour's instance links both.
+
+Not covered: rescaling before tiling (resize first), semantic and panoptic tiling (those blend logits, not ids), and
+test-time augmentation.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+
+import numpy as np
+import torch
+
+from . import ops
+
+MAX_MERGED_IDS = 4096  # what the consumers of an id map take (statistics, RLE, overlays, AP)
+
+
+@dataclass(frozen=True)
+class TileGrid:
+    """The tiles of one image: all of size (th, tw), numbered row-major over `ys` x `xs` (their origins).  `cuts_y` /
+    `cuts_x` bound the cells: output pixel (y, x) belongs to the tile whose row cell [cuts_y[r], cuts_y[r+1]) and column
+    cell [cuts_x[c], cuts_x[c+1]) contain it.  `windows[t]` = (y0, x0, y1, x1); `pairs` lists every a < b whose windows
+    intersect as (a, b, ay, ax, by, bx, h, w): the (h, w) intersection at (ay, ax) of tile a and (by, bx) of tile b."""
+    height: int
+    width: int
+    th: int
+    tw: int
+    ys: list = field(default_factory=list)
+    xs: list = field(default_factory=list)
+    cuts_y: list = field(default_factory=list)
+    cuts_x: list = field(default_factory=list)
+    windows: list = field(default_factory=list)
+    pairs: list = field(default_factory=list)
+
+    @property
+    def n_tiles(self) -> int:
+        return len(self.windows)
+
+    def owner_cell(self, t: int):
+        """(cy0, cy1, cx0, cx1): the output pixels tile t owns."""
+        r, c = divmod(t, len(self.xs))
+        return self.cuts_y[r], self.cuts_y[r + 1], self.cuts_x[c], self.cuts_x[c + 1]
+
+    def geom_table(self) -> np.ndarray:
+        """(T, 6) int32 rows (oy, ox, cy0, cy1, cx0, cx1) of include/wm2f.h."""
+        rows = [(w[0], w[1], *self.owner_cell(t)) for t, w in enumerate(self.windows)]
+        return np.asarray(rows, dtype=np.int32).reshape(len(rows), 6)
+
+    def pair_table(self) -> np.ndarray:
+        """(P, 8) int32 rows (a, b, ay, ax, by, bx, h, w) of include/wm2f.h."""
+        return np.asarray(self.pairs, dtype=np.int32).reshape(len(self.pairs), 8)
+
+
+def _axis(L: int, tile: int, overlap: int):
+    """Tile side, origins and cuts of one axis of length L."""
+    t = min(tile, L)
+    n = 1 if L <= tile else 1 + -(-(L - tile) // (tile - overlap))
+    o = [0] if n == 1 else [(i * (L - tile)) // (n - 1) for i in range(n)]
+    cuts = [0] + [(o[i] + t + o[i + 1]) // 2 for i in range(n - 1)] + [L]
+    return t, o, cuts
+
+
+def tile_windows(height: int, width: int, tile: int = 1024, overlap: int = 256) -> TileGrid:
+    """The tiles of a (height, width) image.  Per axis of length L: side t = min(tile, L); n = 1 tiles when L <= tile,
+    else 1 + ceil((L - tile) / (tile - overlap)); origins o[i] = (i * (L - tile)) // (n - 1) -- the first tile starts at
+    0, the last ends at L, neighbours overlap by at least `overlap`.  The cut between two neighbours is the midpoint of
+    their overlap, (o[i] + t + o[i+1]) // 2."""
+    height, width, tile, overlap = int(height), int(width), int(tile), int(overlap)
+    if height < 1 or width < 1:
+        raise ValueError(f"tile_windows: bad image size {height} x {width}")
+    if tile < 1 or not 0 <= overlap <= tile // 2:
+        raise ValueError(f"tile_windows: need tile >= 1 and 0 <= overlap <= tile // 2, got tile {tile}, overlap {overlap}")
+    th, ys, cuts_y = _axis(height, tile, overlap)
+    tw, xs, cuts_x = _axis(width, tile, overlap)
+    R, C = len(ys), len(xs)
+    windows = [(y, x, y + th, x + tw) for y in ys for x in xs]
+    # separable: every row / column whose extent meets r's / c's (itself included); b <= a is dropped below
+    row_meets = [[r2 for r2 in range(R) if abs(ys[r2] - ys[r]) < th] for r in range(R)]
+    col_meets = [[c2 for c2 in range(C) if abs(xs[c2] - xs[c]) < tw] for c in range(C)]
+    pairs = []
+    for a in range(R * C):
+        ra, ca = divmod(a, C)
+        for rb in row_meets[ra]:
+            for cb in col_meets[ca]:
+                b = rb * C + cb
+                if b <= a:
+                    continue
+                y0, y1 = max(ys[ra], ys[rb]), min(ys[ra], ys[rb]) + th
+                x0, x1 = max(xs[ca], xs[cb]), min(xs[ca], xs[cb]) + tw
+                pairs.append((a, b, y0 - ys[ra], x0 - xs[ca], y0 - ys[rb], x0 - xs[cb], y1 - y0, x1 - x0))
+    return TileGrid(height, width, th, tw, ys, xs, cuts_y, cuts_x, windows, pairs)
+
+
+def merged_segments_info(remap, n_merged: int, results) -> list:
+    """The host half of `merge_tile_results`: remap (T, N) integers (-1: not reported), the number of merged ids and the
+    per-tile results -> one entry per merged id: `id`, `label_id` (its members share it), `score` (the maximum over
+    members), `was_fused` False, `members` [(tile, id), ...] ascending."""
+    n_merged = int(n_merged)
+    if n_merged > MAX_MERGED_IDS:
+        raise ValueError(f"merge_tile_results: {n_merged} merged instances, but an id map takes at most {MAX_MERGED_IDS} "
+                         "downstream (statistics, RLE, overlays, AP): raise `threshold` or split the image")
+    remap = np.asarray(remap)
+    merged = [{"id": k, "label_id": None, "score": None, "was_fused": False, "members": []} for k in range(n_merged)]
+    for t, res in enumerate(results):
+        for info in res["segments_info"]:
+            i = int(info["id"])
+            k = int(remap[t, i])
+            if k < 0:
+                continue
+            if not k < n_merged:
+                raise ValueError(f"merge_tile_results: remap[{t}][{i}] = {k} with {n_merged} merged ids")
+            m = merged[k]
+            m["members"].append((t, i))
+            if m["label_id"] is None:
+                m["label_id"] = int(info["label_id"])
+            m["score"] = info["score"] if m["score"] is None else max(m["score"], info["score"])
+    return merged
+
+
+def _tile_tables(results, T: int):
+    """n_ids (T) and labels (T, N) int32 from the tiles' segments_info, whose ids must be 0 .. n-1 (the post-processor's)."""
+    n_ids = np.zeros(T, dtype=np.int32)
+    for t, res in enumerate(results):
+        ids = [int(s["id"]) for s in res["segments_info"]]
+        if ids != list(range(len(ids))):
+            raise ValueError(f"merge_tile_results: tile {t}: segments_info ids must be 0 .. n-1 in order, got {ids[:8]} ...")
+        n_ids[t] = len(ids)
+    N = int(n_ids.max()) if T else 0
+    labels = np.full((T, N), -1, dtype=np.int32)
+    for t, res in enumerate(results):
+        labels[t, :n_ids[t]] = [int(s["label_id"]) for s in res["segments_info"]]
+    return n_ids, labels
+
+
+def merge_tile_results(results, grid: TileGrid, merge_threshold=(1, 2), return_instance_stats: bool = False) -> dict:
+    """Merge the per-tile results of `post_process_instance_segmentation(target_sizes=[(grid.th, grid.tw)] * T)` (tiles in
+    `grid` order) into one image's result: {"segmentation": (H, W) int32 on the device with -1 background,
+    "segments_info": [...]}, entries as `merged_segments_info` gives them.
+
+    Two instances of neighbouring tiles with the same label are one object when their intersection inside the tiles'
+    overlap is at least `merge_threshold` = (num, den) of the smaller of their two areas inside that overlap; links are
+    transitive.  Every output pixel shows the prediction of the tile that owns it (`grid.cuts_y`, `grid.cuts_x`),
+    relabelled; an instance with no pixel in any owning cell is not reported.  `return_instance_stats=True` adds "area",
+    "bbox" and "centroid" of the merged map's instances, as the post-processor does.  Four kernel calls, one host-to-device
+    and one device-to-host copy."""
+    results = list(results)
+    T = grid.n_tiles
+    if len(results) != T:
+        raise ValueError(f"merge_tile_results: {len(results)} results for {T} tiles")
+    maps = [r["segmentation"] for r in results]
+    if not all(isinstance(m, torch.Tensor) for m in maps):
+        raise TypeError("merge_tile_results: every result needs a `segmentation` tensor (not RLE or binary maps)")
+    for m in maps:
+        ops._core._on_gpu(m, "segmentation")
+        if tuple(m.shape) != (grid.th, grid.tw):
+            raise ValueError(f"merge_tile_results: a tile map of {tuple(m.shape)}, the grid's tiles are {(grid.th, grid.tw)}")
+    num, den = (int(v) for v in merge_threshold)
+    if num < 0 or den < 1:
+        raise ValueError(f"merge_tile_results: merge_threshold (num, den) needs num >= 0 and den >= 1, got {(num, den)}")
+    n_ids_h, labels_h = _tile_tables(results, T)
+    N = int(labels_h.shape[1])
+    tiles = torch.stack(maps)
+    dev = tiles.device
+    geom_h, pairs_h = grid.geom_table(), grid.pair_table()
+    packed = np.concatenate([n_ids_h, labels_h.reshape(-1), geom_h.reshape(-1), pairs_h.reshape(-1)])
+    d = torch.from_numpy(packed).pin_memory().to(dev, non_blocking=True)
+    o = np.cumsum([0, T, T * N, T * 6, pairs_h.size])
+    n_ids, labels = d[o[0]:o[1]], d[o[1]:o[2]].view(T, N)
+    geom, pairs = d[o[2]:o[3]].view(T, 6), d[o[3]:o[4]].view(-1, 8)
+
+    hist = ops.tile_pair_counts(tiles, n_ids, pairs, N)
+    owned = ops.tile_owned_counts(tiles, n_ids, geom, N)
+    remap, n_merged = ops.tile_link(hist, pairs, labels, n_ids, owned, (num, den))
+    out = ops.tile_compose(tiles, n_ids, geom, remap, (grid.height, grid.width))
+
+    back = [remap.reshape(-1).to(torch.int64), n_merged.to(torch.int64)]
+    n_stats = min(int(n_ids_h.sum()), MAX_MERGED_IDS)  # an upper bound of n_merged known without a copy
+    if return_instance_stats and n_stats:
+        back.append(ops.labelmap_instance_stats(out.unsqueeze(0), N=n_stats).reshape(-1))
+    host = torch.cat(back).cpu()  # the one device-to-host copy
+    segments = merged_segments_info(host[:T * N].view(T, N).numpy(), int(host[T * N]), results)
+    if return_instance_stats and segments:
+        from .instances import stats_to_boxes
+        stats = host[T * N + 1:].view(-1, 8)[:len(segments)]
+        area, bbox, centroid = (v.tolist() for v in stats_to_boxes(stats))
+        for k, info in enumerate(segments):
+            info["area"] = area[k]
+            info["bbox"] = bbox[k]
+            info["centroid"] = tuple(centroid[k]) if area[k] > 0 else None
+    return {"segmentation": out, "segments_info": segments}
+
+
+def _device_image(image) -> torch.Tensor:
+    """A PIL RGB image, a numpy or torch (H, W, 3) uint8 array -> a uint8 (H, W, 3) tensor on the GPU."""
+    from ._lib import Wm2fError
+    from .preprocess import _image_hwc_u8
+    img = _image_hwc_u8(image, 0)
+    if not torch.cuda.is_available():
+        raise Wm2fError("segment_tiled runs on a GPU only (no CPU fallback): no device is visible")
+    if isinstance(img, torch.Tensor):
+        return img if img.is_cuda else img.cuda()
+    return torch.from_numpy(np.ascontiguousarray(img)).cuda()
+
+
+def segment_tiled(image, model, processor, tile: int = 1024, overlap: int = 256, batch_size: int = 4,
+                  threshold: float = 0.5, mask_threshold: float = 0.5, overlap_mask_area_threshold: float = 0.8,
+                  merge_threshold=(1, 2), return_instance_stats: bool = False) -> dict:
+    """Instance segmentation of an image of any size at native resolution: overlapping tiles (`tile_windows`), `batch_size`
+    of them at a time through `processor(images=...)`, `model(pixel_values=...)` under no_grad and
+    `processor.post_process_instance_segmentation(target_sizes=tile size)`, then `merge_tile_results`.  The image (PIL
+    RGB, numpy or torch (H, W, 3) uint8) is moved to the device once and the tiles are slices of it.  An image no larger
+    than one tile takes the same route with one tile.  `processor` is this package's `Mask2FormerImageProcessor` (or
+    anything that takes a list of device uint8 (h, w, 3) tensors and post-processes into id maps on the device); it is
+    called with `images=` alone, so its own size settings decide how a tile is fed.  Returns `merge_tile_results`'s
+    dictionary."""
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f"segment_tiled: batch_size must be at least 1, got {batch_size}")
+    img = _device_image(image)
+    grid = tile_windows(int(img.shape[0]), int(img.shape[1]), tile, overlap)
+    crops = [img[y0:y1, x0:x1] for y0, x0, y1, x1 in grid.windows]
+    results = []
+    with torch.no_grad(), torch.cuda.device(img.device):
+        for s in range(0, len(crops), batch_size):
+            batch = crops[s:s + batch_size]
+            inputs = processor(images=batch)  # the crops are on the device already
+            outputs = model(pixel_values=inputs["pixel_values"])
+            results += processor.post_process_instance_segmentation(
+                outputs, threshold=threshold, mask_threshold=mask_threshold,
+                overlap_mask_area_threshold=overlap_mask_area_threshold, target_sizes=[(grid.th, grid.tw)] * len(batch))
+    return merge_tile_results(results, grid, merge_threshold=merge_threshold, return_instance_stats=return_instance_stats)
