@@ -148,10 +148,9 @@ int wm2f_msdeform_fused_lanes_fwd(const void* value, const void* lanes, void* ou
  *              workgroups + loader waves), one workgroup per CU
  *   margin  window margin in pixels for the LDS-window kernel; sampling points farther than that
  *           from their reference point take a slow path (results never depend on it).
- * Any other variant returns WM2F_EUNSUPPORTED: superseded kernels (phased quads, half-head form), measured negatives
- * (flags instead of barriers, strip order, the round-1 loader schedule), timing ablations and stamped builds live in the
- * separate profiling library (include/wm2f_prof.h), never in libwm2f.so.  wm2f_msdeform_fwd / _fused_fwd are variant 0,
- * margin 4. */
+ * Any other variant returns WM2F_EUNSUPPORTED: timing ablations and stamped builds of these kernels live in the separate
+ * profiling library (include/wm2f_prof.h), never in libwm2f.so; the superseded kernels and measured negatives that other
+ * numbers once selected were removed and are recorded in DESIGN.md.  wm2f_msdeform_fwd / _fused_fwd are variant 0, margin 4. */
 int wm2f_msdeform_fwd_v(const void* value, const void* a, const void* b, const void* ref, void* out,
                         const int32_t* level_hw, int B, int S, int Q, int heads, int D, int L, int P,
                         int dtype, int fused, int variant, int margin, void* stream);

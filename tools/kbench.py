@@ -50,7 +50,7 @@ def main():
     S = sum(h * w for h, w in shapes)
     g = torch.Generator(device="cpu").manual_seed(0)
     res = {}
-    if any(k in only for k in ("k1", "k1f", "k1v", "k1t", "k1q", "k1s", "k1b", "k1l", "k1o", "k1h")):
+    if any(k in only for k in ("k1", "k1f", "k1v", "k1t", "k1s", "k1b", "k1l")):
         value = torch.randn(B, S, H, D, device=dev)
         # reference points + the module's initial offset pattern (|offset| <= 4 px) + noise
         ref = torch.cat([torch.stack(torch.meshgrid((torch.arange(h) + 0.5) / h, (torch.arange(w) + 0.5) / w, indexing="ij")[::-1], -1).reshape(-1, 2)
@@ -78,22 +78,19 @@ def main():
             res["k1_msdeform_fwd"] = r
         refl = ref[:, None, :].expand(S, L, 2).contiguous()
         if "k1v" in only:
-            for variant, margin in ((1, 4), (2, 4), (3, 4), (4, 4)) + (((44, 4),) if a.prof else ()):
+            for variant, margin in ((1, 4), (2, 4), (4, 4)) + (((44, 4),) if a.prof else ()):
                 r = timeit(lambda: ops.ms_deform_attn_variant(value, shapes, loc, aw, variant=variant, margin=margin), a.iters)
                 r.update(bytes=nbytes, GBps=nbytes / r["med_us"] / 1e3)
                 res[f"k1_unfused_variant{variant}_margin{margin}"] = r
                 r = timeit(lambda: ops.ms_deform_attn_variant(value, shapes, off, logits, refl, fused=True, variant=variant, margin=margin), a.iters)
                 r.update(bytes=nbytes, GBps=nbytes / r["med_us"] / 1e3)
                 res[f"k1_fused_variant{variant}_margin{margin}"] = r
-        if "k1l" in only:  # fused forms: [offsets | logits] rows vs lane-major rows vs the round-1 loader schedule, interleaved rounds
+        if "k1l" in only:  # fused forms: [offsets | logits] rows vs lane-major rows vs two arrays, interleaved rounds
             packed = torch.cat([off.reshape(B, S, -1), logits.reshape(B, S, -1)], -1).contiguous()
             lanes = ops.k1_lane_rows(off, logits)
             fns = {"packed_rows": lambda: ops.ms_deform_attn_fused_packed(value, shapes, packed, refl, H, L, P),
                    "lane_major_rows": lambda: ops.ms_deform_attn_fused_lanes(value, shapes, lanes, H),
-                   "two_arrays": lambda: ops.ms_deform_attn_variant(value, shapes, off, logits, refl, fused=True, variant=4),
-                   "two_arrays_half_head": lambda: ops.ms_deform_attn_variant(value, shapes, off, logits, refl, fused=True, variant=8),
-                   "two_arrays_sched0": lambda: ops.ms_deform_attn_variant(value, shapes, off, logits, refl, fused=True, variant=7),
-                   "two_arrays_strips": lambda: ops.ms_deform_attn_variant(value, shapes, off, logits, refl, fused=True, variant=6)}
+                   "two_arrays": lambda: ops.ms_deform_attn_variant(value, shapes, off, logits, refl, fused=True, variant=4)}
             rounds = {k: [] for k in fns}
             for _ in range(5):
                 for k_, fn in fns.items():
@@ -101,15 +98,6 @@ def main():
             for k_ in fns:
                 ts = sorted(rounds[k_])
                 res[f"k1_fused_{k_}"] = dict(min_us=ts[0], med_us=ts[len(ts) // 2], GBps=nbytes / ts[len(ts) // 2] / 1e3)
-        if "k1o" in only:  # tile work order of the streaming kernel: 2-wide strips (4) against raster (6), interleaved rounds
-            fns = {v: (lambda v=v: ops.ms_deform_attn_variant(value, shapes, off, logits, refl, fused=True, variant=v, margin=4)) for v in (4, 6)}  # 4 raster, 6 strips
-            rounds = {v: [] for v in fns}
-            for _ in range(5):
-                for v, fn in fns.items():
-                    rounds[v].append(timeit(fn, a.iters)["med_us"])
-            for v in fns:
-                ts = sorted(rounds[v])
-                res[f"k1_fused_variant{v}_rounds"] = dict(min_us=ts[0], med_us=ts[len(ts) // 2], GBps=nbytes / ts[len(ts) // 2] / 1e3)
         if "k1b" in only:  # backward
             vv, ll, ww_ = value.clone().requires_grad_(), loc.clone().requires_grad_(), aw.clone().requires_grad_()
             go = torch.randn(B, S, H * D, device=dev)
@@ -120,8 +108,8 @@ def main():
             res["k1_fwd_plus_bwd"] = timeit(fb, a.iters)
             res["k1_bwd_float_atomics"] = timeit(lambda: ops.ms_deform_attn_bwd(value, shapes, loc, aw, go, deterministic=False), a.iters)
             res["k1_bwd_deterministic"] = timeit(lambda: ops.ms_deform_attn_bwd(value, shapes, loc, aw, go, deterministic=True), a.iters)
-        if any(k in only for k in ("k1t", "k1q", "k1s", "k1h")):  # one variant only, for PMC runs (LDS-window / phased quad / streaming half-head / full-head)
-            vv_ = 2 if "k1t" in only else (3 if "k1q" in only else (8 if "k1h" in only else 4))  # k1h: half-head form
+        if any(k in only for k in ("k1t", "k1s")):  # one variant only, for PMC runs (LDS-window / streaming)
+            vv_ = 2 if "k1t" in only else 4
             r = timeit(lambda: ops.ms_deform_attn_variant(value, shapes, off, logits, refl, fused=True, variant=vv_, margin=4), a.iters)
             r.update(bytes=nbytes, GBps=nbytes / r["med_us"] / 1e3)
             res[f"k1_fused_variant{vv_}_margin4"] = r

@@ -44,28 +44,6 @@ def main():
             res.setdefault(name, []).append(round(ts[len(ts) // 2], 2))
     for k, v in res.items():
         print(json.dumps({"lib": k, "k1_fused_packed_init_operands_med_us": v}))
-    if "--variants" in sys.argv:  # the LAST library's streaming-kernel variants (two-array fused form) on the same operands
-        lib = ctypes.CDLL(libs[-1])
-        f = lib.wm2f_msdeform_fwd_v
-        f.restype = ctypes.c_int
-        f.argtypes = [ctypes.c_void_p] * 5 + [ctypes.POINTER(ctypes.c_int32)] + [ctypes.c_int] * 11 + [ctypes.c_void_p]
-        offs = off.reshape(-1).to(dev).expand(B, S, -1).contiguous()
-        logits = torch.zeros(B, S, H * L * P, device=dev)
-        ys = [torch.linspace(0.5, hh - 0.5, hh) / hh for hh, ww in shapes]
-        xs = [torch.linspace(0.5, ww - 0.5, ww) / ww for hh, ww in shapes]
-        ref = torch.cat([torch.stack(torch.meshgrid(y, x, indexing="ij")[::-1], -1).reshape(-1, 2) for y, x in zip(ys, xs)]).to(dev).contiguous()
-        for variant in (4, 7, 6, 4, 7, 6, 4, 7, 6):
-            call = lambda: f(value.data_ptr(), offs.data_ptr(), logits.data_ptr(), ref.data_ptr(), out.data_ptr(), hw, B, S, S, H, D, L, P, 0, 1, variant, 4, st)
-            for _ in range(5):
-                assert call() == 0
-            torch.cuda.synchronize()
-            ts = []
-            for _ in range(iters):
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record(); call(); b.record(); torch.cuda.synchronize()
-                ts.append(a.elapsed_time(b) * 1e3)
-            ts.sort()
-            print(json.dumps({"lib": libs[-1], "variant": variant, "two_array_fused_init_operands_med_us": round(ts[len(ts) // 2], 2)}))
 
 if __name__ == "__main__":
     main()

@@ -245,11 +245,6 @@ int launch_tiled(const void* value, const void* a, const void* b, void* out, con
 
 // msdeform_quad.hip
 template <bool FUSED>
-int launch_quad(const void* value, const void* a, const void* b, void* out, const int32_t* level_hw, int B, int S, int Q,
-                int heads, int L, int P, void* stream, const char* who, bool* handled, int mode, int a_qstride,
-                int b_qstride);
-
-template <bool FUSED>
 int launch_stream(const void* value, const void* a, const void* b, void* out, const int32_t* level_hw, int B, int S,
                   int Q, int heads, int L, int P, void* stream, const char* who, bool* handled, int mode, int a_qstride,
                   int b_qstride, int lanes = 0);
@@ -279,12 +274,10 @@ static LaunchGeom geom(int B, int Q, int heads, int D) {
 // variant (production library): 0 = auto (streaming quad kernel, else LDS-window kernel, else direct gather), 1 = direct
 //          gather only, 2 = LDS-window kernel only, 4 = streaming quad kernel only -- the three kernels the library runs,
 //          selectable so that the two fall-backs can be held to the golden vectors on shapes `auto` gives to the first.
-// Profiling build only (libwm2f_prof.so, include/wm2f_prof.h) -- measured negatives, ablations, stamped builds:
-//          3 = phased quad kernel (superseded by the streaming form), 13/23/43 its ablations, 73 stamped;
+// Profiling build only (libwm2f_prof.so, include/wm2f_prof.h) -- ablations and stamped builds of these kernels:
 //          12/22/32/42/52 LDS-window ablations, 62 = LDS windows in slab-major work order;
-//          5 = streaming kernel with per-window flags instead of workgroup barriers, 6 = tiles in 2-wide vertical strips,
-//          7 = round-1 loader schedule, 8 = half-head form (two 77-KiB workgroups per CU), 44 without LDS reads,
-//          74 / 84 stamped full-head / half-head builds
+//          44 = streaming kernel without LDS reads, 74 = its stamped build.
+// Every other number is refused in both builds (the superseded kernels and measured negatives they once selected: DESIGN.md).
 template <bool FUSED>
 static int launch_fwd(const void* value, const void* a, const void* b, const void* ref, void* out,
                       const int32_t* level_hw, int B, int S, int Q, int heads, int D, int L, int P, int dtype,
@@ -295,16 +288,20 @@ static int launch_fwd(const void* value, const void* a, const void* b, const voi
   WM2F_REQUIRE(D == 8 || D == 16 || D == 32 || D == 64, "%s: head_dim %d not in {8,16,32,64}", who, D);
   LevelInfo lv;
   if (int rc = fill_levels(lv, level_hw, L, S, who)) return rc;
-#ifndef WM2F_PROFILING
-  if (variant != 0 && variant != 1 && variant != 2 && variant != 4) {
+#ifdef WM2F_PROFILING
+  const bool prof_variant = variant == 12 || variant == 22 || variant == 32 || variant == 42 || variant == 52 || variant == 62 ||
+                            variant == 44 || variant == 74;
+#else
+  const bool prof_variant = false;
+#endif
+  if (variant != 0 && variant != 1 && variant != 2 && variant != 4 && !prof_variant) {
     set_error("%s: variant %d is a superseded kernel, a timing ablation or a stamped build: profiling library only "
               "(libwm2f_prof.so, include/wm2f_prof.h)", who, variant);
     return WM2F_EUNSUPPORTED;
   }
-#endif
-  if (D == 32 && margin == 4 && (variant == 0 || variant % 10 == 4 || (variant >= 5 && variant <= 8))) {
+  if (D == 32 && margin == 4 && (variant == 0 || variant % 10 == 4)) {
     bool handled = false;
-    const int smode = variant == 5 ? 100 : variant == 6 ? 200 : variant == 7 ? 300 : variant == 8 ? 400 : variant == 84 ? 74 : variant / 10;
+    const int smode = variant / 10;  // 0 the kernel, 4 without LDS reads, 7 stamped
     if (int rc = launch_stream<FUSED>(value, a, b, out, level_hw, B, S, Q, heads, L, P, stream, who, &handled, smode, 0, 0))
       return rc;
     if (handled) return WM2F_OK;
@@ -313,17 +310,6 @@ static int launch_fwd(const void* value, const void* a, const void* b, const voi
       return WM2F_EUNSUPPORTED;
     }
   }
-#ifdef WM2F_PROFILING
-  if (D == 32 && margin == 4 && variant % 10 == 3) {
-    bool handled = false;
-    if (int rc = launch_quad<FUSED>(value, a, b, out, level_hw, B, S, Q, heads, L, P, stream, who, &handled,
-                                    variant / 10, 0, 0))
-      return rc;
-    if (handled) return WM2F_OK;
-    set_error("%s: the phased quad kernel needs D=32, P=4, Q==S and 3 levels with sides 1:2:4, coarse first", who);
-    return WM2F_EUNSUPPORTED;
-  }
-#endif
   if (variant != 1 && D == 32) {
     bool handled = false;
     if (int rc = launch_tiled<FUSED>(value, a, b, out, level_hw, B, S, Q, heads, L, P, margin,
@@ -432,7 +418,7 @@ extern "C" int wm2f_msdeform_fused_lanes_fwd(const void* value, const void* lane
     int smode = 0;
 #ifdef WM2F_PROFILING
     if (const char* e = getenv("WM2F_K1_STAMP")) smode = atoi(e) ? 7 : 0;  // profiling build: the stamped kernel on the lane-major rows
-    if (const char* e = getenv("WM2F_K1_MODE")) smode = atoi(e);          // profiling build: 200 strip order, 300 round-1 loader schedule
+    if (const char* e = getenv("WM2F_K1_MODE")) smode = atoi(e);          // profiling build: 800 slab order, 807 stamped, 814-816 / 820 its timing ablations
 #endif
     if (int rc = launch_stream<true>(value, lanes, lanes, out, level_hw, B, S, Q, heads, L, P, stream, who, &handled, smode, row,
                                      head_stride, 1 | (value_hm ? 2 : 0) | (head_major & 4)))

@@ -15,11 +15,11 @@
 //
 // [round-1 history] With fp32 LDS atomics: kernel A 0.52 ms; kernel B 10.3 ms, ALL of it in the ds_add_f32 stream
 // (ablation: without the flush 10.3 ms, without the LDS adds 0.2 ms): an LDS float atomic costs ~176
-// cycles per wave-instruction (~2.7 cycles per lane) whether or not lanes conflict -- the wave-per-query
-// form below (two contiguous 128-B rows per instruction) runs exactly as long as a scattered form did.
+// cycles per wave-instruction (~2.7 cycles per lane) whether or not lanes conflict -- a wave-per-query
+// form (two contiguous 128-B rows per instruction) ran exactly as long as a scattered form did.
 // Total 10.8 ms vs 25 ms for the global-atomic backward.
 // Now: the window accumulates in FIXED POINT with integer LDS atomics (~5 cycles per wave-instruction, measured by
-// tools/probes/lds_atomic_rate.hip; scaling and its overflow bound are at the accumulation site):
+// tools/probes/lds_atomic_rate.hip; scaling and its overflow bound are above kernel B):
 // kernel B 2.31 ms, kernel A 0.51 ms.
 #include "msdeform_tiled.h"
 #include <stdlib.h>
@@ -28,7 +28,7 @@
 namespace wm2f {
 
 constexpr int kBwdThreads = 512;
-constexpr int kQuadBwdThreads = 1024;  // the quad-form value kernel
+constexpr int kQuadBwdThreads = 1024;  // the value kernel
 
 __device__ const float4 g_zero_page_bwd[1] = {{0.f, 0.f, 0.f, 0.f}};  // LDS-DMA source for out-of-image pixels
 
@@ -399,12 +399,20 @@ __global__ __launch_bounds__(NT) void msdeform_tiled_bwd_lw_kernel(
   }
 }
 
-#ifdef WM2F_PROFILING  // superseded by the quad form below; kept as its measured baseline
+typedef __attribute__((address_space(3))) int lds_int_t;
+
 // ---------------------------------------------------------------------------------- kernel B
-// Wave-per-query.  Lanes 0..NL*P-1 each work out ONE sampling point (pixel, four weights, flags); the
-// wave then walks the points with those values as scalars (v_readlane), and every atomic instruction
-// adds two contiguous 128-B rows: lanes 0-31 = the 32 channels of the left corner, lanes 32-63 = the
-// right corner.  No redundant coordinate arithmetic, at most 2-way LDS bank conflicts.
+// grad_value through the tile's LDS windows.  The work is laid out as in the forward's quad kernels: a wave pass = 16 queries
+// x 4 lanes, each lane owning the 8 channels {4k + j}.  Coordinates, bilinear weights and window tests are computed once per
+// (query, point) by every lane of the quad in parallel for 16 queries: ~100 vector instructions per (query, head) for its
+// 24 LDS atomics (a wave per query with one lane per point needed 400: DESIGN.md 9.6b).
+//
+// Fixed-point accumulation.  An LDS float atomic costs ~190 cycles per wave-instruction on gfx950, an integer one
+// ~5 (tools/probes/lds_atomic_rate.hip), so the window holds int32 sums of round(x * scale[channel]).
+// scale = 2^31 / (512 * max|grad_out| of this tile, head and channel): a window element receives from each of the
+// tile's <= 336 queries at most sum_p attention_weight <= 1 times a bilinear weight <= 1 of that query's
+// grad_out, so |sum| <= 336 * max < 2^31 / scale -- the integer sum cannot overflow.  Each addend is rounded to
+// 2^-22 * max (the fp32 sum it replaces rounds each partial sum to 2^-24 of its own magnitude).
 //
 // DET (wm2f_msdeform_bwd_det): run-to-run identical grad_value.  The window sums are already order-independent
 // (integer LDS adds); what was not is the order in which overlapping windows (and the rare out-of-window points) reach
@@ -417,168 +425,8 @@ __global__ __launch_bounds__(NT) void msdeform_tiled_bwd_lw_kernel(
 // i.e. below 2^62 units for S < 2^17 -- no overflow, and integer addition commutes.  (All adds as 64-bit integer
 // atomics were tried first: 7.5 ms against 2.8 ms for the float atomics -- the 64-bit atomic rate; the staging form
 // moves 0.6 GB each way as plain traffic instead.)
-template <int NL, int P, bool DET>
-__global__ __launch_bounds__(kBwdThreads) void msdeform_tiled_bwd_value_kernel(
-    const float* __restrict__ loc, const float* __restrict__ attn_w, const float* __restrict__ grad_out,
-    float* __restrict__ grad_value, float* __restrict__ staging, long long* __restrict__ acc64, const int* __restrict__ emax_bits,
-    TileGeom g, int S, int Q, int heads, int n_logical, int per_xcd) {
-  constexpr int D = 32, kWaves = kBwdThreads / kWave, NP = NL * P;
-  static_assert(NP <= 64, "one lane per sampling point");
-  extern __shared__ __attribute__((aligned(16))) float4 win[];
-  const int id = xcd_contiguous_id(blockIdx.x, per_xcd);
-  if (id >= n_logical) return;
-  int* lv_tab = reinterpret_cast<int*>(win + g.lv_tab_off4);
-  const TileCtx<NL> c = tile_setup<NL>(g, id, heads, lv_tab);
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int ch = lane & 31, hs = lane >> 5;  // channel, left / right corner
-  const int row_stride = heads * D;
-  float* gvb = grad_value + ((int64_t)c.b * S * heads + c.h) * D;
-
-  for (int i = tid; i < g.lv_tab_off4; i += kBwdThreads) win[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-  // Fixed-point accumulation.  An LDS float atomic costs ~190 cycles per wave-instruction on gfx950, an integer one
-  // ~5 (tools/probes/lds_atomic_rate.hip), so the window holds int32 sums of round(x * scale[channel]).
-  // scale = 2^31 / (512 * max|grad_out| of this tile, head and channel): a window element receives from each of the
-  // tile's <= 336 queries at most sum_p attention_weight <= 1 times a bilinear weight <= 1 of that query's
-  // grad_out, so |sum| <= 336 * max < 2^31 / scale -- the integer sum cannot overflow.  Each addend is rounded to
-  // 2^-22 * max (the fp32 sum it replaces rounds each partial sum to 2^-24 of its own magnitude).
-  __shared__ float ch_max[kBwdThreads / kWave][32];
-  {
-    float m = 0.f;
-    for (int qi = wave; qi < c.nq; qi += kWaves) {
-      const int q = tile_query<NL>(lv_tab, qi, Q);
-      m = fmaxf(m, fabsf(grad_out[(((int64_t)c.b * Q + q) * heads + c.h) * D + ch]));
-    }
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    if (lane < 32) ch_max[wave][lane] = m;
-  }
-  __syncthreads();
-  float gmax = 0.f;
-#pragma unroll
-  for (int w = 0; w < kBwdThreads / kWave; ++w) gmax = fmaxf(gmax, ch_max[w][ch]);
-  const float fx_scale = gmax > 0.f ? 4194304.f / gmax : 0.f;  // 2^22 / max
-  const float fx_inv = gmax > 0.f ? gmax * (1.f / 4194304.f) : 0.f;
-  float det_unit_inv = 0.f;  // DET: 2^(44 - E), a float -> units of the spill image
-  long long* acc_b = nullptr;
-  __shared__ float ch_inv[32];
-  if (DET) {
-    int E = ((emax_bits[c.b * heads + c.h] >> 23) & 0xff) - 127;
-    if (E < -80) E = -80;
-    det_unit_inv = __int_as_float((44 - E + 127) << 23);
-    acc_b = acc64 + ((int64_t)c.b * S * heads + c.h) * D;
-    if (tid < 32) ch_inv[tid] = fx_inv;  // lane = channel for tid < 32
-  }
-  int* wini = reinterpret_cast<int*>(win);
-
-  // this lane's point (lanes >= NP idle in the per-point phase): level constants
-  const int pl = lane < NP ? lane / P : 0;
-  int Wl_p = g.w[0], Hl_p = g.h[0], ww_p = g.win_w[0], wh_p = g.win_h[0], wx0_p = c.wx0[0], wy0_p = c.wy0[0];
-  int base_p = g.lds_off4[0] * 4, start_p = g.start[0];
-#pragma unroll
-  for (int l = 1; l < NL; ++l)
-    if (pl == l) {
-      Wl_p = g.w[l]; Hl_p = g.h[l]; ww_p = g.win_w[l]; wh_p = g.win_h[l]; wx0_p = c.wx0[l]; wy0_p = c.wy0[l];
-      base_p = g.lds_off4[l] * 4; start_p = g.start[l];
-    }
-
-  for (int qi = wave; qi < c.nq; qi += kWaves) {
-    const int q = tile_query<NL>(lv_tab, qi, Q);
-    const int64_t pair = ((int64_t)c.b * Q + q) * heads + c.h;
-    const float gof = grad_out[pair * D + ch];
-    const float gofs = gof * fx_scale;
-    // ---- per-point phase (one lane per point)
-    float w00 = 0.f, w01 = 0.f, w10 = 0.f, w11 = 0.f;
-    int lds_idx = -1, glb_idx = 0, flags = 0;  // flags: bit0..3 corner in image, bit4 footprint in window
-    if (lane < NP) {
-      const float2 lc = *reinterpret_cast<const float2*>(loc + pair * (NP * 2) + lane * 2);
-      const float aw = attn_w[pair * NP + lane];
-      float x, y;
-      pixel_coords(lc.x, lc.y, Wl_p, Hl_p, x, y);
-      if (x > -1.f && x < (float)Wl_p && y > -1.f && y < (float)Hl_p) {
-        const float x0f = floorf(x), y0f = floorf(y);
-        const int x0 = (int)x0f, y0 = (int)y0f;
-        const float fx1 = x - x0f, fy1 = y - y0f;
-        const float a1 = aw * fy1, a0 = aw - a1;
-        w01 = a0 * fx1; w00 = a0 - w01; w11 = a1 * fx1; w10 = a1 - w11;
-        const bool xl = x0 >= 0, xr = x0 + 1 < Wl_p, yt = y0 >= 0, yb = y0 + 1 < Hl_p;
-        flags = (yt && xl ? 1 : 0) | (yt && xr ? 2 : 0) | (yb && xl ? 4 : 0) | (yb && xr ? 8 : 0);
-        const int xrw = x0 - wx0_p, yrw = y0 - wy0_p;
-        if ((unsigned)xrw < (unsigned)(ww_p - 1) && (unsigned)yrw < (unsigned)(wh_p - 1)) {
-          flags |= 16;
-          lds_idx = base_p + (yrw * ww_p + xrw) * 32;  // float index of the top-left corner's row
-        }
-        glb_idx = (start_p + y0 * Wl_p + x0);  // token of the top-left corner (may be out of range: flags)
-        flags |= (ww_p << 8) | (Wl_p << 16);   // row pitches for the bottom corners (ww < 256, Wl < 65536)
-      }
-    }
-    // ---- per-corner-row phase: point parameters as wave-uniform scalars
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      const int f = __builtin_amdgcn_readlane(flags, p);
-      if ((f & 15) == 0) continue;  // point outside the image (uniform branch)
-      const float s00 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, w00), p));
-      const float s01 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, w01), p));
-      const float s10 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, w10), p));
-      const float s11 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, w11), p));
-      const int li = __builtin_amdgcn_readlane(lds_idx, p), gi = __builtin_amdgcn_readlane(glb_idx, p);
-      const int wwp = (f >> 8) & 0xff, Wlp = (f >> 16) & 0xffff;
-      const float wt = hs ? s01 : s00, wb = hs ? s11 : s10;
-      const bool ok_t = (f >> hs) & 1, ok_b = (f >> (2 + hs)) & 1;
-      if (f & 16) {  // whole footprint inside the window: LDS accumulation
-        if (ok_t) atomicAdd(wini + li + hs * 32 + ch, __float2int_rn(wt * gofs));
-        if (ok_b) atomicAdd(wini + li + (wwp + hs) * 32 + ch, __float2int_rn(wb * gofs));
-      } else if (DET) {  // rare: straight to memory, in units
-        if (ok_t) atomicAdd(reinterpret_cast<unsigned long long*>(acc_b + (int64_t)(gi + hs) * row_stride + ch),
-                            (unsigned long long)__float2ll_rn(wt * gof * det_unit_inv));
-        if (ok_b) atomicAdd(reinterpret_cast<unsigned long long*>(acc_b + (int64_t)(gi + Wlp + hs) * row_stride + ch),
-                            (unsigned long long)__float2ll_rn(wb * gof * det_unit_inv));
-      } else {  // rare: straight to memory
-        if (ok_t) atomicAdd(gvb + (int64_t)(gi + hs) * row_stride + ch, wt * gof);
-        if (ok_b) atomicAdd(gvb + (int64_t)(gi + Wlp + hs) * row_stride + ch, wb * gof);
-      }
-    }
-  }
-  __syncthreads();
-  if (DET) {  // the whole window, converted, into this tile's slab (float4 i holds channels 4 (i % 8) ..)
-    float4* slab = reinterpret_cast<float4*>(staging) + (int64_t)id * g.lv_tab_off4;
-    const int4* wi4 = reinterpret_cast<const int4*>(win);
-    for (int i = tid; i < g.lv_tab_off4; i += kBwdThreads) {
-      const int4 v = wi4[i];
-      const float4 sc = *reinterpret_cast<const float4*>(ch_inv + 4 * (i & 7));
-      slab[i] = make_float4((float)v.x * sc.x, (float)v.y * sc.y, (float)v.z * sc.z, (float)v.w * sc.w);
-    }
-    return;
-  }
-  // flush: one lane per channel, 32 lanes per pixel -> every atomic wave-instruction is two whole 128-B rows
-  const int pslot = tid >> 5;
-#pragma unroll
-  for (int l = 0; l < NL; ++l) {
-    const int Wl = g.w[l], Hl = g.h[l], ww = g.win_w[l];
-    const int npix = ww * g.win_h[l];
-    const float inv_ww = 1.f / (float)ww;
-    const int* wli = wini + g.lds_off4[l] * 4;
-    float* glev = gvb + (int64_t)g.start[l] * row_stride;
-    for (int idx = pslot; idx < npix; idx += kBwdThreads / 32) {
-      const int wy = (int)(((float)idx + 0.5f) * inv_ww), wx = idx - wy * ww;
-      const int x = c.wx0[l] + wx, y = c.wy0[l] + wy;
-      if (x < 0 || x >= Wl || y < 0 || y >= Hl) continue;
-      const int vi = wli[idx * 32 + ch];
-      if (vi != 0) atomicAdd(glev + (int64_t)(y * Wl + x) * row_stride + ch, (float)vi * fx_inv);
-    }
-  }
-}
-
-#endif  // WM2F_PROFILING (wave-per-query value kernel)
-
-typedef __attribute__((address_space(3))) int lds_int_t;
-
-// ---------------------------------------------------------------------------------- kernel B, quad form
-// Same windows, fixed-point sums, flush / slab and out-of-window rule as the kernel above, but the work is laid out as in
-// the forward's quad kernels: a wave pass = 16 queries x 4 lanes, each lane owning the 8 channels {4k + j}.  Coordinates,
-// bilinear weights and window tests are then computed once per (query, point) by every lane of the quad in parallel
-// for 16 queries, instead of by 12 lanes of a wave whose other 52 wait and which then walks the 12 points serially with
-// six v_readlane each: the wave-per-query kernel issued 19.2 k vector + 10 k scalar instructions per wave (PMC: vector
-// pipe 51 % busy, the rest waits) -- 400 vector instructions per (query, head) for its 24 LDS atomics; this form needs
-// ~100.  LDS banks: at a fixed k all lanes touch dword 4k + j of their pixel row, i.e. the same 4 banks per row parity;
+//
+// LDS banks: at a fixed k all lanes touch dword 4k + j of their pixel row, i.e. the same 4 banks per row parity;
 // the row is therefore stored XOR-swizzled, channel c of window pixel r at dword c ^ 4 ((r >> 1) & 7), which spreads 16
 // neighbouring pixels over all 64 banks and costs nothing (v_xad_u32 forms (4k ^ 4s) + base in one instruction); the
 // flush and the slab store undo it.
@@ -606,7 +454,7 @@ __global__ __launch_bounds__(NT) void msdeform_tiled_bwd_value_quad_kernel(
     if (ROWS == 2) return __uint_as_float((unsigned)reinterpret_cast<const unsigned short*>(grad_out)[i] << 16);
     return grad_out[i];
   };
-  // per-channel scale of the fixed-point sums: as in the kernel above (2^22 / max |grad_out| of this tile, head, channel)
+  // per-channel scale of the fixed-point sums (2^22 / max |grad_out| of this tile, head, channel)
   __shared__ float ch_max[NT / kWave][32];
   __shared__ float ch_scale[32], ch_inv[32];
   {
@@ -881,12 +729,6 @@ int launch_tiled_bwd(const void* value, const void* loc, const void* attn_w, con
   if (n_logical > (1 << 30)) return WM2F_OK;
   const int per_xcd = (int)ceil_div64(n_logical, kNumXcd);
   hipStream_t st = (hipStream_t)stream;
-#ifdef WM2F_PROFILING
-  const char* e_old = getenv("WM2F_K1_BWD_OLD");  // profiling build: the wave-per-query value kernel, for A/B
-  const bool old_form = e_old && *e_old == '1';
-#else
-  const bool old_form = false;
-#endif
   long long* acc64 = nullptr;
   int* emax_bits = nullptr;
   float* staging = nullptr;
@@ -958,17 +800,10 @@ int launch_tiled_bwd(const void* value, const void* loc, const void* attn_w, con
     *handled = true;
     return WM2F_OK;
   }
-#ifdef WM2F_PROFILING  // the wave-per-query value kernel exists in the profiling build only (A/B: WM2F_K1_BWD_OLD=1)
-#define WM2F_TB_OLD(NLv) \
-  if (old_form) kb = det_ws ? msdeform_tiled_bwd_value_kernel<NLv, 4, true> : msdeform_tiled_bwd_value_kernel<NLv, 4, false>;
-#else
-#define WM2F_TB_OLD(NLv)
-#endif
 #define WM2F_TB(NLv)                                                                                              \
   case NLv: {                                                                                                     \
     auto ka = msdeform_tiled_bwd_lw_kernel<NLv, 4>;                                                               \
     auto kb = det_ws ? msdeform_tiled_bwd_value_quad_kernel<NLv, 4, true> : msdeform_tiled_bwd_value_quad_kernel<NLv, 4, false>; \
-    WM2F_TB_OLD(NLv)                                                                                              \
     if (p.lds_bytes > 64 * 1024) {                                                                                \
       hipError_t e1 = hipFuncSetAttribute((const void*)ka, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes); \
       hipError_t e2 = hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes); \
@@ -980,7 +815,7 @@ int launch_tiled_bwd(const void* value, const void* loc, const void* attn_w, con
     hipLaunchKernelGGL(ka, dim3(per_xcd* kNumXcd), dim3(kBwdThreads), p.lds_bytes, st, (const float*)value,       \
                        (const float*)loc, (const float*)attn_w, (const float*)grad_out, (float*)grad_loc,         \
                        (float*)grad_w, p.g, S, Q, heads, (int)n_logical, per_xcd);                                \
-    hipLaunchKernelGGL(kb, dim3(per_xcd* kNumXcd), dim3(old_form ? kBwdThreads : kQuadBwdThreads), p.lds_bytes, st, (const float*)loc, \
+    hipLaunchKernelGGL(kb, dim3(per_xcd* kNumXcd), dim3(kQuadBwdThreads), p.lds_bytes, st, (const float*)loc, \
                        (const float*)attn_w, (const float*)grad_out, (float*)grad_value, staging, acc64, emax_bits,  \
                        p.g, S, Q, heads, (int)n_logical, per_xcd);                                                \
     if (det_ws)                                                                                                   \
@@ -992,7 +827,6 @@ int launch_tiled_bwd(const void* value, const void* loc, const void* attn_w, con
     default: return WM2F_OK;
   }
 #undef WM2F_TB
-#undef WM2F_TB_OLD
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     set_error("%s: tiled backward launch failed: %s", who, hipGetErrorString(e));
