@@ -23,7 +23,10 @@
 //     own x loads of the next k-step, then computes the current one; one `s_waitcnt vmcnt(0)` + barrier per k-step;
 //   * a CU owns a contiguous range of 16-token column tiles, its waves split it as evenly as tiles allow, and a wave walks
 //     its share two column tiles (32 tokens) per turn: each A fragment read from LDS feeds 2 x 6 MFMAs (3 ds_read_b128 per
-//     12 MFMAs of 16 cycles: a quarter of the LDS array's 256 B/clk);
+//     12 MFMAs of 16 cycles: a quarter of the LDS array's 256 B/clk); a wave with an odd share has one live tile in its
+//     last turn and then runs the one tile's split and six-MFMA chains only (a wave-uniform branch), so the turn costs
+//     one tile: at the encoder's 42 tiles per CU the busiest SIMD runs 11 tile-steps, and project_kv, one tile per wave,
+//     half the MFMAs it ran before;
 //   * x is the B operand, loaded as fp32 (lane (j, g): token j, channels 8g .. 8g + 7 of the k-step) and split in
 //     registers once per element and feature slice; a wave owns ALL N features of its tokens when N <= 288, so the
 //     LayerNorm of a token is a reduction inside the wave.  N = 1024 (fc1) runs as four 256-wide slices one after the
@@ -166,7 +169,8 @@ __global__ __launch_bounds__(kSgThreads) void token_gemm_split_kernel(SgArgs a) 
     const int n_live = ct0 >= w1 ? 0 : (ct0 + 1 >= w1 ? 1 : 2);  // wave-uniform
     bf16x8 bh[CT], bm[CT], bl[CT];
 #pragma unroll
-    for (int c = 0; c < CT; ++c) split3(xr[c], bh[c], bm[c], bl[c]);
+    for (int c = 0; c < CT; ++c)
+      if (c < n_live) split3(xr[c], bh[c], bm[c], bl[c]);  // wave-uniform; a dead tile's pieces are never read
     // the next step's loads fly under this step's MFMAs -- except before a LayerNorm epilogue, where their 16 registers
     // made the epilogue spill: there they are issued after it
     const bool late = EPI == 2 && ks + 1 == n_ks;
@@ -186,8 +190,9 @@ __global__ __launch_bounds__(kSgThreads) void token_gemm_split_kernel(SgArgs a) 
       c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bm[cc], c, 0, 0, 0);
       return __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bh[cc], c, 0, 0, 0);
     };
-    // a turn with one live column tile runs the second on zeros (x loads out of range) and stores nothing of it: a
-    // separate one-tile loop beside this one made the compiler spill the accumulators
+    // a turn with one live column tile skips the second tile's split and its six-MFMA chains by a wave-uniform branch
+    // inside the one unrolled loop (a separate one-tile loop beside this one made the compiler spill the accumulators);
+    // the dead tile's accumulators stay zero and nothing of it is stored.  A live tile's MFMA sequence is the same either way
     if (n_live > 0) {
       bf16x8 av[2][3];
       read_a(av[0], 0);
@@ -196,7 +201,7 @@ __global__ __launch_bounds__(kSgThreads) void token_gemm_split_kernel(SgArgs a) 
         if (rt + 1 < NRT) read_a(av[(rt + 1) & 1], rt + 1);
         __builtin_amdgcn_sched_barrier(0);
         acc[rt][0] = six(acc[rt][0], av[rt & 1], 0);
-        acc[rt][1] = six(acc[rt][1], av[rt & 1], 1);
+        if (n_live > 1) acc[rt][1] = six(acc[rt][1], av[rt & 1], 1);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -219,6 +224,9 @@ __global__ __launch_bounds__(kSgThreads) void token_gemm_split_kernel(SgArgs a) 
             acc[rt][c] = v;
           }
           if (EPI == 2) {  // LayerNorm over the token's N features (n_sl == 1): this lane's NRT * 4 values, then the 4 lane groups
+            // this lane's 4 features of row tile 0; a row tile's 64 bytes go into the instruction's offset field (the
+            // same addresses as row_o + (rt * 16 + 4 * g) * 4 in one register per store cost 15 registers and spilled)
+            const unsigned row_g = tok_ok ? row_o + (unsigned)(16 * g) : kOob;
             constexpr int kEB = 2;  // row tiles per batch of epilogue loads (4 spilled beside the accumulators of two column tiles)
             if (a.residual) {
               const __amdgpu_buffer_rsrc_t r_rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.residual, 0, (int)(a.M * a.N * 4), 0x00020000);
@@ -227,7 +235,7 @@ __global__ __launch_bounds__(kSgThreads) void token_gemm_split_kernel(SgArgs a) 
                 f32x4 rv[kEB];
 #pragma unroll
                 for (int i = 0; i < kEB; ++i)
-                  rv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_rs, row_o + (unsigned)(((h0 + i) * 16 + 4 * g) * 4), 0, 0));
+                  rv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_rs, row_g, (h0 + i) * 64, 0));
 #pragma unroll
                 for (int i = 0; i < kEB; ++i) acc[h0 + i][c] += rv[i];
                 __builtin_amdgcn_sched_barrier(0);  // one batch of residual rows in registers at a time
@@ -257,21 +265,20 @@ __global__ __launch_bounds__(kSgThreads) void token_gemm_split_kernel(SgArgs a) 
             }
 #pragma unroll
             for (int rt = 0; rt < NRT; ++rt)
-              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[rt][c]), o_rs, row_o + (unsigned)((rt * 16 + 4 * g) * 4), 0, 0);
+              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[rt][c]), o_rs, row_g, rt * 64, 0);
             if (a.out_pos) {  // the next layer's hidden + pos
               const __amdgpu_buffer_rsrc_t p_rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.pos, 0, (int)(a.pos_rows * a.N * 4), 0x00020000);
               const __amdgpu_buffer_rsrc_t q_rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.out_pos, 0, (int)(a.M * a.N * 4), 0x00020000);
-              const unsigned prow = tok_ok ? (unsigned)((tk % a.pos_rows) * a.N * 4) : kOob;
+              const unsigned prow = tok_ok ? (unsigned)(((tk % a.pos_rows) * a.N + 4 * g) * 4) : kOob;
 #pragma unroll
               for (int h0 = 0; h0 < NRT; h0 += kEB) {
                 f32x4 pv[kEB];
 #pragma unroll
                 for (int i = 0; i < kEB; ++i)
-                  pv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(p_rs, prow + (unsigned)(((h0 + i) * 16 + 4 * g) * 4), 0, 0));
+                  pv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(p_rs, prow, (h0 + i) * 64, 0));
 #pragma unroll
                 for (int i = 0; i < kEB; ++i)
-                  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[h0 + i][c] + pv[i]), q_rs,
-                                                         row_o + (unsigned)(((h0 + i) * 16 + 4 * g) * 4), 0, 0);
+                  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[h0 + i][c] + pv[i]), q_rs, row_g, (h0 + i) * 64, 0);
               }
             }
           } else if (EPI == 1) {
