@@ -859,6 +859,56 @@ int wm2f_augment_nearest_labels(const void* maps, int dtype, int64_t n_map_elems
                                 const int32_t* tables, int64_t n_table, int32_t* out, uint8_t* present, int B, int Hp,
                                 int Wp, int ignore_index, void* stream);
 
+/* ---- colour jitter on device: brightness, contrast, saturation, hue ----------------------
+ * Four operations on uint8 RGB images, each defined by a Pillow 12.2 expression and reproduced byte for byte:
+ *   WM2F_PHOTO_BRIGHTNESS  factor f >= 0   ImageEnhance.Brightness(im).enhance(f)
+ *   WM2F_PHOTO_CONTRAST    factor f >= 0   ImageEnhance.Contrast(im).enhance(f)
+ *   WM2F_PHOTO_SATURATION  factor f >= 0   ImageEnhance.Color(im).enhance(f)
+ *   WM2F_PHOTO_HUE         dh in 0 .. 255  h, s, v = im.convert("HSV").split(); h = (h + dh) mod 256;
+ *                                          Image.merge("HSV", (h, s, v)).convert("RGB")
+ * A chain is an ordered list of at most four operations, each kind at most once, applied left to right; each operation
+ * produces a uint8 image that the next one reads.
+ * Blend.  The three enhancers are Image.blend(degenerate, image, f).  Per byte, with d the degenerate byte, v the image
+ *   byte and a = float32(f): t = fl32(fl32(d) + fl32(a * fl32(v - d))) -- the product is rounded to float32, then the
+ *   sum; NOT a fused multiply-add -- and the result is 0 if t <= 0, 255 if t >= 255, else trunc(t).  (Pillow skips the
+ *   clip for 0 <= f <= 1, where t lies in range already.)
+ * Degenerates.  L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 of a pixel.
+ *   brightness: d = 0.  saturation: d = L of the same pixel.
+ *   contrast: d = m for every byte of the image, m = int(S / (H W) + 0.5) with S the integer sum of L over the image AS IT
+ *   STANDS WHEN THE CONTRAST STEP IS REACHED (after the steps in front of it), the division and the sum in float64.
+ * RGB -> HSV.  mx, mn the largest and smallest of the three bytes; V = mx.  mx == mn: H = S = 0.  Otherwise, in float32
+ *   unless said: cr = mx - mn; s = cr / mx; rc = (mx - r) / cr, gc, bc alike; h = bc - gc if r == mx, else
+ *   2.0 + rc - bc if g == mx, else 4.0 + gc - rc, the two forms with a constant evaluated left to right in float64 and
+ *   then stored to float32; h = float32(fmod(float64(h) / 6.0 + 1.0, 1.0)) (the operand lies in [5/6, 11/6), so
+ *   x >= 1 ? x - 1 : x is exact); H = clip8(int(float64(h) * 255.0)), S = clip8(int(float64(s) * 255.0)).
+ * HSV -> RGB.  S == 0: all three bytes are V.  Otherwise hf = float64(float32(H)) * 6.0 / 255.0; i = floor(hf);
+ *   f = float32(hf - i); fs = float32(float64(S) / 255.0); p = round(V (1 - fs)), q = round(V (1 - fs f)),
+ *   t = round(V (1 - fs (1 - f))) in float64 -- except the product fs f, which is a float32 product -- with C round (half
+ *   away from zero), clipped to a byte; (R, G, B) by i mod 6 = (V, t, p), (q, V, p), (p, V, t), (p, q, V), (t, p, V),
+ *   (V, p, q).  A hue step with dh = 0 still goes through both conversions and changes pixels, as Pillow does.
+ * wm2f_photometric_u8 works IN PLACE on B packed HWC uint8 images.
+ *       desc       HOST int64 (B, WM2F_PHOTO_DESC_LEN): in_off (bytes into images), H, W, n_ops, then four (kind,
+ *                  parameter) pairs; the parameter is the bit pattern of the float32 factor (0 .. 2^32 - 1), or dh for
+ *                  WM2F_PHOTO_HUE.  Pairs from n_ops on are ignored.  An image with n_ops = 0 is left untouched.
+ *       workspace  wm2f_photometric_workspace(B) bytes (-1 for a bad B), 8-byte aligned: B int64 sums of L, cleared on
+ *                  the stream inside the call.
+ *   Two launches at most and no host synchronisation.  The sum launch runs only when some chain holds a contrast step and
+ *   its grid covers only those images: it applies the steps in front of the contrast step per pixel in registers and adds
+ *   L up as integers (wave reduction, one 64-bit atomic add per workgroup), so S does not depend on the schedule.  The
+ *   apply launch covers the images with n_ops > 0, runs the whole chain per pixel in registers, forms m in float64 and
+ *   writes the bytes back.  Images start at any byte: the pixels in front of the first 4-byte boundary that is also a
+ *   pixel boundary, and those behind the last whole group of four, go byte by byte; the body goes 12 bytes per thread.
+ * Bounds: B <= WM2F_PRE_MAX_IMAGES and sides <= WM2F_PRE_MAX_SIDE, else WM2F_EUNSUPPORTED.  WM2F_EINVAL: a repeated or
+ * unknown kind, n_ops outside 0 .. 4, a negative or non-finite factor, dh outside 0 .. 255, an image that leaves
+ * images_bytes. */
+#define WM2F_PHOTO_BRIGHTNESS 0
+#define WM2F_PHOTO_CONTRAST 1
+#define WM2F_PHOTO_SATURATION 2
+#define WM2F_PHOTO_HUE 3
+#define WM2F_PHOTO_DESC_LEN 12
+int64_t wm2f_photometric_workspace(int B);
+int wm2f_photometric_u8(uint8_t* images, int64_t images_bytes, const int64_t* desc, void* workspace, int B, void* stream);
+
 /* ---- connected components of class maps ------------------------------------------------
  * The cv2 steps of the reference's dataset loaders (datasets/pheno_bench/dataset.py:48-135, crop_weed
  * dataset_from_png_annotations.py:48-131): cv2.resize(INTER_NEAREST) of the mask, cv2.connectedComponents per class,

@@ -28,6 +28,8 @@ WM2F_RLE_MAX_IDS = 1024
 WM2F_AUG_MAX_VIRTUAL = 65536
 WM2F_TILE_MAX_SIDE, WM2F_TILE_MAX_IDS, WM2F_TILE_MAX_TILES, WM2F_TILE_MAX_PAIRS = 16384, 256, 1024, 16384
 WM2F_AUG_PRE_DESC_LEN, WM2F_AUG_LAB_DESC_LEN = 16, 12
+WM2F_PHOTO_BRIGHTNESS, WM2F_PHOTO_CONTRAST, WM2F_PHOTO_SATURATION, WM2F_PHOTO_HUE = 0, 1, 2, 3
+WM2F_PHOTO_DESC_LEN = 12
 # return codes of include/wm2f.h
 WM2F_OK, WM2F_EINVAL, WM2F_EUNSUPPORTED, WM2F_ELAUNCH = 0, -1, -2, -3
 
@@ -131,6 +133,8 @@ SIGNATURES = {
     "wm2f_resize_nearest_labels": (c_int, [_P, _I, c_int64, POINTER(c_int64), _P, c_int64, _P, _P, _I, _I, _I, _I, _P]),
     "wm2f_augment_resize_normalize_u8": (c_int, [_P, c_int64, POINTER(c_int64), _P, c_int64, _P, _P, _P, _I, _I, _I, _P]),
     "wm2f_augment_nearest_labels": (c_int, [_P, _I, c_int64, POINTER(c_int64), _P, c_int64, _P, _P, _I, _I, _I, _I, _P]),
+    "wm2f_photometric_workspace": (c_int64, [_I]),
+    "wm2f_photometric_u8": (c_int, [_P, c_int64, POINTER(c_int64), _P, _I, _P]),
     "wm2f_ccl_workspace": (c_int64, [_I, _I]),
     "wm2f_ccl_label": (c_int, [_P, _I, _I, _I, _I, _P, _P, POINTER(ctypes.c_uint8), _I, _I, _I, _P, _P, _P]),
     "wm2f_ccl_keys": (c_int, [_P, _I, _I, _I, _P, _P]),

@@ -1,4 +1,4 @@
-"""Image and label-map preprocessing, and the training augmentation."""
+"""Image and label-map preprocessing, and the training augmentation (DESIGN sections 20 and 29)."""
 from __future__ import annotations
 
 import torch
@@ -78,3 +78,21 @@ def augment_nearest_labels(maps: torch.Tensor, desc, tables: torch.Tensor, Hp: i
             d_ptr, _p(tables), tables.numel(), _p(out), _p(present), B, Hp, Wp,
             int(ignore_index))
     return out, present
+
+
+def photometric_u8(images: torch.Tensor, desc) -> torch.Tensor:
+    """Colour jitter of packed uint8 HWC images (flat, on the device) IN PLACE (wm2f_photometric_u8):
+    per image a chain of at most four of brightness, contrast, saturation and hue, byte for byte what Pillow's
+    ImageEnhance and HSV conversions give.  `desc` is a host int64 array (B, 12): in_off, H, W, n_ops, then four (kind,
+    parameter) pairs, the parameter being the float32 factor's bit pattern or the hue byte dh.  Returns `images`.  The
+    (B,) int64 workspace of the contrast sums is allocated here; nothing synchronises with the host."""
+    _on_gpu(images, "images")
+    if images.dtype != torch.uint8 or not images.is_contiguous():
+        raise TypeError(f"images: expected a contiguous uint8 tensor (it is written in place), got {images.dtype}")
+    d, d_ptr = _host_desc(desc)
+    if d.ndim != 2 or d.shape[1] != _lib.WM2F_PHOTO_DESC_LEN:
+        raise ValueError(f"desc: expected (B, {_lib.WM2F_PHOTO_DESC_LEN}), got {d.shape}")
+    B = int(d.shape[0])
+    ws = torch.empty(max(B, 1), device=images.device, dtype=torch.int64)
+    _launch("wm2f_photometric_u8", images, _p(images), images.numel(), d_ptr, _p(ws), B)
+    return images

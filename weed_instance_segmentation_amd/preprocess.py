@@ -281,8 +281,10 @@ class Mask2FormerImageProcessor(Mask2FormerInstancePostProcessor):
                    device="cuda", mask_dtype: torch.dtype = torch.float32, augment=None, **overrides) -> BatchFeature:
         """`augment`: None, one `AugmentParams` for every image or a list with one per image.  With
         parameters each image is mirrored (flip), resized to the parameters' own (h, w) -- `size` and `size_divisor` do
-        not apply -- and cut to the window; `pad_size` defaults to the batch's largest window.  The call stays
-        deterministic: the draws are `TrainAugmentation.sample`'s."""
+        not apply -- and cut to the window; `pad_size` defaults to the batch's largest window.  Parameters that carry a
+        `photometric` chain have it applied to the source image first, on the call's private device
+        copy: the caller's tensors are never written, and maps and labels do not see it.  The call stays deterministic:
+        the draws are `TrainAugmentation.sample`'s."""
         unknown = set(overrides) - set(_SETTINGS)
         if unknown:
             raise TypeError(f"unexpected keyword arguments {sorted(unknown)}")
@@ -405,6 +407,13 @@ class Mask2FormerImageProcessor(Mask2FormerInstancePostProcessor):
         desc[:, 0] = img_off[:-1]
         t_tab = buf[:tables.nbytes].view(torch.int32)
         t_lut = buf[o_lut:o_lut + lut.nbytes].view(torch.float32)
+        if augs is not None and any(a.photometric is not None and a.photometric.ops for a in augs):
+            # colour jitter: in place on the private copy, before the flip and the resize read it
+            from .augment import PhotometricParams
+            none = PhotometricParams()
+            pdesc = np.array([(a.photometric or none).desc_row(int(img_off[b]), *sizes_in[b]) for b, a in enumerate(augs)],
+                             dtype=np.int64)
+            ops.photometric_u8(buf[o_img:o_img + int(img_off[-1])], pdesc)
         if augs is None:
             pv, pm = ops.resize_normalize_u8(buf[o_img:o_img + int(img_off[-1])], desc, t_tab, t_lut, Hp, Wp)
         else:
