@@ -252,6 +252,26 @@ int wm2f_masked_xattn_bf16_bwd(const void* q, const void* k, const void* v, cons
                                const void* out, const void* lse, const void* grad_out, void* grad_q, void* grad_k,
                                void* grad_v, void* workspace, int B, int heads, int Q, int N, int D, void* stream);
 
+/* The kernel a K2 call runs (host arithmetic only, no GPU needed): the four entry points above decide with this function, so
+ * what it reports is what they launch.  dtype WM2F_F32 / WM2F_BF16 selects the fp32 or the bf16 entry points, backward != 0
+ * the backward.  mask_aligned != 0: the pointer conditions of the call hold -- fp32 forward: the mask's address is a
+ * multiple of 4 (or it is NULL); bf16: also 16-byte aligned operands; the fp32 backward ignores it.  Fills
+ *   route[0] kernel (WM2F_K2_*)            route[1] NQT, the kernel's template query tiles per workgroup
+ *   route[2] q_chunks                      route[3] n_splits (key splits)
+ *   route[4] tiles_per_split (16-key tiles; the last splits may own fewer, or none)
+ *   route[5] accumulate (1: the query chunks add grad_k / grad_v atomically)
+ * and returns WM2F_OK; a shape, head size or dtype no kernel is built for gives route[0] = WM2F_K2_UNSUPPORTED and zeros.
+ * The entry points' own argument checks (null pointers, heads or B above the grid limit of 65535) are not part of the
+ * route: a call they refuse never gets here.  NULL route: WM2F_EINVAL. */
+#define WM2F_K2_UNSUPPORTED 0
+#define WM2F_K2_FWD_GENERAL 1
+#define WM2F_K2_FWD_FULL 2
+#define WM2F_K2_BF16_FWD 3
+#define WM2F_K2_BWD_GENERAL 4
+#define WM2F_K2_BWD_FULL 5
+#define WM2F_K2_BF16_BWD 6
+int wm2f_masked_xattn_route(int B, int heads, int Q, int N, int D, int dtype, int backward, int mask_aligned, int* route);
+
 /* ---- Swin backbone: shifted-window attention, inference forward ---------------------------------
  * One launch per Swin layer for pad + roll + window partition + q k^T * D^-1/2 + relative-position bias + shift mask +
  * softmax + p v + window reverse + roll back + crop (transformers modeling_swin.py:401-468, :486-505, :553-626).

@@ -30,6 +30,9 @@ WM2F_TILE_MAX_SIDE, WM2F_TILE_MAX_IDS, WM2F_TILE_MAX_TILES, WM2F_TILE_MAX_PAIRS 
 WM2F_AUG_PRE_DESC_LEN, WM2F_AUG_LAB_DESC_LEN = 16, 12
 WM2F_PHOTO_BRIGHTNESS, WM2F_PHOTO_CONTRAST, WM2F_PHOTO_SATURATION, WM2F_PHOTO_HUE = 0, 1, 2, 3
 WM2F_PHOTO_DESC_LEN = 12
+# route[0] of wm2f_masked_xattn_route
+(WM2F_K2_UNSUPPORTED, WM2F_K2_FWD_GENERAL, WM2F_K2_FWD_FULL, WM2F_K2_BF16_FWD, WM2F_K2_BWD_GENERAL, WM2F_K2_BWD_FULL,
+ WM2F_K2_BF16_BWD) = range(7)
 # return codes of include/wm2f.h
 WM2F_OK, WM2F_EINVAL, WM2F_EUNSUPPORTED, WM2F_ELAUNCH = 0, -1, -2, -3
 
@@ -78,6 +81,7 @@ SIGNATURES = {
     "wm2f_attn_mask_build": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_masked_xattn_workspace": (c_int64, [_I, _I, _I, _I, _I]),
     "wm2f_masked_xattn_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "wm2f_masked_xattn_route": (c_int, [_I, _I, _I, _I, _I, _I, _I, _I, _HOST_I32]),
     "wm2f_masked_xattn_bf16_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "wm2f_masked_xattn_bf16_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "wm2f_masked_xattn_bwd_workspace": (c_int64, [_I, _I, _I, _I, _I]),

@@ -55,6 +55,49 @@ static inline int xattn_splits(int B, int heads, int N, bool fwd = true) {
   return s;
 }
 
+// The ONE place that decides which kernel a K2 call runs and on what grid.  The four launchers and
+// wm2f_masked_xattn_route (include/wm2f.h) read it; nothing else restates the rule.  `aligned`: the pointer conditions of
+// the call hold (fp32 forward: dword-aligned mask; bf16: also 16-byte aligned operands; the fp32 backward has none).
+struct K2Route {
+  int kernel = WM2F_K2_UNSUPPORTED, nqt = 0, q_chunks = 0, n_splits = 0, tps = 0, accumulate = 0;
+};
+
+static inline K2Route k2_route(int B, int heads, int Q, int N, int D, int dtype, bool backward, bool aligned) {
+  K2Route r;
+  const bool bf16 = dtype == WM2F_BF16;
+  if (B <= 0 || heads <= 0 || Q <= 0 || N <= 0 || (dtype != WM2F_F32 && !bf16)) return r;
+  if (bf16 ? D != 32 : (D != 16 && D != 32 && D != 64)) return r;
+  const int n_tiles = ceil_div(N, 16), q_tiles = ceil_div(Q, 16);
+  // whole key tiles and 32-bit byte offsets: what every full-tile kernel (buffer addressing) needs
+  const bool whole = (N % 16) == 0 && (int64_t)N * heads * D * (bf16 ? 2 : 4) < (int64_t(1) << 31) && (int64_t)Q * N < (int64_t(1) << 31);
+  if (bf16 && (!whole || !aligned || (backward && Q > 112))) return r;  // the bf16 kernels have the full-tile form only
+  r.n_splits = xattn_splits(B, heads, N, !backward);
+  r.tps = ceil_div(n_tiles, r.n_splits);
+  if (!backward) {
+    // query row tiles per workgroup: 2 at D = 64 (register budget), else up to 7 (see xattn_splits)
+    const int cap = (D == 64) ? 2 : (bf16 ? 7 : tune_env("WM2F_K2_QTILES", 7));
+    const int nqt = ceil_div(q_tiles, ceil_div(q_tiles, cap));
+    r.nqt = nqt <= 1 ? 1 : nqt <= 2 ? 2 : nqt <= 4 ? 4 : 7;  // D = 64: nqt <= 2
+    r.q_chunks = ceil_div(Q, r.nqt * 16);
+    // full-tile kernel: every key tile whole, 32-bit byte offsets, dword-aligned mask rows
+    r.kernel = bf16 ? WM2F_K2_BF16_FWD
+                    : (whole && aligned && tune_env("WM2F_K2_FULL", 1) != 0) ? WM2F_K2_FWD_FULL : WM2F_K2_FWD_GENERAL;
+    return r;
+  }
+  r.nqt = D == 64 ? 3 : (q_tiles <= 4 ? 4 : 7);
+  r.q_chunks = ceil_div(Q, r.nqt * 16);  // bf16: 1 (Q <= 112)
+  if (bf16) {
+    r.kernel = WM2F_K2_BF16_BWD;
+    return r;
+  }
+  // full-tile backward: each workgroup stages its 112 query rows once: with 4 tiles per split (N = 1024) that costs more
+  // than it saves (237 against 189 us), so 8 tiles per split at least; the general kernel takes every other shape
+  const bool full = D == 32 && whole && r.q_chunks == 1 && r.tps >= 8 && tune_env("WM2F_K2_BWD_FULL", 1) != 0;
+  r.kernel = full ? WM2F_K2_BWD_FULL : WM2F_K2_BWD_GENERAL;
+  r.accumulate = r.q_chunks > 1 ? 1 : 0;  // dK / dV are sums over the query chunks: the chunks add atomically
+  return r;
+}
+
 // Epilogue of the key-split kernels: the 4 waves' partial (O, m, l) of a workgroup meet in LDS, are combined and go to the
 // workspace as ONE partial per (image, head, query, split).  `m_scale` converts the running max to natural-log units
 // (1 for the general kernel, ln 2 for the log2-domain one; p and l are the same numbers in either base).
@@ -872,6 +915,14 @@ extern "C" int64_t wm2f_masked_xattn_workspace(int B, int heads, int Q, int N, i
   return (int64_t)B * heads * Q * xattn_splits(B, heads, N) * (D + 4) * 4;
 }
 
+extern "C" int wm2f_masked_xattn_route(int B, int heads, int Q, int N, int D, int dtype, int backward, int mask_aligned,
+                                       int* route) {
+  WM2F_REQUIRE(route != nullptr, "wm2f_masked_xattn_route: null pointer");
+  const K2Route r = k2_route(B, heads, Q, N, D, dtype, backward != 0, mask_aligned != 0);
+  route[0] = r.kernel; route[1] = r.nqt; route[2] = r.q_chunks; route[3] = r.n_splits; route[4] = r.tps; route[5] = r.accumulate;
+  return WM2F_OK;
+}
+
 extern "C" int wm2f_masked_xattn_fwd(const void* q, const void* k, const void* v, const void* mask,
                                      const void* row_open, void* out, void* lse, void* workspace, int B, int heads,
                                      int Q, int N, int D, int dtype, void* stream) {
@@ -881,22 +932,14 @@ extern "C" int wm2f_masked_xattn_fwd(const void* q, const void* k, const void* v
   WM2F_REQUIRE(B > 0 && heads > 0 && Q > 0 && N > 0, "%s: non-positive size", who);
   WM2F_REQUIRE(D == 16 || D == 32 || D == 64, "%s: head_dim %d not in {16,32,64}", who, D);
   WM2F_REQUIRE(heads <= 65535 && B <= 65535, "%s: heads / B exceed the grid limits", who);
-  const int n_splits = xattn_splits(B, heads, N);
-  const int n_tiles = ceil_div(N, 16);
-  const int tps = ceil_div(n_tiles, n_splits);
-  // query row tiles per workgroup: 2 (see xattn_splits; D = 64: at most 3 by register budget)
-  const int cap = (D == 64) ? 2 : tune_env("WM2F_K2_QTILES", 7);
-  const int q_tiles = ceil_div(Q, 16);
-  const int q_chunks = ceil_div(q_tiles, cap);
-  int nqt = ceil_div(q_tiles, q_chunks);
+  const K2Route rt = k2_route(B, heads, Q, N, D, dtype, false, (reinterpret_cast<uintptr_t>(mask) & 3) == 0);
+  const int n_splits = rt.n_splits, tps = rt.tps, nqt = rt.nqt;
+  const bool full = rt.kernel == WM2F_K2_FWD_FULL;
   hipStream_t st = (hipStream_t)stream;
   dim3 block(kXWaves * kWave);
-  // full-tile kernel: every key tile whole, 32-bit byte offsets, dword-aligned mask rows
-  const bool full = (N % 16) == 0 && (int64_t)N * heads * D * 4 < (int64_t(1) << 31) && (int64_t)Q * N < (int64_t(1) << 31) &&
-                    (reinterpret_cast<uintptr_t>(mask) & 3) == 0 && tune_env("WM2F_K2_FULL", 1) != 0;
 #define WM2F_XL(NQTv, Dv)                                                                                      \
   {                                                                                                            \
-    dim3 grid(n_splits* ceil_div(Q, NQTv * 16), heads, B);                                                     \
+    dim3 grid(n_splits* rt.q_chunks, heads, B);                                                                \
     if (full)                                                                                                  \
       hipLaunchKernelGGL((masked_xattn_fwd_full_kernel<NQTv, Dv>), grid, block, 0, st, (const float*)q,        \
                          (const float*)k, (const float*)v, (const uint8_t*)mask, (const int*)row_open,         \
@@ -907,9 +950,9 @@ extern "C" int wm2f_masked_xattn_fwd(const void* q, const void* k, const void* v
                          (float*)workspace, Q, N, heads, n_splits, tps);                                       \
   }
 #define WM2F_XD(Dv)                                  \
-  if (nqt <= 1) WM2F_XL(1, Dv)                       \
-  else if (nqt <= 2) WM2F_XL(2, Dv)                  \
-  else if (nqt <= 4) WM2F_XL(4, Dv)                  \
+  if (nqt == 1) WM2F_XL(1, Dv)                       \
+  else if (nqt == 2) WM2F_XL(2, Dv)                  \
+  else if (nqt == 4) WM2F_XL(4, Dv)                  \
   else WM2F_XL(7, Dv)
   // query-split kernel: a workgroup covers kXWaves * NQT * 16 queries
 #define WM2F_XQ(NQTv, Dv)                                                                                      \
@@ -923,7 +966,7 @@ extern "C" int wm2f_masked_xattn_fwd(const void* q, const void* k, const void* v
   // the L2 re-read was not the limit, the serial MFMA -> softmax -> MFMA chain inside a wave is.  Kept selectable.
   const bool qsplit = D <= 32 && tune_env("WM2F_K2_QSPLIT", 0) != 0;
   if (qsplit) {
-    const int per_wave = ceil_div(q_tiles, kXWaves);  // query tiles a wave needs to cover Q with one workgroup
+    const int per_wave = ceil_div(ceil_div(Q, 16), kXWaves);  // query tiles a wave needs to cover Q with one workgroup
     if (D == 16) {
       if (per_wave <= 1) WM2F_XQ(1, 16) else WM2F_XQ(2, 16)
     } else {
@@ -933,10 +976,8 @@ extern "C" int wm2f_masked_xattn_fwd(const void* q, const void* k, const void* v
     WM2F_XD(16)
   } else if (D == 32) {
     WM2F_XD(32)
-  } else {
-    if (nqt <= 1) WM2F_XL(1, 64)
-    else if (nqt <= 2) WM2F_XL(2, 64)
-    else WM2F_XL(3, 64)
+  } else {  // D = 64: at most 2 query tiles per workgroup
+    if (nqt == 1) WM2F_XL(1, 64) else WM2F_XL(2, 64)
   }
 #undef WM2F_XQ
 #undef WM2F_XD
@@ -965,28 +1006,24 @@ extern "C" int wm2f_masked_xattn_bf16_fwd(const void* q, const void* k, const vo
   WM2F_REQUIRE(q && k && v && out && workspace, "%s: null pointer", who);
   WM2F_REQUIRE(B > 0 && heads > 0 && Q > 0 && N > 0, "%s: non-positive size", who);
   WM2F_REQUIRE(heads <= 65535 && B <= 65535, "%s: heads / B exceed the grid limits", who);
-  if (D != 32 || (N % 16) != 0 || (int64_t)N * heads * D * 2 >= (int64_t(1) << 31) || (int64_t)Q * N >= (int64_t(1) << 31) ||
-      (reinterpret_cast<uintptr_t>(mask) & 3) != 0 || ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) |
-                                                        reinterpret_cast<uintptr_t>(v)) & 15) != 0) {
+  const bool aligned = (reinterpret_cast<uintptr_t>(mask) & 3) == 0 &&
+                       ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+  const K2Route rt = k2_route(B, heads, Q, N, D, WM2F_BF16, false, aligned);
+  if (rt.kernel != WM2F_K2_BF16_FWD) {
     set_error("%s: needs head_dim 32, N %% 16 == 0, 16-byte aligned operands and 32-bit offsets (cast to fp32 and use "
               "wm2f_masked_xattn_fwd)", who);
     return WM2F_EUNSUPPORTED;
   }
-  const int n_splits = xattn_splits(B, heads, N);
-  const int n_tiles = N / 16;
-  const int tps = ceil_div(n_tiles, n_splits);
-  const int q_tiles = ceil_div(Q, 16);
-  const int q_chunks = ceil_div(q_tiles, 7);
-  const int nqt = ceil_div(q_tiles, q_chunks);
+  const int n_splits = rt.n_splits, tps = rt.tps, nqt = rt.nqt;
   hipStream_t st = (hipStream_t)stream;
   dim3 block(kXWaves * kWave);
 #define WM2F_XB(NQTv)                                                                                                  \
-  hipLaunchKernelGGL((masked_xattn_bf16_fwd_full_kernel<NQTv>), dim3(n_splits* ceil_div(Q, NQTv * 16), heads, B), block, 0, \
+  hipLaunchKernelGGL((masked_xattn_bf16_fwd_full_kernel<NQTv>), dim3(n_splits* rt.q_chunks, heads, B), block, 0,             \
                      st, (const uint16_t*)q, (const uint16_t*)k, (const uint16_t*)v, (const uint8_t*)mask,              \
                      (const int*)row_open, (float*)workspace, Q, N, heads, n_splits, tps)
-  if (nqt <= 1) WM2F_XB(1);
-  else if (nqt <= 2) WM2F_XB(2);
-  else if (nqt <= 4) WM2F_XB(4);
+  if (nqt == 1) WM2F_XB(1);
+  else if (nqt == 2) WM2F_XB(2);
+  else if (nqt == 4) WM2F_XB(4);
   else WM2F_XB(7);
 #undef WM2F_XB
   WM2F_CHECK_LAUNCH(who);
@@ -1642,8 +1679,8 @@ extern "C" int wm2f_masked_xattn_bwd(const void* q, const void* k, const void* v
   WM2F_REQUIRE(B > 0 && heads > 0 && Q > 0 && N > 0, "%s: non-positive size", who);
   WM2F_REQUIRE(D == 16 || D == 32 || D == 64, "%s: head_dim %d not in {16,32,64}", who, D);
   WM2F_REQUIRE(heads <= 65535 && B <= 65535, "%s: heads / B exceed the grid limits", who);
-  const int n_splits = xattn_splits(B, heads, N, false);
-  const int tps = ceil_div(ceil_div(N, 16), n_splits);
+  const K2Route rt = k2_route(B, heads, Q, N, D, dtype, true, true);
+  const int n_splits = rt.n_splits, tps = rt.tps, q_chunks = rt.q_chunks;
   hipStream_t st = (hipStream_t)stream;
   float* dq_ws = (float*)workspace;
   float* delta = dq_ws + (int64_t)B * heads * Q * n_splits * D;
@@ -1652,8 +1689,7 @@ extern "C" int wm2f_masked_xattn_bwd(const void* q, const void* k, const void* v
   {                                                                                                                \
     hipLaunchKernelGGL((xattn_delta_kernel<Dv>), dim3((unsigned)ceil_div64(nrow, 256)), dim3(256), 0, st,          \
                        (const float*)out, (const float*)grad_out, delta, B, heads, Q);                             \
-    const int q_chunks = ceil_div(Q, NQTv * 16);                                                                   \
-    if (q_chunks > 1) { /* dK / dV are sums over the query chunks: zero them, the chunks add atomically */         \
+    if (rt.accumulate) { /* dK / dV are sums over the query chunks: zero them, the chunks add atomically */         \
       const size_t kv_bytes = (size_t)B * N * heads * Dv * 4;                                                       \
       if (hipMemsetAsync(grad_k, 0, kv_bytes, st) != hipSuccess || hipMemsetAsync(grad_v, 0, kv_bytes, st) != hipSuccess) { \
         set_error("%s: hipMemsetAsync failed", who);                                                               \
@@ -1661,7 +1697,7 @@ extern "C" int wm2f_masked_xattn_bwd(const void* q, const void* k, const void* v
       }                                                                                                            \
     }                                                                                                              \
     dim3 grid(n_splits* q_chunks, heads, B);                                                                       \
-    if (full_bwd && Dv == 32 && q_chunks == 1)                                                                     \
+    if (rt.kernel == WM2F_K2_BWD_FULL && Dv == 32)                                                                 \
       hipLaunchKernelGGL((masked_xattn_bwd_full_kernel<NQTv>), dim3(n_splits, heads, B), dim3(kXWaves* kWave), 0, st, \
                          (const float*)q, (const float*)k, (const float*)v, (const uint8_t*)mask, (const int*)row_open, \
                          (const float*)lse, (const float*)delta, (const float*)grad_out, dq_ws, (float*)grad_k,    \
@@ -1670,19 +1706,14 @@ extern "C" int wm2f_masked_xattn_bwd(const void* q, const void* k, const void* v
     hipLaunchKernelGGL((masked_xattn_bwd_kernel<NQTv, Dv>), grid, dim3(kXWaves* kWave), 0, st, (const float*)q,    \
                        (const float*)k, (const float*)v, (const uint8_t*)mask, (const int*)row_open,               \
                        (const float*)lse, (const float*)delta, (const float*)grad_out, dq_ws, (float*)grad_k,      \
-                       (float*)grad_v, Q, N, heads, n_splits, tps, q_chunks > 1 ? 1 : 0);                          \
+                       (float*)grad_v, Q, N, heads, n_splits, tps, rt.accumulate);                                 \
     hipLaunchKernelGGL((xattn_dq_reduce_kernel<Dv>), dim3((unsigned)ceil_div64(nrow*(Dv / 4), 256)), dim3(256), 0, \
                        st, (const float*)dq_ws, (float*)grad_q, B, heads, Q, n_splits);                            \
   }
-  const int q_tiles = ceil_div(Q, 16);
-  // full-tile backward: whole key tiles, 32-bit byte offsets (the general kernel takes every other shape)
-  const bool full_bwd = D == 32 && (N % 16) == 0 && (int64_t)N * heads * D * 4 < (int64_t(1) << 31) && (int64_t)Q * N < (int64_t(1) << 31) &&
-                        tps >= 8 &&  // each workgroup stages its 112 query rows once: with 4 tiles per split (N = 1024) that costs more than it saves (237 against 189 us)
-                        tune_env("WM2F_K2_BWD_FULL", 1) != 0;
   if (D == 16) {
-    if (q_tiles <= 4) WM2F_BD(16, 4) else WM2F_BD(16, 7)
+    if (rt.nqt == 4) WM2F_BD(16, 4) else WM2F_BD(16, 7)
   } else if (D == 32) {
-    if (q_tiles <= 4) WM2F_BD(32, 4) else WM2F_BD(32, 7)
+    if (rt.nqt == 4) WM2F_BD(32, 4) else WM2F_BD(32, 7)
   } else {
     WM2F_BD(64, 3)
   }
@@ -1699,15 +1730,15 @@ extern "C" int wm2f_masked_xattn_bf16_bwd(const void* q, const void* k, const vo
   WM2F_REQUIRE(q && k && v && out && lse && grad_out && grad_q && grad_k && grad_v && workspace, "%s: null pointer", who);
   WM2F_REQUIRE(B > 0 && heads > 0 && Q > 0 && N > 0, "%s: non-positive size", who);
   WM2F_REQUIRE(heads <= 65535 && B <= 65535, "%s: heads / B exceed the grid limits", who);
-  if (D != 32 || (N % 16) != 0 || Q > 112 || (int64_t)N * heads * D * 2 >= (int64_t(1) << 31) || (int64_t)Q * N >= (int64_t(1) << 31) ||
-      ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
-        reinterpret_cast<uintptr_t>(grad_k) | reinterpret_cast<uintptr_t>(grad_v) | reinterpret_cast<uintptr_t>(grad_out)) & 15) != 0) {
+  const bool aligned = ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
+                         reinterpret_cast<uintptr_t>(grad_k) | reinterpret_cast<uintptr_t>(grad_v) | reinterpret_cast<uintptr_t>(grad_out)) & 15) == 0;
+  const K2Route rt = k2_route(B, heads, Q, N, D, WM2F_BF16, true, aligned);
+  if (rt.kernel != WM2F_K2_BF16_BWD) {
     set_error("%s: needs head_dim 32, N %% 16 == 0, Q <= 112, 16-byte aligned operands and 32-bit offsets (cast to fp32 and use "
               "wm2f_masked_xattn_bwd)", who);
     return WM2F_EUNSUPPORTED;
   }
-  const int n_splits = xattn_splits(B, heads, N, false);
-  const int tps = ceil_div(N / 16, n_splits);
+  const int n_splits = rt.n_splits, tps = rt.tps;
   hipStream_t st = (hipStream_t)stream;
   float* dq_ws = (float*)workspace;
   float* delta = dq_ws + (int64_t)B * heads * Q * n_splits * D;
@@ -1719,7 +1750,7 @@ extern "C" int wm2f_masked_xattn_bf16_bwd(const void* q, const void* k, const vo
                      (const uint16_t*)q, (const uint16_t*)k, (const uint16_t*)v, (const uint8_t*)mask, (const int*)row_open, \
                      (const float*)lse, (const float*)delta, (const float*)grad_out, dq_ws, (uint16_t*)grad_k,              \
                      (uint16_t*)grad_v, Q, N, heads, n_splits, tps)
-  if (ceil_div(Q, 16) <= 4) WM2F_BB(4);
+  if (rt.nqt == 4) WM2F_BB(4);
   else WM2F_BB(7);
 #undef WM2F_BB
   WM2F_CHECK_LAUNCH(who);
