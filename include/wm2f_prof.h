@@ -20,6 +20,11 @@
  *     computed)   (tools/probes/k1_rows_bench.py)
  *   - K2 / K3 read their experiment knobs from the environment on every launch
  *       WM2F_K2_QTILES, WM2F_K2_WG_TARGET, WM2F_K2_FULL, WM2F_K2_QSPLIT, WM2F_K3_DBG   (tools/kbench.py)
+ *   - wm2f_token_linear_split_fwd reads on every launch   (tools/kbench.py --prof --only tgs)
+ *       WM2F_TGS_ABL  timing ablations of the shipped kernel, whose OUTPUTS ARE NOT VALID: 1 no epilogue stores, 2 no
+ *                     epilogue loads (residual and pos read as zero), 4 no MFMAs; any other value is refused
+ *       WM2F_TGS_OPT  0: the LayerNorm epilogue with its residual / pos loads one batch at a time, as before section 13.2
+ *                     (valid outputs, the same bits as the shipped kernel); 1 or unset: the shipped kernel
  *   - the stamp buffer below: a __device__ global, i.e. the global mutable state the production library forbids.
  */
 #ifndef WM2F_PROF_H

@@ -192,6 +192,47 @@ def main():
                 r = timeit(lambda: F.linear(x, w, bb), a.iters)
             r.update(TFLOPs=flop / r["med_us"] / 1e6)
             res[f"library_{name}"] = r
+    if "tgs" in only:  # split-bf16 token kernel: the shipped kernel, its timing ablations and the serial
+        # LayerNorm epilogue, at the five encoder sites and the three project_kv token counts; interleaved rounds in
+        # one process.  With --prof (WM2F_TGS_ABL / WM2F_TGS_OPT are read by libwm2f_prof.so on every launch); without it,
+        # e.g. with --lib <the parent's library>, the loaded library's kernel alone, as "shipped_<directory of --lib>".
+        Mtok = B * S
+        sites = [("value_proj", Mtok, 256, 256, {}), ("offsets_logits", Mtok, 256, 288, dict(out_group=36)),
+                 ("output_proj+ln", Mtok, 256, 256, dict(ln=True)), ("fc1+relu", Mtok, 256, 1024, dict(relu=True)),
+                 ("fc2+ln+pos", Mtok, 1024, 256, dict(ln=True, pos=True))]
+        sites += [(f"project_kv_{B * h * w}", B * h * w, 256, 256, {}) for h, w in shapes]
+        variants = [("shipped", {}), ("no_epilogue_stores_INVALID", {"WM2F_TGS_ABL": "1"}),
+                    ("no_epilogue_loads_INVALID", {"WM2F_TGS_ABL": "2"}), ("no_mfma_INVALID", {"WM2F_TGS_ABL": "4"})]
+        # the LayerNorm sites also with the serial epilogue loads of before §13.2 (WM2F_TGS_OPT=0)
+        variants += [("serial_ln_loads", {"WM2F_TGS_OPT": "0"})]
+        if not a.prof:
+            variants = [("shipped" + ("_" + os.path.basename(os.path.dirname(os.path.abspath(a.lib))) if a.lib else ""), {})]
+        for name, M_, K, N, kw in sites:
+            x = torch.randn(M_, K, device=dev)
+            w = torch.randn(N, K, device=dev) * 0.05
+            ws = ops.split_weight(w)
+            bb = torch.randn(N, device=dev)
+            ln = (torch.randn(N, device=dev), torch.randn(N, device=dev), 1e-5) if kw.get("ln") else None
+            res_ = torch.randn(M_, N, device=dev) if ln else None
+            pe = torch.randn(S, N, device=dev) if kw.get("pos") else None
+            fn = lambda: ops.token_linear(x, w, bb, relu=bool(kw.get("relu")), residual=res_, ln=ln, pos=pe,  # noqa: E731
+                                          out_group=kw.get("out_group", 0), w_split=ws)
+            todo = variants
+            if not ln:  # no epilogue loads to ablate or to pipeline
+                todo = [(v, e) for v, e in todo if v not in ("no_epilogue_loads_INVALID", "serial_ln_loads")]
+            rounds = {v: [] for v, _ in todo}
+            for _ in range(5):
+                for v, env in todo:
+                    for k_ in ("WM2F_TGS_ABL", "WM2F_TGS_OPT"):
+                        os.environ.pop(k_, None)
+                    os.environ.update(env)
+                    rounds[v].append(timeit(fn, a.iters)["med_us"])
+            for k_ in ("WM2F_TGS_ABL", "WM2F_TGS_OPT"):
+                os.environ.pop(k_, None)
+            for v, _ in todo:
+                ts = sorted(rounds[v])
+                res[f"tgs_{name}_{v}"] = dict(M=M_, K=K, N=N, med_us=ts[len(ts) // 2], min_us=ts[0], spread_us=ts[-1] - ts[0],
+                                              rounds_us=[round(t, 2) for t in rounds[v]])
     if "k3m" in only:  # K3 with the fused attention-mask epilogue at the three level resolutions (the inference route)
         emb = torch.randn(B, Q, 256, device=dev)
         for hw in shapes:

@@ -20,7 +20,8 @@
 //     contiguous bytes, lane-linear, and one k-step's panel of a feature slice is contiguous;
 //   * one persistent workgroup per CU, 8 waves (2 per SIMD, 256 registers each), no loader wave: every wave issues its
 //     share of the NEXT k-step's panel by LDS-DMA (1 KiB pieces) into the other half of a two-panel ring, together with its
-//     own x loads of the next k-step, then computes the current one; one `s_waitcnt vmcnt(0)` + barrier per k-step;
+//     own x loads of the next k-step, then computes the current one; one `s_waitcnt vmcnt(0)` + barrier per k-step, and
+//     no other wait for vector memory between a k-step's LDS-DMA issue and its first MFMA (sg_wait_vm below);
 //   * a CU owns a contiguous range of 16-token column tiles, its waves split it as evenly as tiles allow, and a wave walks
 //     its share two column tiles (32 tokens) per turn: each A fragment read from LDS feeds 2 x 6 MFMAs (3 ds_read_b128 per
 //     12 MFMAs of 16 cycles: a quarter of the LDS array's 256 B/clk); a wave with an odd share has one live tile in its
@@ -31,7 +32,13 @@
 //     registers once per element and feature slice; a wave owns ALL N features of its tokens when N <= 288, so the
 //     LayerNorm of a token is a reduction inside the wave.  N = 1024 (fc1) runs as four 256-wide slices one after the
 //     other on the same tokens, so the slices' x re-reads hit the caches, not HBM.
-// Roofline: bf16 MFMA, 6 x 2 M N K flop against 2.5 PFLOP/s; HBM: x once, out once (+ residual, + pos).
+//   * the LayerNorm epilogue keeps two batches of residual rows, then of pos rows, in flight (in the registers the x loads
+//     of the next step, issued behind it, leave free), so its waits for memory overlap instead of following one another.
+// Roofline: bf16 MFMA, 6 x 2 M N K flop against 2.5 PFLOP/s; HBM: x once, out once (+ residual, + pos).  Measured
+// (timing ablations of the profiling build): no site is MFMA-bound -- without its MFMAs a launch is 8-15 %
+// faster, without its epilogue stores 13-26 %; a k-step waits on its memory path (x, the panel every CU re-reads per
+// k-step and turn), and the epilogue's stores and loads come on top.  Keeping the bias epilogues' stores in flight across
+// the barrier, and walking odd workgroups half a turn out of phase, were built and measured there and are not kept.
 #include "common.h"
 
 namespace wm2f {
@@ -92,16 +99,31 @@ struct SgArgs {
   int tiles_total;  // ceil(M / 16)
 };
 
+// The k-step's wait for this wave's vector memory: s_waitcnt vmcnt(0), expcnt and lgkmcnt left at their maxima.  It is
+// the builtin, not inline asm: the compiler's own wait insertion then knows the counter is drained and adds no wait of
+// its own between a k-step's LDS-DMA issue and its first MFMA (it did, vmcnt(3) / vmcnt(1) in front of the x loads, when
+// the wait was hidden in asm: in hardware those waited for the LDS-DMA pieces just issued).
+__device__ __forceinline__ void sg_wait_vm() {
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+}
+
 __device__ __forceinline__ void sg_barrier() {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  sg_wait_vm();
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
 }
 
+// The LayerNorm epilogue's loads, template parameter PIPE: residual batches double-buffered, and the pos
+// batch of a row-tile pair loaded before the stores of the pair before it.  The product library is compiled with
+// PIPE = true alone; the profiling build also carries the serial epilogue (WM2F_TGS_OPT=0) and the timing ablations ABL
+// (WM2F_TGS_ABL: 1 no epilogue stores, 2 no epilogue loads, 4 no MFMAs -- OUTPUTS NOT VALID), include/wm2f_prof.h.
+constexpr int kAblStores = 1, kAblLoads = 2, kAblMfma = 4;
+
 // NRT = row tiles of one feature slice (16: N = 256 and the 256-wide slices of N = 1024; 18: N = 288).
 // EPI = the epilogue, fixed at compile time (one LayerNorm epilogue inside the k-step loop beside the others spilled):
 // 0 = bias (+ ReLU) row-major, 1 = bias (+ ReLU) feature-group major, 2 = bias + residual + LayerNorm (+ pos)
-template <int NRT, int EPI>
+template <int NRT, int EPI, bool PIPE = true, int ABL = 0>
 __global__ __launch_bounds__(kSgThreads) void token_gemm_split_kernel(SgArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [2][NRT][3][64][16 B], then bias | gamma | beta
   constexpr int kPanelBytes = NRT * 3 * kFrag;
@@ -182,7 +204,13 @@ __global__ __launch_bounds__(kSgThreads) void token_gemm_split_kernel(SgArgs a) 
       for (int p = 0; p < 3; ++p) dst[p] = *reinterpret_cast<const bf16x8*>(panel + (rt * 3 + p) * kFrag + lane * 16);
     };
     // the six products of one (row tile, column tile); the small terms first
-    auto six = [&](f32x4 c, const bf16x8 (&av)[3], int cc) {
+    auto six = [&](f32x4 c, const bf16x8 (&av)[3], int cc) -> f32x4 {
+      if (ABL & kAblMfma) {  // timing ablation: three multiply-adds keep the LDS reads and the split alive
+        c[0] += __builtin_bit_cast(f32x4, av[0])[0] * __builtin_bit_cast(f32x4, bl[cc])[0];
+        c[1] += __builtin_bit_cast(f32x4, av[1])[1] * __builtin_bit_cast(f32x4, bm[cc])[1];
+        c[2] += __builtin_bit_cast(f32x4, av[2])[2] * __builtin_bit_cast(f32x4, bh[cc])[2];
+        return c;
+      }
       c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1], bm[cc], c, 0, 0, 0);
       c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[2], bh[cc], c, 0, 0, 0);
       c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bl[cc], c, 0, 0, 0);
@@ -217,6 +245,8 @@ __global__ __launch_bounds__(kSgThreads) void token_gemm_split_kernel(SgArgs a) 
           const int64_t tk = (int64_t)(ct0 + c) * 16 + j;
           const bool tok_ok = tk < a.M;
           const unsigned row_o = tok_ok ? (unsigned)((tk * a.N + n0) * 4) : kOob;
+          // timing ablation "no epilogue stores": a condition that is never true at run time keeps the values alive
+          const bool st = !(ABL & kAblStores) || a.tiles_total < 0;
 #pragma unroll
           for (int rt = 0; rt < NRT; ++rt) {
             f32x4 v = acc[rt][c] + *reinterpret_cast<const f32x4*>(vec + n0 + rt * 16 + 4 * g);
@@ -228,17 +258,37 @@ __global__ __launch_bounds__(kSgThreads) void token_gemm_split_kernel(SgArgs a) 
             // same addresses as row_o + (rt * 16 + 4 * g) * 4 in one register per store cost 15 registers and spilled)
             const unsigned row_g = tok_ok ? row_o + (unsigned)(16 * g) : kOob;
             constexpr int kEB = 2;  // row tiles per batch of epilogue loads (4 spilled beside the accumulators of two column tiles)
-            if (a.residual) {
+            if (a.residual && !(ABL & kAblLoads)) {
               const __amdgpu_buffer_rsrc_t r_rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.residual, 0, (int)(a.M * a.N * 4), 0x00020000);
-#pragma unroll
-              for (int h0 = 0; h0 < NRT; h0 += kEB) {
-                f32x4 rv[kEB];
+              if (PIPE) {
+                // two batches in the registers the late-issued x loads leave free: batch b + 1 flies while b is added
+                f32x4 rv[2][kEB];
 #pragma unroll
                 for (int i = 0; i < kEB; ++i)
-                  rv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_rs, row_g, (h0 + i) * 64, 0));
+                  rv[0][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_rs, row_g, i * 64, 0));
 #pragma unroll
-                for (int i = 0; i < kEB; ++i) acc[h0 + i][c] += rv[i];
-                __builtin_amdgcn_sched_barrier(0);  // one batch of residual rows in registers at a time
+                for (int h0 = 0; h0 < NRT; h0 += kEB) {
+                  const int b = (h0 / kEB) & 1;
+                  if (h0 + kEB < NRT) {
+#pragma unroll
+                    for (int i = 0; i < kEB; ++i)
+                      rv[b ^ 1][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_rs, row_g, (h0 + kEB + i) * 64, 0));
+                  }
+#pragma unroll
+                  for (int i = 0; i < kEB; ++i) acc[h0 + i][c] += rv[b][i];
+                  __builtin_amdgcn_sched_barrier(0);
+                }
+              } else {
+#pragma unroll
+                for (int h0 = 0; h0 < NRT; h0 += kEB) {
+                  f32x4 rv[kEB];
+#pragma unroll
+                  for (int i = 0; i < kEB; ++i)
+                    rv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_rs, row_g, (h0 + i) * 64, 0));
+#pragma unroll
+                  for (int i = 0; i < kEB; ++i) acc[h0 + i][c] += rv[i];
+                  __builtin_amdgcn_sched_barrier(0);  // one batch of residual rows in registers at a time
+                }
               }
             }
             float s1 = 0.f, s2 = 0.f;
@@ -263,24 +313,59 @@ __global__ __launch_bounds__(kSgThreads) void token_gemm_split_kernel(SgArgs a) 
               const f32x4 gm = *reinterpret_cast<const f32x4*>(vec + a.N + f0), bt = *reinterpret_cast<const f32x4*>(vec + 2 * a.N + f0);
               acc[rt][c] = (acc[rt][c] - mean) * rstd * gm + bt;
             }
+            const bool pipe_pos = PIPE && a.out_pos;  // then `out` is stored pair by pair between the pos loads
+            if (st && !pipe_pos) {
 #pragma unroll
-            for (int rt = 0; rt < NRT; ++rt)
-              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[rt][c]), o_rs, row_g, rt * 64, 0);
+              for (int rt = 0; rt < NRT; ++rt)
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[rt][c]), o_rs, row_g, rt * 64, 0);
+            }
             if (a.out_pos) {  // the next layer's hidden + pos
               const __amdgpu_buffer_rsrc_t p_rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.pos, 0, (int)(a.pos_rows * a.N * 4), 0x00020000);
               const __amdgpu_buffer_rsrc_t q_rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.out_pos, 0, (int)(a.M * a.N * 4), 0x00020000);
               const unsigned prow = tok_ok ? (unsigned)(((tk % a.pos_rows) * a.N + 4 * g) * 4) : kOob;
-#pragma unroll
-              for (int h0 = 0; h0 < NRT; h0 += kEB) {
-                f32x4 pv[kEB];
+              const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+              if (PIPE) {
+                // the pos rows of pair h0 + 2 are loaded before the stores of pair h0: the wait for a pos batch then
+                // covers the stores of the pair before, issued a whole batch earlier, never the ones just issued
+                f32x4 pv[2][kEB];
 #pragma unroll
                 for (int i = 0; i < kEB; ++i)
-                  pv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(p_rs, prow, (h0 + i) * 64, 0));
+                  pv[0][i] = (ABL & kAblLoads) ? zero4 : __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(p_rs, prow, i * 64, 0));
 #pragma unroll
-                for (int i = 0; i < kEB; ++i)
-                  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[h0 + i][c] + pv[i]), q_rs, row_g, (h0 + i) * 64, 0);
+                for (int h0 = 0; h0 < NRT; h0 += kEB) {
+                  const int b = (h0 / kEB) & 1;
+                  if (h0 + kEB < NRT) {
+#pragma unroll
+                    for (int i = 0; i < kEB; ++i)
+                      pv[b ^ 1][i] = (ABL & kAblLoads) ? zero4 : __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(p_rs, prow, (h0 + kEB + i) * 64, 0));
+                  }
+                  if (st) {
+#pragma unroll
+                    for (int i = 0; i < kEB; ++i)
+                      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[h0 + i][c]), o_rs, row_g, (h0 + i) * 64, 0);
+#pragma unroll
+                    for (int i = 0; i < kEB; ++i)
+                      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, (ABL & kAblLoads) ? acc[h0 + i][c] : acc[h0 + i][c] + pv[b][i]), q_rs, row_g, (h0 + i) * 64, 0);
+                  }
+                  __builtin_amdgcn_sched_barrier(0);
+                }
+              } else {
+#pragma unroll
+                for (int h0 = 0; h0 < NRT; h0 += kEB) {
+                  f32x4 pv[kEB];
+#pragma unroll
+                  for (int i = 0; i < kEB; ++i)
+                    pv[i] = (ABL & kAblLoads) ? zero4 : __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(p_rs, prow, (h0 + i) * 64, 0));
+                  if (st) {
+#pragma unroll
+                    for (int i = 0; i < kEB; ++i)
+                      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, (ABL & kAblLoads) ? acc[h0 + i][c] : acc[h0 + i][c] + pv[i]), q_rs, row_g, (h0 + i) * 64, 0);
+                  }
+                }
               }
             }
+          } else if (!st) {
+            // timing ablation: nothing is stored
           } else if (EPI == 1) {
             // feature-group-major output (N / G, M, G); a lane's 4 consecutive features stay inside one group (G % 4 == 0)
             const unsigned G = (unsigned)a.out_group;
@@ -305,6 +390,15 @@ __global__ __launch_bounds__(kSgThreads) void token_gemm_split_kernel(SgArgs a) 
     if (q + 1 < n_q && late) issue(q + 1);
     sg_barrier();  // step q + 1's panel and x have landed; every wave is done with slot q & 1
   }
+}
+
+using sg_kernel_t = void (*)(SgArgs);
+
+// the instance of (N == 288, epilogue); PIPE applies to the LayerNorm epilogue alone
+template <bool PIPE, int ABL>
+sg_kernel_t sg_pick(bool n288, int epi) {
+  if (n288) return epi == 2 ? token_gemm_split_kernel<18, 2, PIPE, ABL> : (epi == 1 ? token_gemm_split_kernel<18, 1, true, ABL> : token_gemm_split_kernel<18, 0, true, ABL>);
+  return epi == 2 ? token_gemm_split_kernel<16, 2, PIPE, ABL> : (epi == 1 ? token_gemm_split_kernel<16, 1, true, ABL> : token_gemm_split_kernel<16, 0, true, ABL>);
 }
 
 int device_cu_count(int* n_cu) {
@@ -383,9 +477,25 @@ extern "C" int wm2f_token_linear_split_fwd(const void* x, const void* w_split, c
   const int nrt = N == 288 ? 18 : 16;
   const size_t lds = (size_t)2 * nrt * 3 * kFrag + (size_t)3 * N * sizeof(float);
   const int epi = ln_gamma ? 2 : (out_group > 0 ? 1 : 0);
-  void (*kfn)(SgArgs) = nullptr;
-  if (N == 288) kfn = epi == 2 ? token_gemm_split_kernel<18, 2> : (epi == 1 ? token_gemm_split_kernel<18, 1> : token_gemm_split_kernel<18, 0>);
-  else kfn = epi == 2 ? token_gemm_split_kernel<16, 2> : (epi == 1 ? token_gemm_split_kernel<16, 1> : token_gemm_split_kernel<16, 0>);
+  sg_kernel_t kfn = sg_pick<true, 0>(N == 288, epi);
+#ifdef WM2F_PROFILING
+  {  // WM2F_TGS_OPT = 0: the LayerNorm epilogue with its loads one batch at a time, as before §13.2 (valid outputs, the
+     // same bits); WM2F_TGS_ABL = 1 / 2 / 4: the shipped kernel without epilogue stores / epilogue loads / MFMAs
+     // (OUTPUTS NOT VALID)
+    const char* eo = getenv("WM2F_TGS_OPT");
+    const char* ea = getenv("WM2F_TGS_ABL");
+    const int abl = ea ? atoi(ea) : 0;
+    if (abl != 0) {
+      WM2F_REQUIRE(abl == 1 || abl == 2 || abl == 4, "%s: WM2F_TGS_ABL = %d is not built (1, 2, 4 are)", who, abl);
+      WM2F_REQUIRE(!eo, "%s: WM2F_TGS_ABL ablates the shipped kernel only (unset WM2F_TGS_OPT)", who);
+      kfn = abl == 1 ? sg_pick<true, 1>(N == 288, epi) : (abl == 2 ? sg_pick<true, 2>(N == 288, epi) : sg_pick<true, 4>(N == 288, epi));
+    } else if (eo) {
+      const int opt = atoi(eo);
+      WM2F_REQUIRE(opt == 0 || opt == 1, "%s: WM2F_TGS_OPT = %d is not built (0 and 1 are)", who, opt);
+      if (opt == 0) kfn = sg_pick<false, 0>(N == 288, epi);
+    }
+  }
+#endif
   hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) {
     set_error("%s: cannot raise dynamic LDS to %zu: %s", who, lds, hipGetErrorString(e));
