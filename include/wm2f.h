@@ -929,6 +929,55 @@ int wm2f_augment_nearest_labels(const void* maps, int dtype, int64_t n_map_elems
 int64_t wm2f_photometric_workspace(int B);
 int wm2f_photometric_u8(uint8_t* images, int64_t images_bytes, const int64_t* desc, void* workspace, int B, void* stream);
 
+/* ---- orientation on device: vertical flip, quarter turns, rotation ------------------------
+ * Per image, with im the stored RGB image (or id map) of size (H, W), the output is byte for byte what Pillow 12.2 makes
+ * of these steps, each taken only when enabled, in this order:
+ *   1. vflip = 1:      im.transpose(FLIP_TOP_BOTTOM): row y is stored row H - 1 - y.
+ *   2. turns = 1, 2, 3: im.transpose(ROTATE_90 / ROTATE_180 / ROTATE_270), counter-clockwise.  With (H, W) the size in
+ *      front of the turn: 1: out[y][x] = in[x][W - 1 - y]; 2: out[y][x] = in[H - 1 - y][W - 1 - x];
+ *      3: out[y][x] = in[H - 1 - x][y].  Turns 1 and 3 make the frame (W, H).
+ *   3. affine = 1:     image  im.rotate(angle, resample=BILINEAR, expand=False, fillcolor=fill),
+ *                      map    im.rotate(angle, resample=NEAREST, expand=False, fillcolor=fill).
+ *      The frame keeps its size.  Below, (H, W) is the size of the turned frame the rotation reads.
+ * Matrix.  Computed on the host in Python floats exactly as Image.rotate does: a = -radians(angle % 360.0);
+ *   m = [round(cos a, 15), round(sin a, 15), 0, round(-sin a, 15), round(cos a, 15), 0]; with cx = W / 2.0, cy = H / 2.0:
+ *   m2 = m0 (-cx) + m1 (-cy), m5 = m3 (-cx) + m4 (-cy), then m2 += cx, m5 += cy.  The six float64 values travel as bit
+ *   patterns.  Pillow routes angle % 360 of 0 and 180, and of 90 and 270 on a square image, to transpose: the host folds
+ *   those into `turns` and leaves affine = 0.
+ * Image, bilinear.  All arithmetic is float64, every product rounded before its sum (nothing fused).  For output pixel
+ *   (x, y): xi = x + 0.5, yi = y + 0.5; xin = m0 xi + m1 yi + m2, yin = m3 xi + m4 yi + m5 (left to right).  The pixel is
+ *   `fill` when xin < 0, xin >= W, yin < 0 or yin >= H.  Otherwise xin -= 0.5, yin -= 0.5; X = floor(xin), Y = floor(yin);
+ *   dx = xin - X, dy = yin - Y.  Columns X and X + 1 are clamped to [0, W - 1], row Y to [0, H - 1].  Per channel, with a, b
+ *   the bytes at the two columns: v1 = a + (b - a) dx on row Y; v2 the same on row Y + 1 when 0 <= Y + 1 < H, else
+ *   v2 = v1; v = v1 + (v2 - v1) dy; the byte is v truncated.
+ * Map, nearest.  Pillow's 16.16 fixed point, FIX(v) = floor(v 65536.0 + 0.5) as host integers: a0, a1, a3, a4 = FIX(m0),
+ *   FIX(m1), FIX(m3), FIX(m4); a2 = FIX(m2 + m0 0.5 + m1 0.5), a5 = FIX(m5 + m3 0.5 + m4 0.5).  Source column
+ *   (a2 + a1 y + a0 x) >> 16 and row (a5 + a4 y + a3 x) >> 16 (arithmetic shift, 64-bit in the kernel; with sides
+ *   <= 16384 the values stay inside int32, so Pillow's 32-bit accumulators never wrap); `fill` when either index is
+ *   outside the frame.
+ * wm2f_orient_u8: packed HWC uint8 images, out of place; offsets and buffer sizes in bytes.
+ * wm2f_orient_labels_u8 / _i32: id maps, one templated kernel; offsets and buffer sizes in elements.
+ *       desc   HOST int64 (B, WM2F_ORIENT_DESC_LEN): in_off, H, W (the stored size), out_off, vflip, turns, affine, the six
+ *              float64 bit patterns m0 .. m5, the six fixed-point integers a0 .. a5, then the fill: three bytes r, g, b
+ *              (images) or the id and two ignored entries (maps).  The output of an image holds H W pixels, as a
+ *              (W, H) frame when turns is odd.  An image with nothing enabled is copied.
+ *   One launch for the whole batch, no workspace and no host synchronisation.  A workgroup owns a 64 x 64 output tile and
+ *   builds it in LDS: flips and turns read the tile's footprint in contiguous runs and transpose it in LDS; the rotation
+ *   computes the coordinates once per pixel and takes the three channels from the same four taps, with the flip and the
+ *   turn folded into the tap address.  Rows go out as contiguous runs.  Runs are moved as aligned dwords and, at their two
+ *   ends, byte by byte; no byte outside an image is read or written.
+ * Bounds: B <= WM2F_PRE_MAX_IMAGES and sides <= WM2F_PRE_MAX_SIDE, else WM2F_EUNSUPPORTED.  WM2F_EINVAL: an image that
+ * leaves the input or the output buffer, overlapping outputs, overlapping src and dst, vflip or affine outside {0, 1},
+ * turns outside 0 .. 3, with affine = 1 a non-finite matrix entry (images) or a fixed-point term outside int32 (maps), a
+ * fill byte outside 0 .. 255 or a fill id that does not fit the map's type. */
+#define WM2F_ORIENT_DESC_LEN 22
+int wm2f_orient_u8(const uint8_t* src, int64_t src_bytes, uint8_t* dst, int64_t dst_bytes, const int64_t* desc, int B,
+                   void* stream);
+int wm2f_orient_labels_u8(const uint8_t* src, int64_t src_elems, uint8_t* dst, int64_t dst_elems, const int64_t* desc,
+                          int B, void* stream);
+int wm2f_orient_labels_i32(const int32_t* src, int64_t src_elems, int32_t* dst, int64_t dst_elems, const int64_t* desc,
+                           int B, void* stream);
+
 /* ---- connected components of class maps ------------------------------------------------
  * The cv2 steps of the reference's dataset loaders (datasets/pheno_bench/dataset.py:48-135, crop_weed
  * dataset_from_png_annotations.py:48-131): cv2.resize(INTER_NEAREST) of the mask, cv2.connectedComponents per class,

@@ -1,6 +1,6 @@
-"""Training augmentation (DESIGN.md sections 20 and 29): random horizontal flip, random scale, fixed-size crop or
-short-edge choice, and colour jitter (brightness, contrast, saturation, hue).  Not in the reference, which trains on one
-deterministic resize per image.
+"""Training augmentation (DESIGN.md sections 20, 29 and 30): random horizontal flip, random scale, fixed-size crop or
+short-edge choice, colour jitter (brightness, contrast, saturation, hue) and orientation (vertical flip, quarter turns,
+rotation by any angle).  Not in the reference, which trains on one deterministic resize per image.
 
     from weed_instance_segmentation_amd import TrainAugmentation, AugmentParams
 
@@ -13,10 +13,15 @@ deterministic resize per image.
                             hue=0.05)                                             # the same, with colour jitter
     out = adjust_colors(image, PhotometricParams((("brightness", 1.2), ("hue", -0.03))))   # outside the processor
 
+    aug = TrainAugmentation(scale=(0.1, 2.0), crop_size=(1024, 1024), vflip_prob=0.5, quarter_turns=True, rotate=15,
+                            fill=(124, 116, 104), map_fill=255)                   # top-down imagery: any orientation
+    out = rotate_images(image, RotateParams(vflip=True, turns=1, angle=13.37))    # outside the processor
+
 `AugmentParams` are explicit and public, so an augmentation can be replayed.  The processor stays deterministic; every
 random draw happens in `TrainAugmentation.sample`, from the caller's CPU `torch.Generator`.  The pixels are produced by
 csrc/augment.hip, bit for bit what Pillow makes of the flipped, resized, cropped image, and the colours by
-csrc/photometric.hip, bit for bit what Pillow's `ImageEnhance` and HSV conversions make of the source image.
+csrc/photometric.hip, bit for bit what Pillow's `ImageEnhance` and HSV conversions make of the source image, and the
+orientation by csrc/orient.hip, bit for bit what Pillow's `transpose` and `rotate` make of image and id map.
 """
 from __future__ import annotations
 
@@ -28,7 +33,8 @@ import torch
 
 from . import _lib
 
-__all__ = ["AugmentParams", "PhotometricParams", "TrainAugmentation", "adjust_colors"]
+__all__ = ["AugmentParams", "PhotometricParams", "RotateParams", "TrainAugmentation", "adjust_colors", "rotate_images",
+           "rotate_maps"]
 
 PHOTOMETRIC_KINDS = ("brightness", "contrast", "saturation", "hue")  # index = the WM2F_PHOTO_* constant
 _FLOAT32_MAX = 3.4028234663852886e38
@@ -47,6 +53,102 @@ def _pair(v, name: str):
 
 def _float32_bits(v: float) -> int:
     return struct.unpack("<I", struct.pack("<f", v))[0]
+
+
+def _float64_bits(v: float) -> int:
+    return struct.unpack("<q", struct.pack("<d", v))[0]
+
+
+def _fix(v: float) -> int:
+    """Pillow's FIX: floor(v * 65536.0 + 0.5), as a Python integer."""
+    return math.floor(v * 65536.0 + 0.5)
+
+
+def _is_int(v) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+@dataclass(frozen=True)
+class RotateParams:
+    """One image's orientation, applied to the source image and its id map in this order, each step
+    only when enabled: `vflip` (Pillow's FLIP_TOP_BOTTOM), `turns` in 0 .. 3 counter-clockwise quarter turns (ROTATE_90,
+    ROTATE_180, ROTATE_270; 1 and 3 swap the frame of a non-square image to (W, H)), then `angle` in degrees when
+    angle % 360 != 0: `rotate(angle, BILINEAR, expand=False, fillcolor=fill)` for the image and
+    `rotate(angle, NEAREST, expand=False, fillcolor=map_fill)` for the map, counter-clockwise, the frame keeping its
+    size.  `fill` is three bytes, `map_fill` a raw id (the processor writes it before `do_reduce_labels`)."""
+    vflip: bool = False
+    turns: int = 0
+    angle: float = 0.0
+    fill: tuple = (0, 0, 0)
+    map_fill: int = 0
+
+    def __post_init__(self):
+        if not (isinstance(self.vflip, bool) or (_is_int(self.vflip) and self.vflip in (0, 1))):
+            raise ValueError(f"vflip must be a bool, got {self.vflip!r}")
+        if not _is_int(self.turns) or not 0 <= self.turns <= 3:
+            raise ValueError(f"turns must be an integer in 0 .. 3, got {self.turns!r}")
+        if isinstance(self.angle, bool) or not isinstance(self.angle, (int, float)) or not math.isfinite(self.angle):
+            raise ValueError(f"angle must be a finite number of degrees, got {self.angle!r}")
+        try:
+            fill = tuple(self.fill)
+        except TypeError:
+            fill = ()
+        if len(fill) != 3 or not all(_is_int(c) and 0 <= c <= 255 for c in fill):
+            raise ValueError(f"fill must be three bytes (r, g, b), got {self.fill!r}")
+        if not _is_int(self.map_fill) or not -2 ** 31 <= self.map_fill < 2 ** 31:
+            raise ValueError(f"map_fill must be an int32 id, got {self.map_fill!r}")
+        object.__setattr__(self, "vflip", bool(self.vflip))
+        object.__setattr__(self, "angle", float(self.angle))
+        object.__setattr__(self, "fill", fill)
+
+    @property
+    def enabled(self) -> bool:
+        """Whether any of the three steps changes the image."""
+        return self.vflip or self.turns != 0 or self.angle % 360.0 != 0
+
+    def out_size(self, height: int, width: int) -> tuple:
+        """The (H, W) of the oriented frame of a stored (height, width) image: swapped by an odd number of turns."""
+        return (int(width), int(height)) if self.turns & 1 else (int(height), int(width))
+
+    def matrix(self, height: int, width: int) -> list:
+        """The six float64 entries `Image.rotate` hands to the affine transform for a (height, width) frame -- the frame
+        the rotation reads, that is the TURNED frame -- computed in Python floats exactly as Pillow does."""
+        a = -math.radians(self.angle % 360.0)
+        m = [round(math.cos(a), 15), round(math.sin(a), 15), 0.0, round(-math.sin(a), 15), round(math.cos(a), 15), 0.0]
+        cx, cy = width / 2.0, height / 2.0
+        m[2], m[5] = m[0] * -cx + m[1] * -cy + m[2], m[3] * -cx + m[4] * -cy + m[5]
+        m[2] += cx
+        m[5] += cy
+        return m
+
+    def fixed(self, height: int, width: int) -> list:
+        """Pillow's 16.16 terms a0 .. a5 of the nearest-neighbour transform for the same frame, as Python integers."""
+        m = self.matrix(height, width)
+        return [_fix(m[0]), _fix(m[1]), _fix(m[2] + m[0] * 0.5 + m[1] * 0.5),
+                _fix(m[3]), _fix(m[4]), _fix(m[5] + m[3] * 0.5 + m[4] * 0.5)]
+
+    def folded(self, height: int, width: int) -> tuple:
+        """(turns, affine) as the kernels take them for a stored (height, width) image.  Pillow routes angle % 360 of 0 and
+        180, and of 90 and 270 on a square frame, to `transpose`; those are folded into the turn and `affine` is False."""
+        h, w = self.out_size(height, width)
+        a = self.angle % 360.0
+        if a == 0:
+            return self.turns, False
+        if a == 180:
+            return (self.turns + 2) % 4, False
+        if a in (90, 270) and h == w:
+            return (self.turns + (1 if a == 90 else 3)) % 4, False
+        return self.turns, True
+
+    def desc_row(self, in_off: int, height: int, width: int, out_off: int, labels: bool = False) -> list:
+        """The image's row of wm2f_orient_u8's host descriptor, or with labels=True of wm2f_orient_labels_*'s
+        (include/wm2f.h); (height, width) is the stored size."""
+        turns, affine = self.folded(height, width)
+        h, w = self.out_size(height, width)
+        m, fx = (self.matrix(h, w), self.fixed(h, w)) if affine else ([0.0] * 6, [0] * 6)
+        fill = [self.map_fill, 0, 0] if labels else list(self.fill)
+        return [int(in_off), int(height), int(width), int(out_off), int(self.vflip), turns, int(affine),
+                *[_float64_bits(v) for v in m], *fx, *fill]
 
 
 @dataclass(frozen=True)
@@ -112,14 +214,19 @@ class AugmentParams:
     """One image's augmentation: `flip` (0 or 1, a horizontal mirror of the source, applied before the resize), `size` =
     (h, w) of the resized frame, `origin` = (y0, x0) and `window` = (ch, cw) of the crop inside that frame.  The window
     must lie inside the frame: y0 + ch <= h and x0 + cw <= w.  `photometric`, a `PhotometricParams` or None, is the colour
-    chain applied to the source image before the flip and the resize."""
+    chain applied to the source image before the flip and the resize.  `rotate`, a `RotateParams` or None, is the
+    orientation (vertical flip, quarter turns, rotation) applied after the colour chain and before the flip and the
+    resize; `size`, `origin` and `window` then refer to the turned frame."""
     flip: int
     size: tuple
     origin: tuple = (0, 0)
     window: tuple | None = None
     photometric: PhotometricParams | None = None
+    rotate: RotateParams | None = None
 
     def __post_init__(self):
+        if self.rotate is not None and not isinstance(self.rotate, RotateParams):
+            raise ValueError(f"rotate must be a RotateParams or None, got {self.rotate!r}")
         if self.photometric is not None and not isinstance(self.photometric, PhotometricParams):
             raise ValueError(f"photometric must be a PhotometricParams or None, got {self.photometric!r}")
         if self.flip not in (0, 1, False, True):
@@ -166,10 +273,20 @@ class TrainAugmentation:
     `torch.randperm(4)` for the order of the chain and then one float64 uniform each for brightness, contrast, saturation
     and hue, in that order of names and always all four, whether or not the kind is switched on.  Kinds left None are
     dropped from the chain; the others appear in the permutation's order (entry k of the permutation names the k-th of
-    brightness, contrast, saturation, hue).  So a seed gives the same geometry with and without colour jitter."""
+    brightness, contrast, saturation, hue).  So a seed gives the same geometry with and without colour jitter.
+
+    Orientation: `vflip_prob` (the probability of a vertical flip), `quarter_turns` (True: a uniform
+    number of counter-clockwise quarter turns in 0 .. 3) and `rotate` (None, a number d for an angle uniform in [-d, d]
+    degrees, or a (lo, hi) pair); `fill` and `map_fill` are what the rotation writes where it reads outside the image and
+    the id map.  With all three off `sample` takes no new draw and returns `rotate=None`.  With any of them on it takes
+    three draws BEFORE all the others, always all three and in this order: one float32 uniform (vertical flip when it is
+    below `vflip_prob`), one randint(4) (the turns), one float64 uniform (the angle); draws of options that are off are
+    discarded.  They come first because the turned frame is the (H, W) that decides (h, w) and the ranges of y0 and x0: a
+    recipe with orientation on therefore gives a seed ANOTHER geometry than the same recipe without."""
 
     def __init__(self, short_edge=None, max_size: int = 1333, scale=None, crop_size=None, flip_prob: float = 0.5,
-                 size_divisor: int = 32, brightness=None, contrast=None, saturation=None, hue=None):
+                 size_divisor: int = 32, brightness=None, contrast=None, saturation=None, hue=None,
+                 vflip_prob: float = 0.0, quarter_turns: bool = False, rotate=None, fill=(0, 0, 0), map_fill: int = 0):
         if (short_edge is None) == (scale is None):
             raise ValueError("give exactly one of short_edge=(...) and scale=(lo, hi)")
         if not 0.0 <= float(flip_prob) <= 1.0:
@@ -199,6 +316,38 @@ class TrainAugmentation:
             self.scale, self.crop_size = (lo, hi), (Ch, Cw)
         self.color_ranges = tuple(self._color_range(name, v) for name, v in
                                   zip(PHOTOMETRIC_KINDS, (brightness, contrast, saturation, hue)))
+        if not 0.0 <= float(vflip_prob) <= 1.0:
+            raise ValueError(f"vflip_prob must lie in [0, 1], got {vflip_prob}")
+        if not isinstance(quarter_turns, bool):
+            raise ValueError(f"quarter_turns must be a bool, got {quarter_turns!r}")
+        self.vflip_prob, self.quarter_turns = float(vflip_prob), quarter_turns
+        self.rotate_range = self._angle_range(rotate)
+        self._orient_base = RotateParams(fill=fill, map_fill=map_fill)  # validates the two fills
+        self.fill, self.map_fill = self._orient_base.fill, map_fill
+
+    @staticmethod
+    def _angle_range(v):
+        """None, or the (lo, hi) range of the angle in degrees."""
+        if v is None:
+            return None
+        try:
+            if isinstance(v, (int, float)) and not isinstance(v, bool):
+                d = float(v)
+                if not d >= 0.0:
+                    raise ValueError
+                lo, hi = -d, d
+            else:
+                lo, hi = (float(x) for x in v)
+        except (TypeError, ValueError):
+            raise ValueError(f"rotate: expected None, a number >= 0 or a (lo, hi) pair of degrees, got {v!r}") from None
+        if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
+            raise ValueError(f"rotate: the range {(lo, hi)} must be finite with lo <= hi")
+        return lo, hi
+
+    @property
+    def orients(self) -> bool:
+        """Whether any of vertical flip, quarter turns and rotation is switched on."""
+        return self.vflip_prob > 0.0 or self.quarter_turns or self.rotate_range is not None
 
     @staticmethod
     def _color_range(name: str, v):
@@ -233,6 +382,17 @@ class TrainAugmentation:
             raise ValueError(f"image size must be positive, got {(height, width)}")
         if generator is not None and generator.device.type != "cpu":
             raise ValueError("generator must be a CPU torch.Generator")
+        rotate = None
+        if self.orients:
+            u_flip = float(torch.rand(1, generator=generator).item())
+            k = int(torch.randint(4, (1,), generator=generator).item())
+            u_angle = float(torch.rand(1, dtype=torch.float64, generator=generator).item())
+            angle = 0.0
+            if self.rotate_range is not None:
+                lo, hi = self.rotate_range
+                angle = min(lo + (hi - lo) * u_angle, hi)
+            rotate = RotateParams(u_flip < self.vflip_prob, k if self.quarter_turns else 0, angle, self.fill, self.map_fill)
+            H, W = rotate.out_size(H, W)  # everything below sees the turned frame
         flip = int(torch.rand(1, generator=generator).item() < self.flip_prob)
         if self.short_edge is not None:
             from .preprocess import output_size
@@ -257,7 +417,7 @@ class TrainAugmentation:
                 (PHOTOMETRIC_KINDS[k], min(self.color_ranges[k][0] + (self.color_ranges[k][1] - self.color_ranges[k][0]) * u[k],
                                            self.color_ranges[k][1]))
                 for k in order if self.color_ranges[k] is not None))
-        return AugmentParams(flip, (h, w), (y0, x0), (ch, cw), photometric)
+        return AugmentParams(flip, (h, w), (y0, x0), (ch, cw), photometric, rotate)
 
 
 def adjust_colors(images, params, device="cuda"):
@@ -296,3 +456,80 @@ def adjust_colors(images, params, device="cuda"):
     if single:
         return out[0]
     return [o.clone() for o in out]  # each result owns its memory, not a slice of the batch buffer
+
+
+def _rotate_on_device(tensors, sizes, params, dev, labels: bool):
+    """Pack, one orient call, unpack: what `rotate_images` and `rotate_maps` share.  `tensors` are flat-able host or
+    device tensors of one dtype, `sizes` their stored (H, W)."""
+    from . import ops
+    import numpy as np
+    per = 1 if labels else 3
+    off = [0]
+    for H, W in sizes:
+        off.append(off[-1] + H * W * per)
+    src = torch.empty(off[-1], dtype=tensors[0].dtype, device=dev)
+    dst = torch.empty_like(src)
+    for b, t in enumerate(tensors):
+        src[off[b]:off[b + 1]].copy_(t.reshape(-1), non_blocking=True)
+    desc = np.array([p.desc_row(off[b], *sizes[b], off[b], labels=labels) for b, p in enumerate(params)], dtype=np.int64)
+    (ops.orient_labels if labels else ops.orient_u8)(src, dst, desc)
+    out = []
+    for b, p in enumerate(params):
+        h, w = p.out_size(*sizes[b])
+        o = dst[off[b]:off[b + 1]]
+        out.append((o.view(h, w) if labels else o.view(h, w, 3)).clone())  # each result owns its memory
+    return out
+
+
+def _rotate_args(name, items, params, device):
+    single = not isinstance(items, (list, tuple))
+    items = [items] if single else list(items)
+    if not items:
+        raise ValueError(f"{name} is empty")
+    ps = list(params) if isinstance(params, (list, tuple)) else [params] * len(items)
+    if len(ps) != len(items) or not all(isinstance(p, RotateParams) for p in ps):
+        raise ValueError(f"params: expected one RotateParams or a list of {len(items)}, one per entry of {name}")
+    if not torch.cuda.is_available():
+        raise _lib.Wm2fError(f"rotate_{name}: the wm2f kernels run on a GPU only (no CPU fallback)")
+    _lib.load()
+    dev = next((x.device for x in items if isinstance(x, torch.Tensor) and x.is_cuda), torch.device(device))
+    if dev.type != "cuda":
+        raise _lib.Wm2fError(f"device={device}: the wm2f kernels run on a GPU only (no CPU fallback)")
+    return single, items, ps, dev
+
+
+def rotate_images(images, params, device="cuda"):
+    """The orientation(s) `params` on the GPU (csrc/orient.hip), byte for byte what Pillow's
+    `transpose` and `rotate(angle, BILINEAR, fillcolor=fill)` give.  `images`: one (H, W, 3) uint8 image (torch tensor on
+    host or device, numpy array or PIL RGB image) or a list of them; `params`: one `RotateParams` for every image or a
+    list with one per image.  Returns new uint8 device tensors of the turned size (one tensor for one image, a list for a
+    list); the inputs are never written."""
+    import numpy as np
+    from .preprocess import _image_hwc_u8
+    single, ims, ps, dev = _rotate_args("images", images, params, device)
+    ims = [_image_hwc_u8(im, i) for i, im in enumerate(ims)]
+    ts = [im if isinstance(im, torch.Tensor) else torch.from_numpy(np.array(im)) for im in ims]
+    out = _rotate_on_device(ts, [tuple(int(v) for v in t.shape[:2]) for t in ts], ps, dev, labels=False)
+    return out[0] if single else out
+
+
+def rotate_maps(maps, params, device="cuda"):
+    """The same for (H, W) id maps, uint8 or int32 (torch tensor, numpy array, or a PIL image of mode L or I), all of one
+    dtype: Pillow's `transpose` and `rotate(angle, NEAREST, fillcolor=map_fill)`.  Returns new device tensors of the
+    maps' dtype."""
+    import numpy as np
+    single, ms, ps, dev = _rotate_args("maps", maps, params, device)
+    ts = []
+    for i, m in enumerate(ms):
+        if not isinstance(m, (torch.Tensor, np.ndarray)):
+            m = np.array(m)
+        t = m if isinstance(m, torch.Tensor) else torch.from_numpy(np.array(m))
+        if t.ndim != 2 or t.dtype not in (torch.uint8, torch.int32) or t.numel() == 0:
+            raise ValueError(f"maps[{i}]: expected a non-empty (H, W) uint8 or int32 map, got {tuple(t.shape)} {t.dtype}")
+        ts.append(t)
+    if len({t.dtype for t in ts}) != 1:
+        raise ValueError("maps: all maps of one call must have the same dtype")
+    if ts[0].dtype == torch.uint8 and not all(0 <= p.map_fill <= 255 for p in ps):
+        raise ValueError("map_fill must lie in 0 .. 255 for uint8 maps")
+    out = _rotate_on_device(ts, [tuple(int(v) for v in t.shape) for t in ts], ps, dev, labels=True)
+    return out[0] if single else out

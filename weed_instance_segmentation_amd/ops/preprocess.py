@@ -96,3 +96,41 @@ def photometric_u8(images: torch.Tensor, desc) -> torch.Tensor:
     ws = torch.empty(max(B, 1), device=images.device, dtype=torch.int64)
     _launch("wm2f_photometric_u8", images, _p(images), images.numel(), d_ptr, _p(ws), B)
     return images
+
+
+def _orient_desc(desc):
+    d, d_ptr = _host_desc(desc)
+    if d.ndim != 2 or d.shape[1] != _lib.WM2F_ORIENT_DESC_LEN:
+        raise ValueError(f"desc: expected (B, {_lib.WM2F_ORIENT_DESC_LEN}), got {d.shape}")
+    return d, d_ptr
+
+
+def orient_u8(src: torch.Tensor, dst: torch.Tensor, desc) -> torch.Tensor:
+    """Vertical flip, quarter turns and rotation of packed uint8 HWC images (flat, on the device) from `src` into `dst`
+    (wm2f_orient_u8), byte for byte what Pillow's transpose and rotate(BILINEAR) give.  `desc` is a
+    host int64 array (B, 22): in_off, H, W, out_off (bytes), vflip, turns, affine, six float64 bit patterns of the
+    matrix, six fixed-point terms, the fill bytes r, g, b (`RotateParams.desc_row`).  One launch; `src` and `dst` must
+    not overlap.  Returns `dst`."""
+    _on_gpu(src, "src"), _on_gpu(dst, "dst")
+    if src.dtype != torch.uint8 or dst.dtype != torch.uint8 or not src.is_contiguous() or not dst.is_contiguous():
+        raise TypeError(f"src, dst: expected contiguous uint8 tensors, got {src.dtype}, {dst.dtype}")
+    if src.device != dst.device:
+        raise ValueError(f"src is on {src.device}, dst on {dst.device}")
+    d, d_ptr = _orient_desc(desc)
+    _launch("wm2f_orient_u8", src, _p(src), src.numel(), _p(dst), dst.numel(), d_ptr, int(d.shape[0]))
+    return dst
+
+
+def orient_labels(src: torch.Tensor, dst: torch.Tensor, desc) -> torch.Tensor:
+    """The same for packed uint8 or int32 id maps (wm2f_orient_labels_u8 / _i32): Pillow's transpose and
+    rotate(NEAREST).  Offsets count elements; the fill is the id in column 19.  Returns `dst`."""
+    _on_gpu(src, "src"), _on_gpu(dst, "dst")
+    _dtype_code(src, (torch.uint8, torch.int32), f"src must be uint8 or int32, got {src.dtype}")
+    if dst.dtype != src.dtype or not src.is_contiguous() or not dst.is_contiguous():
+        raise TypeError(f"src, dst: expected contiguous tensors of one dtype, got {src.dtype}, {dst.dtype}")
+    if src.device != dst.device:
+        raise ValueError(f"src is on {src.device}, dst on {dst.device}")
+    d, d_ptr = _orient_desc(desc)
+    symbol = "wm2f_orient_labels_u8" if src.dtype == torch.uint8 else "wm2f_orient_labels_i32"
+    _launch(symbol, src, _p(src), src.numel(), _p(dst), dst.numel(), d_ptr, int(d.shape[0]))
+    return dst

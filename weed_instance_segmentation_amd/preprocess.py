@@ -283,8 +283,11 @@ class Mask2FormerImageProcessor(Mask2FormerInstancePostProcessor):
         parameters each image is mirrored (flip), resized to the parameters' own (h, w) -- `size` and `size_divisor` do
         not apply -- and cut to the window; `pad_size` defaults to the batch's largest window.  Parameters that carry a
         `photometric` chain have it applied to the source image first, on the call's private device
-        copy: the caller's tensors are never written, and maps and labels do not see it.  The call stays deterministic:
-        the draws are `TrainAugmentation.sample`'s."""
+        copy: the caller's tensors are never written, and maps and labels do not see it.  Parameters that carry a
+        `rotate` with something enabled have image and map oriented next (vertical flip, quarter turns, rotation; DESIGN
+        section 30), one launch each into a second region of the private buffer; `size`, `origin` and `window` then
+        refer to the turned frame, and `map_fill` is a raw id, written as if before `do_reduce_labels`.  The call stays
+        deterministic: the draws are `TrainAugmentation.sample`'s."""
         unknown = set(overrides) - set(_SETTINGS)
         if unknown:
             raise TypeError(f"unexpected keyword arguments {sorted(unknown)}")
@@ -327,7 +330,11 @@ class Mask2FormerImageProcessor(Mask2FormerInstancePostProcessor):
         if dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
 
-        sizes_in = [tuple(int(v) for v in im.shape[:2]) for im in ims]
+        sizes_src = [tuple(int(v) for v in im.shape[:2]) for im in ims]  # as stored
+        # orientation: the resize, the tables and the window see the turned frame
+        orient = augs is not None and any(a.rotate is not None and a.rotate.enabled for a in augs)
+        sizes_in = [a.rotate.out_size(H, W) if a.rotate is not None else (H, W)
+                    for a, (H, W) in zip(augs, sizes_src)] if orient else sizes_src
         if augs is not None:
             frames = [a.size for a in augs]
             sizes_out = [a.window for a in augs]  # what the image occupies in the padded output
@@ -401,7 +408,13 @@ class Mask2FormerImageProcessor(Mask2FormerInstancePostProcessor):
                 else:
                     a = m.numpy() if isinstance(m, torch.Tensor) else m
                     hb[o_map + int(map_off[b]):o_map + int(map_off[b + 1])] = np.ascontiguousarray(a).reshape(-1)
-        buf = host.to(dev, non_blocking=True)
+        if orient:  # a second region behind the first: oriented images | oriented maps, device only
+            o_rimg = total
+            o_rmap = o_rimg + _aligned(int(img_off[-1]))
+            buf = torch.empty(o_rmap + _aligned(int(map_off[-1]) if maps is not None else 0), dtype=torch.uint8, device=dev)
+            buf[:total].copy_(host, non_blocking=True)
+        else:
+            buf = host.to(dev, non_blocking=True)
         for off, t in on_dev:
             buf[off:off + t.numel()].copy_(t.to(dev).reshape(-1))
         desc[:, 0] = img_off[:-1]
@@ -411,9 +424,18 @@ class Mask2FormerImageProcessor(Mask2FormerInstancePostProcessor):
             # colour jitter: in place on the private copy, before the flip and the resize read it
             from .augment import PhotometricParams
             none = PhotometricParams()
-            pdesc = np.array([(a.photometric or none).desc_row(int(img_off[b]), *sizes_in[b]) for b, a in enumerate(augs)],
+            pdesc = np.array([(a.photometric or none).desc_row(int(img_off[b]), *sizes_src[b]) for b, a in enumerate(augs)],
                              dtype=np.int64)
             ops.photometric_u8(buf[o_img:o_img + int(img_off[-1])], pdesc)
+        if orient:
+            # one launch from the first region into the second; images with nothing enabled are copied, and every offset
+            # stays what it was, so the kernels below only read another region
+            from .augment import RotateParams
+            rots = [a.rotate or RotateParams() for a in augs]
+            odesc = np.array([r.desc_row(int(img_off[b]), *sizes_src[b], int(img_off[b])) for b, r in enumerate(rots)],
+                             dtype=np.int64)
+            ops.orient_u8(buf[o_img:o_img + int(img_off[-1])], buf[o_rimg:o_rimg + int(img_off[-1])], odesc)
+            o_img = o_rimg
         if augs is None:
             pv, pm = ops.resize_normalize_u8(buf[o_img:o_img + int(img_off[-1])], desc, t_tab, t_lut, Hp, Wp)
         else:
@@ -425,6 +447,18 @@ class Mask2FormerImageProcessor(Mask2FormerInstancePostProcessor):
         # labels: nearest resize + presence flags, one flag copy, masks per image
         ig = s["ignore_index"]
         ldesc[:, 0] = map_off[:-1]
+        if orient:
+            odesc = np.array([r.desc_row(int(map_off[b]), *sizes_src[b], int(map_off[b]), labels=True)
+                              for b, r in enumerate(rots)], dtype=np.int64)
+            # map_fill is a raw id: the maps in the buffer are already reduced, so the fill is reduced the same way
+            fills = odesc[:, 19]
+            if s["do_reduce_labels"]:
+                fills = np.where(fills == 0, int(ig), fills - 1)
+            if fills.min() < 0 or fills.max() > 255:
+                raise ValueError(f"map_fill: the ids {sorted(set(fills.tolist()))} do not all fit the uint8 id maps")
+            odesc[:, 19] = fills
+            ops.orient_labels(buf[o_map:o_map + int(map_off[-1])], buf[o_rmap:o_rmap + int(map_off[-1])], odesc)
+            o_map = o_rmap
         resize_labels = ops.resize_nearest_labels if augs is None else ops.augment_nearest_labels
         lab, present = resize_labels(buf[o_map:o_map + int(map_off[-1])], ldesc, t_tab, Hp, Wp,
                                      255 if ig is None else int(ig))
