@@ -978,6 +978,45 @@ int wm2f_orient_labels_u8(const uint8_t* src, int64_t src_elems, uint8_t* dst, i
 int wm2f_orient_labels_i32(const int32_t* src, int64_t src_elems, int32_t* dst, int64_t dst_elems, const int64_t* desc,
                            int B, void* stream);
 
+/* ---- Simple Copy-Paste on device ------------------------------------------------------------
+ * Instances of one image of a batch are cut out and pasted, shifted by whole pixels, onto another image of the same
+ * batch (Ghiasi et al., CVPR 2021); nothing is blended.  pixels (B, C, H, W) float32, maps (B, H, W) int32.  A map value
+ * in 0 .. 254 is an instance id; every other value (255, negative, above 255) is no instance: copied through, never
+ * pasted, never counted.  All calls are out of place with respect to the batch: every image may be a source and a
+ * destination in one call.
+ *       desc   HOST int64 (B, WM2F_COPY_PASTE_DESC_LEN): source (-1: none, else another image of the batch), dy, dx,
+ *              h, w (the destination's valid window, 0 <= h <= H, 0 <= w <= W).
+ *       lut    DEVICE int32 (B, 256): lut[b][source id] = the id it is pasted as in image b (0 .. 254), or -1.  Entry 255
+ *              and values outside 0 .. 254 count as -1; an image without source has no live entry.
+ *       areas  DEVICE int32 (B, 3, 256): row 0 `before`, row 1 `after` (indexed by the id in the result), row 2
+ *              `original` (indexed by the source id).
+ * Paste rule.  Destination pixel (y, x) of image b takes source pixel (y - dy, x - dx) of image s = source when that
+ * position lies inside the (H, W) frame, its id i has lut[b][i] >= 0, and y < h, x < w.  Then all C values are copied as
+ * bit patterns and the map takes lut[b][i]; everywhere else the destination is copied.
+ * min_visible = num / den (0 <= num <= den <= 1024); every comparison is int64.
+ *   wm2f_copy_paste_select (step A, maps only): for every id i with lut_in[b][i] >= 0, original = its area in the whole
+ *     source frame, landed = the number of its pixels (ys, xs) with ys + dy < h, xs + dx < w (and both >= 0).
+ *     lut_out[b][i] = lut_in[b][i] when landed > 0 and landed den >= num original, else -1.  Writes row 2 of `areas`
+ *     (0 for ids that were not selected).  `workspace`: B * 256 int32, cleared by the call.
+ *   wm2f_copy_paste (step B): the paste with `lut` as it is.  before[b][i] = the number of pixels of the destination map
+ *     equal to i, after[b][i] the same in the pasted map (i in 0 .. 254); writes rows 0 and 1 of `areas`.
+ *   wm2f_copy_paste_prune (step C, maps only, in place on the pasted maps): every id with after > 0 and
+ *     after den < num before is repainted to ignore_index (which must not be an id).  With num = 0 nothing is launched.
+ * The destination's map and pixels are read once and written once; the source map is read where a source pixel can
+ * arrive and the source pixels only where something is pasted; 16-byte accesses when W % 4 == 0 and the pointers are
+ * 16-byte aligned (the source side when dx % 4 == 0 as well), one pixel per thread otherwise.  LUT and histograms live in
+ * LDS and are flushed with integer atomics: the counts are exact and the same from run to run.  No call allocates,
+ * keeps state or synchronises with the host.
+ * Bounds: B <= 65535, sides <= WM2F_PRE_MAX_SIDE, else WM2F_EUNSUPPORTED.  WM2F_EINVAL: a source outside -1 .. B - 1 or
+ * equal to its destination, a shift beyond +-65536, a window outside the frame, a bad fraction, in-place buffers. */
+#define WM2F_COPY_PASTE_DESC_LEN 5
+int wm2f_copy_paste_select(const int32_t* maps, const int32_t* lut_in, int32_t* lut_out, int32_t* areas, int32_t* workspace,
+                           const int64_t* desc, int B, int H, int W, int64_t num, int64_t den, void* stream);
+int wm2f_copy_paste(const float* pixels_in, const int32_t* maps_in, const int32_t* lut, float* pixels_out, int32_t* maps_out,
+                    int32_t* areas, const int64_t* desc, int B, int C, int H, int W, void* stream);
+int wm2f_copy_paste_prune(int32_t* maps, const int32_t* areas, int B, int H, int W, int64_t num, int64_t den,
+                          int ignore_index, void* stream);
+
 /* ---- connected components of class maps ------------------------------------------------
  * The cv2 steps of the reference's dataset loaders (datasets/pheno_bench/dataset.py:48-135, crop_weed
  * dataset_from_png_annotations.py:48-131): cv2.resize(INTER_NEAREST) of the mask, cv2.connectedComponents per class,

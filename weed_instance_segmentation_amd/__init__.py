@@ -17,8 +17,9 @@ from .rle import (coco_results, decode_rle, encode_label_maps, rle_from_string, 
                   save_coco_results)
 from .contours import (instance_polygons, save_via_annotations, trace_label_maps, via_annotations)  # noqa: F401
 from .preprocess import Mask2FormerImageProcessor  # noqa: F401
-from .augment import (AugmentParams, PhotometricParams, RotateParams, TrainAugmentation, adjust_colors,  # noqa: F401
-                      rotate_images, rotate_maps)
+from .augment import (AugmentParams, CopyPaste, CopyPasteParams, PhotometricParams, RotateParams,  # noqa: F401
+                      TrainAugmentation, adjust_colors, allocate_paste_ids, rotate_images, rotate_maps)
+from .data import CopyPasteBatcher, copy_paste  # noqa: F401
 from .visualize import (build_overlay_tables, convert_gt_map_to_result, render_label_overlay,  # noqa: F401
                         render_segmentation, render_segmentations, save_comparison)
 from .tiling import TileGrid, merge_tile_results, segment_tiled, tile_windows  # noqa: F401

@@ -31,6 +31,7 @@ WM2F_AUG_PRE_DESC_LEN, WM2F_AUG_LAB_DESC_LEN = 16, 12
 WM2F_PHOTO_BRIGHTNESS, WM2F_PHOTO_CONTRAST, WM2F_PHOTO_SATURATION, WM2F_PHOTO_HUE = 0, 1, 2, 3
 WM2F_PHOTO_DESC_LEN = 12
 WM2F_ORIENT_DESC_LEN = 22
+WM2F_COPY_PASTE_DESC_LEN = 5
 WM2F_PRE_MAX_IMAGES, WM2F_PRE_MAX_SIDE = 32, 16384
 # route[0] of wm2f_masked_xattn_route
 (WM2F_K2_UNSUPPORTED, WM2F_K2_FWD_GENERAL, WM2F_K2_FWD_FULL, WM2F_K2_BF16_FWD, WM2F_K2_BWD_GENERAL, WM2F_K2_BWD_FULL,
@@ -144,6 +145,9 @@ SIGNATURES = {
     "wm2f_orient_u8": (c_int, [_P, c_int64, _P, c_int64, POINTER(c_int64), _I, _P]),
     "wm2f_orient_labels_u8": (c_int, [_P, c_int64, _P, c_int64, POINTER(c_int64), _I, _P]),
     "wm2f_orient_labels_i32": (c_int, [_P, c_int64, _P, c_int64, POINTER(c_int64), _I, _P]),
+    "wm2f_copy_paste_select": (c_int, [_P, _P, _P, _P, _P, POINTER(c_int64), _I, _I, _I, c_int64, c_int64, _P]),
+    "wm2f_copy_paste": (c_int, [_P, _P, _P, _P, _P, _P, POINTER(c_int64), _I, _I, _I, _I, _P]),
+    "wm2f_copy_paste_prune": (c_int, [_P, _P, _I, _I, _I, c_int64, c_int64, _I, _P]),
     "wm2f_ccl_workspace": (c_int64, [_I, _I]),
     "wm2f_ccl_label": (c_int, [_P, _I, _I, _I, _I, _P, _P, POINTER(ctypes.c_uint8), _I, _I, _I, _P, _P, _P]),
     "wm2f_ccl_keys": (c_int, [_P, _I, _I, _I, _P, _P]),

@@ -163,7 +163,7 @@ class _AnnotatedPngDataset(torch.utils.data.Dataset):
     """File pairing and item assembly shared by the two loaders; subclasses give the mask file and the instance map."""
 
     def __init__(self, image_folder_path, annotation_path, processor, label2id: dict, max_input_dim: int = 1024,
-                 max_images=None, device="cuda", augment=None, generator=None):
+                 max_images=None, device="cuda", augment=None, generator=None, compact: bool = False):
         self.image_folder = image_folder_path
         self.annotation_path = annotation_path
         self.processor = processor
@@ -171,6 +171,7 @@ class _AnnotatedPngDataset(torch.utils.data.Dataset):
         self.max_input_dim = int(max_input_dim)
         self.device = torch.device(device)
         self.augment, self.generator = augment, generator  # a TrainAugmentation and its CPU torch.Generator, or None
+        self.compact = bool(compact)  # items carry the processed id map instead of the mask stack
         self.image_files = sorted(glob.glob(os.path.join(self.image_folder, "*.png")))
         self.valid_files = []
         for img_path in self.image_files:
@@ -201,29 +202,35 @@ class _AnnotatedPngDataset(torch.utils.data.Dataset):
         target_size = (height, width)
         instance_map, id_to_semantic = self._instance_map(torch.from_numpy(mask).to(self.device), dsize)
         return _assemble_item(self.processor, image, instance_map.cpu().numpy(), id_to_semantic, target_size, file_name,
-                              self.augment, self.generator)
+                              self.augment, self.generator, self.compact)
 
 
 def _assemble_item(processor, image, instance_map: np.ndarray, id_to_semantic: dict, target_size, file_name,
-                   augment=None, generator=None) -> dict:
+                   augment=None, generator=None, compact: bool = False) -> dict:
     """The item every reference loader returns: the processor's outputs for one image and its (H, W) int32 instance map
     (255 = ignore), with the map itself, the id dict, the target size and the file name.
     With `augment` (a TrainAugmentation) the parameters are drawn here for the loaded image from
     `generator`, `target_size` becomes the drawn window and the item also carries the parameters under "augment";
-    `original_map` and `id_to_semantic` still describe the file."""
+    `original_map` and `id_to_semantic` still describe the file.
+    With `compact` the item carries `instance_map`, the processed (Hp, Wp) int32 id map on the device, and neither
+    `mask_labels` nor `class_labels`: `collate_fn` and `expand_labels` take it as any compact sample, and `copy_paste`
+    works on such batches.  `id_to_semantic` names its ids: the processing leaves ids as they are."""
     call, extra = {}, {}
     if augment is not None:
         params = augment.sample(instance_map.shape[0], instance_map.shape[1], generator)
         call = {"augment": params, "pad_size": augment.pad_size}
         extra = {"augment": params}
         target_size = params.window
-    inputs = processor(images=[image], segmentation_maps=[instance_map], instance_id_to_semantic_id=id_to_semantic,
-                       return_tensors="pt", ignore_index=255, **call)
+    if compact:  # the stack the processor also builds is dropped below: keep it at a byte per pixel
+        call["mask_dtype"] = torch.uint8
+    inputs =processor(images=[image], segmentation_maps=[instance_map], instance_id_to_semantic_id=id_to_semantic,
+                       return_tensors="pt", ignore_index=255, return_instance_maps=compact, **call)
+    labels = ({"instance_map": inputs["instance_maps"][0]} if compact else
+              {"mask_labels": inputs["mask_labels"][0], "class_labels": inputs["class_labels"][0]})
     return {
         **extra,
         "pixel_values": inputs["pixel_values"][0],
-        "mask_labels": inputs["mask_labels"][0],
-        "class_labels": inputs["class_labels"][0],
+        **labels,
         "target_size": target_size,
         "original_map": instance_map,
         "id_to_semantic": id_to_semantic,
@@ -440,7 +447,7 @@ class SorghumWeedDataset(torch.utils.data.Dataset):
     `max_input_dim` and `max_images` stand for config.MAX_INPUT_DIM and config.MAX_IMAGES."""
 
     def __init__(self, image_folder_path, annotation_path, processor, label2id: dict, max_input_dim: int = 1024,
-                 max_images=None, device="cuda", augment=None, generator=None):
+                 max_images=None, device="cuda", augment=None, generator=None, compact: bool = False):
         import json
         self.image_folder = image_folder_path
         self.processor = processor
@@ -448,6 +455,7 @@ class SorghumWeedDataset(torch.utils.data.Dataset):
         self.max_input_dim = int(max_input_dim)
         self.device = torch.device(device)
         self.augment, self.generator = augment, generator  # a TrainAugmentation and its CPU torch.Generator, or None
+        self.compact = bool(compact)  # items carry the processed id map instead of the mask stack
         with open(annotation_path, "r") as f:
             self.data = list(json.load(f).values())
         self.valid_entries = []
@@ -468,7 +476,7 @@ class SorghumWeedDataset(torch.utils.data.Dataset):
         polygons, ids, id_to_semantic = _via_polygons(entry, self.label2id, scale, scale, skip_255=True)
         instance_map = polygons_to_instance_map(polygons, ids, (height, width), 255, self.device).cpu().numpy()
         return _assemble_item(self.processor, image, instance_map, id_to_semantic, (height, width), entry["filename"],
-                              self.augment, self.generator)
+                              self.augment, self.generator, self.compact)
 
 
 class CropWeedYamlDataset(torch.utils.data.Dataset):
@@ -476,7 +484,7 @@ class CropWeedYamlDataset(torch.utils.data.Dataset):
     GPU.  `annotation_path` is a folder of `*.yaml` files (sorted); each names its image with the 'filename' key."""
 
     def __init__(self, image_folder_path, annotation_path, processor, label2id: dict, max_input_dim: int = 1024,
-                 max_images=None, device="cuda", augment=None, generator=None):
+                 max_images=None, device="cuda", augment=None, generator=None, compact: bool = False):
         import yaml
         self.image_folder = image_folder_path
         self.annotation_path = annotation_path
@@ -485,6 +493,7 @@ class CropWeedYamlDataset(torch.utils.data.Dataset):
         self.max_input_dim = int(max_input_dim)
         self.device = torch.device(device)
         self.augment, self.generator = augment, generator  # a TrainAugmentation and its CPU torch.Generator, or None
+        self.compact = bool(compact)  # items carry the processed id map instead of the mask stack
         yaml_files = sorted(glob.glob(os.path.join(self.annotation_path, "*.yaml")))
         self.valid_files = []
         print(f'Scanning {len(yaml_files)} annotation files in "{self.annotation_path}"...')
@@ -519,7 +528,7 @@ class CropWeedYamlDataset(torch.utils.data.Dataset):
         polygons, ids, id_to_semantic = _cwfid_polygons(annotation, self.label2id, scale)
         instance_map = polygons_to_instance_map(polygons, ids, (height, width), 255, self.device).cpu().numpy()
         return _assemble_item(self.processor, image, instance_map, id_to_semantic, (height, width),
-                              os.path.basename(image_path), self.augment, self.generator)
+                              os.path.basename(image_path), self.augment, self.generator, self.compact)
 
 
 def load_ground_truth(image_name: str, target_size: tuple, annotation_file: str, img_dir: str, label2id: dict,

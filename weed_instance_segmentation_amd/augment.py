@@ -17,6 +17,9 @@ rotation by any angle).  Not in the reference, which trains on one deterministic
                             fill=(124, 116, 104), map_fill=255)                   # top-down imagery: any orientation
     out = rotate_images(image, RotateParams(vflip=True, turns=1, angle=13.37))    # outside the processor
 
+    recipe = CopyPaste(prob=0.5, select=0.5, classes=(1,), min_visible=0.25)      # Simple Copy-Paste between the images
+    batch = CopyPasteBatcher(recipe, generator)(collate_fn(compact_items))        # of a compact batch (data.py, section 31)
+
 `AugmentParams` are explicit and public, so an augmentation can be replayed.  The processor stays deterministic; every
 random draw happens in `TrainAugmentation.sample`, from the caller's CPU `torch.Generator`.  The pixels are produced by
 csrc/augment.hip, bit for bit what Pillow makes of the flipped, resized, cropped image, and the colours by
@@ -33,8 +36,8 @@ import torch
 
 from . import _lib
 
-__all__ = ["AugmentParams", "PhotometricParams", "RotateParams", "TrainAugmentation", "adjust_colors", "rotate_images",
-           "rotate_maps"]
+__all__ = ["AugmentParams", "CopyPaste", "CopyPasteParams", "PhotometricParams", "RotateParams", "TrainAugmentation",
+           "adjust_colors", "allocate_paste_ids", "rotate_images", "rotate_maps"]
 
 PHOTOMETRIC_KINDS = ("brightness", "contrast", "saturation", "hue")  # index = the WM2F_PHOTO_* constant
 _FLOAT32_MAX = 3.4028234663852886e38
@@ -418,6 +421,155 @@ class TrainAugmentation:
                                            self.color_ranges[k][1]))
                 for k in order if self.color_ranges[k] is not None))
         return AugmentParams(flip, (h, w), (y0, x0), (ch, cw), photometric, rotate)
+
+
+def _instance_ids(id_mapping) -> list:
+    """The ascending instance ids (0 .. 254) among the keys of one image's id -> class dictionary."""
+    return sorted(k for k in (int(k) for k in id_mapping) if 0 <= k <= 254)
+
+
+def allocate_paste_ids(selected, dest_id_mapping) -> tuple:
+    """The ids `selected` (ascending source ids) are pasted as: the k-th gets the k-th smallest value of 0 .. 254 that is
+    not a key of the destination's id -> class dictionary.  255 is never handed out.  With more selected ids than free
+    values the result is shorter than `selected`: the surplus, the highest source ids, is not pasted."""
+    taken = {int(k) for k in dest_id_mapping}
+    free = (v for v in range(255) if v not in taken)
+    return tuple(v for _, v in zip(selected, free))
+
+
+@dataclass(frozen=True)
+class CopyPasteParams:
+    """One batch's copy-paste, explicit so that it can be replayed.  Per destination image b:
+    `source[b]` (-1: nothing is pasted, else the index of ANOTHER image of the batch), `selected[b]` (the source ids to
+    paste, ascending, each in 0 .. 254; empty without source), `new_ids[b]` (what they are pasted as: entry k belongs to
+    selected[b][k]; it may be shorter than `selected[b]`, the surplus is not pasted; its values are distinct and in
+    0 .. 254) and `shift[b]` = (dy, dx) in whole pixels.  `min_visible` in [0, 1] is the share of its area an instance must
+    keep: a pasted one after the shift has clipped it, a destination one after the paste has covered it.  It is applied
+    as the integers `fraction()` = Fraction(min_visible).limit_denominator(1024)."""
+    source: tuple
+    selected: tuple
+    new_ids: tuple
+    shift: tuple
+    min_visible: float = 0.0
+
+    def __post_init__(self):
+        try:
+            source = tuple(self.source)
+            selected = tuple(tuple(s) for s in self.selected)
+            new_ids = tuple(tuple(s) for s in self.new_ids)
+            shift = tuple(self.shift)
+        except TypeError:
+            raise ValueError("source, selected, new_ids and shift must be sequences with one entry per image") from None
+        B = len(source)
+        if not (len(selected) == len(new_ids) == len(shift) == B):
+            raise ValueError(f"source, selected, new_ids and shift must have one entry per image, got lengths "
+                             f"{B}, {len(selected)}, {len(new_ids)}, {len(shift)}")
+        for b in range(B):
+            s = source[b]
+            if not _is_int(s) or not -1 <= s < B or s == b:
+                raise ValueError(f"source[{b}] = {s!r}: expected -1 or the index of another image of the batch of {B}")
+            sel, new = selected[b], new_ids[b]
+            if not all(_is_int(i) and 0 <= i <= 254 for i in sel) or list(sel) != sorted(set(sel)):
+                raise ValueError(f"selected[{b}] = {sel!r}: expected ascending distinct ids in 0 .. 254")
+            if s < 0 and sel:
+                raise ValueError(f"selected[{b}] = {sel!r}, but image {b} has no source")
+            if not all(_is_int(i) and 0 <= i <= 254 for i in new) or len(set(new)) != len(new):
+                raise ValueError(f"new_ids[{b}] = {new!r}: expected distinct ids in 0 .. 254 (255 is never an instance)")
+            if len(new) > len(sel):
+                raise ValueError(f"new_ids[{b}] has {len(new)} entries for {len(sel)} selected ids")
+        shift = tuple(_pair(v, f"shift[{b}]") for b, v in enumerate(shift))
+        mv = self.min_visible
+        if isinstance(mv, bool) or not isinstance(mv, (int, float)) or not 0.0 <= mv <= 1.0:
+            raise ValueError(f"min_visible must be a number in [0, 1], got {mv!r}")
+        object.__setattr__(self, "source", tuple(int(s) for s in source))
+        object.__setattr__(self, "selected", selected)
+        object.__setattr__(self, "new_ids", new_ids)
+        object.__setattr__(self, "shift", shift)
+        object.__setattr__(self, "min_visible", float(mv))
+
+    def __len__(self) -> int:
+        return len(self.source)
+
+    def fraction(self) -> tuple:
+        """(num, den): min_visible as the integers the kernels compare with, visible * den >= num * original."""
+        from fractions import Fraction
+        f = Fraction(self.min_visible).limit_denominator(1024)
+        return f.numerator, f.denominator
+
+    def lut(self):
+        """The (B, 256) int32 table of `ops.copy_paste`: lut[b][source id] = new id, -1 everywhere else."""
+        import numpy as np
+        lut = np.full((len(self), 256), -1, dtype=np.int32)
+        for b, (sel, new) in enumerate(zip(self.selected, self.new_ids)):
+            for i, v in zip(sel, new):
+                lut[b, i] = v
+        return lut
+
+
+class CopyPaste:
+    """Draws `CopyPasteParams` for a collated compact batch (Simple Copy-Paste, Ghiasi et al., CVPR 2021; DESIGN
+    section 31).  `prob`: the probability that an image receives a paste; `select`: the probability that an instance of
+    its source is taken; `max_instances`: None or the largest number of instances one paste may carry; `classes`: None or
+    the class ids that may be pasted (weeds only, say, for class balance); `shift`: None (instances keep their place),
+    a number m (dy and dx uniform over the integers -m .. m) or a pair (my, mx); `min_visible`: see `CopyPasteParams`.
+
+    `sample(id_mappings, generator)` takes the batch's id -> class dictionaries.  With one image nothing is pasted and
+    no draw is taken.  Otherwise it takes, per image b in order and always all of them, whether or not b ends up pasting:
+    one float32 uniform (paste when it is below `prob`); one randint(B - 1) for the source among the other images (k
+    stands for image k when k < b, else k + 1); then, for the ids 0 .. 254 of the source's dictionary whose class is
+    allowed, ascending, one float32 uniform each (kept when it is below `select`); with `max_instances` set, one
+    randperm(number of candidates), whose order decides which kept ids stay when they are more than `max_instances`;
+    then randint(2 my + 1) and randint(2 mx + 1) for the shift.  The same seed gives the same parameters on any
+    machine.  New ids come from `allocate_paste_ids`."""
+
+    def __init__(self, prob: float = 0.5, select: float = 0.5, max_instances=None, classes=None, shift=None,
+                 min_visible: float = 0.0):
+        for name, v in (("prob", prob), ("select", select), ("min_visible", min_visible)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= v <= 1.0:
+                raise ValueError(f"{name} must lie in [0, 1], got {v!r}")
+        if max_instances is not None and (not _is_int(max_instances) or max_instances < 0):
+            raise ValueError(f"max_instances must be None or an integer >= 0, got {max_instances!r}")
+        if shift is None:
+            my = mx = 0
+        elif _is_int(shift):
+            my = mx = shift
+        else:
+            my, mx = _pair(shift, "shift")
+        if my < 0 or mx < 0:
+            raise ValueError(f"shift: expected None, an integer >= 0 or a pair of them, got {shift!r}")
+        self.prob, self.select, self.min_visible = float(prob), float(select), float(min_visible)
+        self.max_instances = max_instances
+        self.classes = None if classes is None else frozenset(int(c) for c in classes)
+        self.shift = (my, mx)
+
+    def sample(self, id_mappings, generator: torch.Generator | None = None) -> CopyPasteParams:
+        if generator is not None and generator.device.type != "cpu":
+            raise ValueError("generator must be a CPU torch.Generator")
+        maps = [{int(k): int(v) for k, v in m.items()} for m in id_mappings]
+        B = len(maps)
+        source, selected, new_ids, shift = [], [], [], []
+        for b in range(B):
+            if B == 1:
+                source.append(-1), selected.append(()), new_ids.append(()), shift.append((0, 0))
+                break
+            paste = float(torch.rand(1, generator=generator).item()) < self.prob
+            k = int(torch.randint(B - 1, (1,), generator=generator).item())
+            s = k if k < b else k + 1
+            cand = [i for i in _instance_ids(maps[s]) if self.classes is None or maps[s][i] in self.classes]
+            kept = [i for i in cand if float(torch.rand(1, generator=generator).item()) < self.select]
+            if self.max_instances is not None:
+                order = torch.randperm(len(cand), generator=generator).tolist()
+                if len(kept) > self.max_instances:
+                    first = [cand[j] for j in order if cand[j] in kept][:self.max_instances]
+                    kept = sorted(first)
+            dy = int(torch.randint(2 * self.shift[0] + 1, (1,), generator=generator).item()) - self.shift[0]
+            dx = int(torch.randint(2 * self.shift[1] + 1, (1,), generator=generator).item()) - self.shift[1]
+            new = allocate_paste_ids(kept, maps[b]) if paste else ()
+            if not paste or not new:
+                source.append(-1), selected.append(()), new_ids.append(()), shift.append((0, 0))
+                continue
+            source.append(s), selected.append(tuple(kept)), new_ids.append(new), shift.append((dy, dx))
+        return CopyPasteParams(tuple(source), tuple(selected), tuple(new_ids), tuple(shift), self.min_visible)
 
 
 def adjust_colors(images, params, device="cuda"):

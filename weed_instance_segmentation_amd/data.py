@@ -14,6 +14,10 @@ matcher read directly.  Full samples written by the reference keep loading: `tes
 by the reference's own `process_and_save` (`tests/golden/make_reference_samples.py`) and `tests/test_data.py` holds this
 module to what the reference's own loader and `collate_fn` make of them.
 
+Compact batches are also what Simple Copy-Paste works on: `copy_paste` pastes instances between
+the images of a collated compact batch on the device (csrc/copy_paste.hip) and `CopyPasteBatcher` samples, pastes and
+expands in one call.
+
 Files are read with `torch.load(..., weights_only=True)`: nothing in a file is executed.  The reference's samples carry
 `original_map` as a NUMPY array (`datasets/pheno_bench/dataset.py:85`, `:132`), which the restricted unpickler refuses
 by default; exactly the three globals a plain numeric array pickles to (`numpy.ndarray`, `numpy.dtype`, numpy's
@@ -146,3 +150,68 @@ def expand_labels(batch: dict, device) -> dict:
             cl.append(c.to(device, non_blocking=True))
     out["mask_labels"], out["class_labels"] = ml, cl
     return out
+
+
+def copy_paste(batch: dict, params, device="cuda", ignore_index: int = IGNORE_INDEX, valid_sizes=None) -> dict:
+    """Simple Copy-Paste between the images of a collated COMPACT batch (csrc/copy_paste.hip): per
+    destination image, the instances `params` (a `CopyPasteParams`) selects in its source are pasted, shifted, into the
+    destination's valid window -- `valid_sizes[b]` = (h, w), the un-padded part; None: the whole frame -- and the id maps
+    follow: pasted instances get their new ids, instances the paste hides disappear, and with `params.min_visible`
+    instances left with less than that share of themselves are dropped (a pasted one is not pasted, a destination one
+    becomes `ignore_index`).  Returns a NEW batch: new `pixel_values`, `instance_maps` as one (B, H, W) int32 device tensor,
+    `id_mappings` with `new id -> source class` added to each destination's entries, `mask_labels` / `class_labels` None,
+    every other key passed through -- ready for `expand_labels`.  The caller's batch is not written.  Nothing
+    synchronises with the host: whether a selected instance really landed is decided on the device, so `id_mappings` may
+    name ids the map no longer holds; `expand_labels` reads the map."""
+    from .augment import CopyPasteParams
+    if not isinstance(params, CopyPasteParams):
+        raise ValueError(f"params: expected a CopyPasteParams, got {type(params).__name__}")
+    maps = batch.get("instance_maps")
+    if maps is None or any(m is None for m in maps):
+        raise ValueError("copy_paste works on compact samples: the batch has no `instance_maps` for every image (mask "
+                         "stacks only).  Store or load the samples with compact=True and call expand_labels afterwards.")
+    pv = batch["pixel_values"]
+    B = int(pv.shape[0])
+    if len(params) != B or len(maps) != B or len(batch["id_mappings"]) != B:
+        raise ValueError(f"the batch has {B} images, params {len(params)}, instance_maps {len(maps)}")
+    id_maps = [{int(k): int(v) for k, v in m.items()} for m in batch["id_mappings"]]
+    merged = []
+    for b in range(B):
+        entry = dict(id_maps[b])
+        s = params.source[b]
+        for i, v in zip(params.selected[b], params.new_ids[b]):
+            if v in id_maps[b]:
+                raise ValueError(f"new_ids[{b}]: id {v} already names an instance of image {b}")
+            if i not in id_maps[s]:
+                raise ValueError(f"selected[{b}]: id {i} is not an instance of its source, image {s}")
+            entry[v] = id_maps[s][i]
+        merged.append(entry)
+    if valid_sizes is not None and len(valid_sizes) != B:
+        raise ValueError(f"valid_sizes: expected {B} (h, w) pairs, got {len(valid_sizes)}")
+    dev = torch.device(device)
+    stack = torch.stack([torch.as_tensor(m) for m in maps]) if not isinstance(maps, torch.Tensor) else maps
+    if stack.ndim != 3 or tuple(stack.shape[1:]) != tuple(pv.shape[2:]):
+        raise ValueError(f"instance_maps {tuple(stack.shape)} do not match pixel_values {tuple(pv.shape)}")
+    stack = stack.to(dev, non_blocking=True).to(torch.int32)
+    window = None if valid_sizes is None else [[int(h), int(w)] for h, w in valid_sizes]
+    pixels, new_maps, _, _ = ops.copy_paste(pv.to(dev, non_blocking=True), stack, params.source, params.lut(), params.shift,
+                                            window, params.fraction(), ignore_index)
+    out = dict(batch)
+    out["pixel_values"], out["instance_maps"], out["id_mappings"] = pixels, new_maps, merged
+    out["mask_labels"], out["class_labels"] = [None] * B, [None] * B
+    return out
+
+
+class CopyPasteBatcher:
+    """`batcher(collated_compact_batch)`: draws the batch's `CopyPasteParams` from `recipe` (a `CopyPaste`) and
+    `generator` (a CPU torch.Generator), pastes (`copy_paste`) and expands the labels (`expand_labels`) on `device`.
+    The parameters of the last call stay in `last_params`, so a batch can be replayed."""
+
+    def __init__(self, recipe, generator=None, device="cuda", ignore_index: int = IGNORE_INDEX):
+        self.recipe, self.generator, self.device, self.ignore_index = recipe, generator, device, ignore_index
+        self.last_params = None
+
+    def __call__(self, batch: dict, valid_sizes=None) -> dict:
+        params = self.recipe.sample(batch["id_mappings"], self.generator)
+        self.last_params = params
+        return expand_labels(copy_paste(batch, params, self.device, self.ignore_index, valid_sizes), self.device)

@@ -278,7 +278,8 @@ class Mask2FormerImageProcessor(Mask2FormerInstancePostProcessor):
         return self.preprocess(images, segmentation_maps, instance_id_to_semantic_id, **kwargs)
 
     def preprocess(self, images, segmentation_maps=None, instance_id_to_semantic_id=None, return_tensors="pt",
-                   device="cuda", mask_dtype: torch.dtype = torch.float32, augment=None, **overrides) -> BatchFeature:
+                   device="cuda", mask_dtype: torch.dtype = torch.float32, augment=None,
+                   return_instance_maps: bool = False, **overrides) -> BatchFeature:
         """`augment`: None, one `AugmentParams` for every image or a list with one per image.  With
         parameters each image is mirrored (flip), resized to the parameters' own (h, w) -- `size` and `size_divisor` do
         not apply -- and cut to the window; `pad_size` defaults to the batch's largest window.  Parameters that carry a
@@ -287,7 +288,10 @@ class Mask2FormerImageProcessor(Mask2FormerInstancePostProcessor):
         `rotate` with something enabled have image and map oriented next (vertical flip, quarter turns, rotation; DESIGN
         section 30), one launch each into a second region of the private buffer; `size`, `origin` and `window` then
         refer to the turned frame, and `map_fill` is a raw id, written as if before `do_reduce_labels`.  The call stays
-        deterministic: the draws are `TrainAugmentation.sample`'s."""
+        deterministic: the draws are `TrainAugmentation.sample`'s.
+        `return_instance_maps=True` (with `segmentation_maps`): the result also carries `instance_maps`, the processed
+        (B, Hp, Wp) int32 id map `mask_labels` are made from, padded with `ignore_index` -- what a compact sample stores
+        and `copy_paste` works on."""
         unknown = set(overrides) - set(_SETTINGS)
         if unknown:
             raise TypeError(f"unexpected keyword arguments {sorted(unknown)}")
@@ -500,4 +504,6 @@ class Mask2FormerImageProcessor(Mask2FormerInstancePostProcessor):
             class_labels.append(torch.tensor(cls, dtype=torch.int64).to(dev, non_blocking=True))
         out["mask_labels"] = mask_labels
         out["class_labels"] = class_labels
+        if return_instance_maps:
+            out["instance_maps"] = lab
         return out
