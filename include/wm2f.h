@@ -1244,6 +1244,68 @@ int wm2f_tile_link(const int32_t* hist, const int32_t* pairs, const int32_t* lab
 int wm2f_tile_compose(const void* tiles, int dtype, const int32_t* n_ids, const int32_t* geom, const int32_t* remap,
                       int32_t* out, int T, int th, int tw, int N, int H, int W, void* stream);
 
+/* ---- repairing id maps: small pieces, largest piece, holes -----------------------------------
+ * A predicted id map paints thresholded masks over one another: an id often owns one plant-sized piece plus detached
+ * specks, and plants have pinholes.  This call repairs a whole (B, H, W) stack in a fixed chain of launches, whatever
+ * the number of instances; tests/clean_reference.py restates the contract with scipy.ndimage.label.
+ * Input: map (B, H, W) is WM2F_F32, WM2F_I32 or WM2F_U8; which value is which id follows wm2f_labelmap_instance_stats
+ *   (a float counts as the integer it equals, +-0 as 0; negative, fractional, not finite or >= 2^24: no id).  The
+ *   instances are the ids 0 .. N-1; every other pixel is FREE (-1, no-id values, ids >= N such as a 255 ignore value).
+ * Steps, in this order:
+ *   1. PIECES.  Two pixels of one id join when they are 8-neighbours; a piece is a connected set of one id, its area
+ *      its pixel count, its first pixel its smallest linear index y * W + x.
+ *   2. keep.  WM2F_CLEAN_KEEP_ALL keeps every piece; WM2F_CLEAN_KEEP_LARGEST keeps per id and image the piece of
+ *      greatest area only, among equal areas the one with the smallest first pixel.
+ *   3. min_area (>= 0).  A piece still kept is dropped when its area < min_area (under KEEP_LARGEST an id whose
+ *      largest piece is too small disappears).  Dropped pixels become free.
+ *   4. fill_holes (0 / 1) with max_hole_area (< 0: no limit).  On the map after steps 2-3 free pixels join when they
+ *      are 4-neighbours (the dual connectivity: a diagonal gap in an 8-connected ring does not leak).  A free
+ *      component is a HOLE OF k when it touches no image border and every id pixel 4-adjacent to it carries the same
+ *      id k; a hole of k with area <= max_hole_area is painted k.  Components that touch the border or are bounded by
+ *      two or more ids stay free.  Holes are judged against the map after steps 2-3, never against partly filled
+ *      output.  A speck of j inside plant i that step 3 dropped becomes (part of) a hole of i and is filled.
+ *   5. relabel (0 / 1).  With 1 the ids that still own a pixel are renumbered 0 .. n'-1 in ascending old-id order.
+ * Outputs: out (B, H, W), WM2F_I32 or WM2F_F32 (out_dtype), overwritten, must not overlap map: the pixel's final id, -1
+ *   when free.  stats (B, N, 8) int64, overwritten:
+ *     [area_in, pieces_in, pieces_kept, area_kept, holes_filled, pixels_filled, area_out, new_id],
+ *   area_out = area_kept + pixels_filled; new_id is -1 for an id without a pixel in out and the old id when relabel = 0.
+ *   n_out (B) int32: the number of ids that own a pixel in out.  stats may be NULL when N = 0.
+ * With KEEP_ALL, min_area <= 1 and fill_holes = 0, out holds exactly the ids of map.
+ * H, W <= 16384, B <= 32, N <= 4096, else WM2F_EUNSUPPORTED; bad flags, a negative min_area, an unknown phase and
+ * overlapping buffers are WM2F_EINVAL.  workspace: wm2f_labelmap_clean_workspace(B, H, W, N) bytes (-1 for a bad
+ * size), 8-byte aligned, no clearing needed: 12 bytes per (image, id) and 20 bytes per pixel (id, union-find parent,
+ * and at root pixels the area and the min / max adjacent id), each array rounded up to 16 bytes.  No call allocates,
+ * keeps state or waits for the device.
+ * phase: WM2F_CLEAN_ALL runs the chain; the other values run one part of it with the same arguments and workspace, in
+ *   this order (the binding launches them one by one so that a kernel timer sees each):
+ *   WM2F_CLEAN_PIECES  init; the 8-connected labelling: local (a 32 x 32 tile per workgroup, union-find in LDS whose
+ *                      union links the larger root under the smaller by atomicMin -- a root is the smallest index of its
+ *                      set, whatever the schedule -- and per tile root its pixel count in LDS), merge (device-scope
+ *                      atomicMin across tile borders), flatten (every tile root points at its final root and adds its
+ *                      tile's count there: one integer atomic per (tile, tile root), none per pixel).
+ *   WM2F_CLEAN_CHOOSE  best: per piece one 64-bit atomicMax of area << 32 | (0xFFFFFFFF - first pixel) on its id's slot
+ *                      (exact: H * W <= 2^28), with area_in and pieces_in; while N <= 1024 a workgroup gathers its 4096
+ *                      pixels' pieces per id in LDS (20 B per id) and flushes the ids it saw, above that the pieces go to
+ *                      the result directly; keep: a piece is kept iff its key equals that slot or KEEP_ALL is set,
+ *                      and its area >= min_area.
+ *   WM2F_CLEAN_HOLES   (nothing when fill_holes = 0) the same labelling code on the free pixels, 4-connected, which also
+ *                      collects per component a border flag and the min and max of the 4-adjacent ids; then one add per
+ *                      hole into holes_filled and pixels_filled.
+ *   WM2F_CLEAN_PAINT   relabel (a workgroup per image scans area_out > 0 over the N ids into a table) and paint (16-byte
+ *                      stores when W % 4 == 0 and out is 16-byte aligned, pixel by pixel otherwise, same results).
+ * 12 kernel launches with holes, 8 without, at every N >= 1, B and size.  All integer, bit-identical from run to run. */
+#define WM2F_CLEAN_KEEP_ALL 0
+#define WM2F_CLEAN_KEEP_LARGEST 1
+#define WM2F_CLEAN_ALL 0
+#define WM2F_CLEAN_PIECES 1
+#define WM2F_CLEAN_CHOOSE 2
+#define WM2F_CLEAN_HOLES 3
+#define WM2F_CLEAN_PAINT 4
+int64_t wm2f_labelmap_clean_workspace(int B, int H, int W, int N);
+int wm2f_labelmap_clean(const void* map, int dtype, void* out, int out_dtype, int64_t* stats, int32_t* n_out,
+                        void* workspace, int B, int H, int W, int N, int keep, int64_t min_area, int fill_holes,
+                        int64_t max_hole_area, int relabel, int phase, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,8 @@ WM2F_PHOTO_BRIGHTNESS, WM2F_PHOTO_CONTRAST, WM2F_PHOTO_SATURATION, WM2F_PHOTO_HU
 WM2F_PHOTO_DESC_LEN = 12
 WM2F_ORIENT_DESC_LEN = 22
 WM2F_COPY_PASTE_DESC_LEN = 5
+WM2F_CLEAN_KEEP_ALL, WM2F_CLEAN_KEEP_LARGEST = 0, 1
+WM2F_CLEAN_ALL, WM2F_CLEAN_PIECES, WM2F_CLEAN_CHOOSE, WM2F_CLEAN_HOLES, WM2F_CLEAN_PAINT = range(5)
 WM2F_PRE_MAX_IMAGES, WM2F_PRE_MAX_SIDE = 32, 16384
 # route[0] of wm2f_masked_xattn_route
 (WM2F_K2_UNSUPPORTED, WM2F_K2_FWD_GENERAL, WM2F_K2_FWD_FULL, WM2F_K2_BF16_FWD, WM2F_K2_BWD_GENERAL, WM2F_K2_BWD_FULL,
@@ -175,6 +177,8 @@ SIGNATURES = {
     "wm2f_tile_owned_counts": (c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     "wm2f_tile_link": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "wm2f_tile_compose": (c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "wm2f_labelmap_clean_workspace": (c_int64, [_I, _I, _I, _I]),
+    "wm2f_labelmap_clean": (c_int, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, c_int64, _I, c_int64, _I, _I, _P]),
 }
 
 # additions of the profiling library (include/wm2f_prof.h)

@@ -12,8 +12,17 @@ on the same kernel.
 
 `boundary_maps` is the pixel work of Boundary IoU: two launches of csrc/boundary.hip whatever the
 number of instances and the width of the band.
+
+    from weed_instance_segmentation_amd import CleanOptions, clean_label_maps
+    fixed = clean_label_maps(prediction["segmentation"], n, CleanOptions(min_area=16, keep="largest", fill_holes=True))
+
+`clean_label_maps` repairs an id map -- specks dropped, one connected piece per instance, pinholes
+filled -- in a fixed chain of launches of csrc/clean.hip whatever the number of instances.  The post-processor, the
+tiled route and `test_with_metrics` take the same `CleanOptions` as `clean=`.
 """
 from __future__ import annotations
+
+import dataclasses
 
 import numpy as np
 import torch
@@ -105,3 +114,82 @@ def boundary_maps(maps, dilation_ratio: float = 0.02, dilation: int | None = Non
     stack = seg.to(dev)
     out = ops.labelmap_boundary(stack.unsqueeze(0) if seg.dim() == 2 else stack, d)
     return out[0] if seg.dim() == 2 else out
+
+
+@dataclasses.dataclass(frozen=True)
+class CleanOptions:
+    """What `clean_label_maps` (and `clean=` of the post-processor, `merge_tile_results`, `segment_tiled` and
+    `test_with_metrics`) does to every instance of an id map, in this order:
+
+    - `keep`: "all" keeps every 8-connected piece of an instance, "largest" only the piece with the most pixels (the
+      first in raster order among equals);
+    - `min_area`: a piece still kept is dropped when it has fewer pixels; dropped pixels become background;
+    - `fill_holes`: background enclosed by ONE instance (4-connected, touching no image border) is painted with it -- a
+      hole bounded by two instances stays; `max_hole_area` limits the size of a hole that is filled (None: any)."""
+    min_area: int = 0
+    keep: str = "all"
+    fill_holes: bool = False
+    max_hole_area: int | None = None
+
+    def __post_init__(self):
+        if self.keep not in ("all", "largest"):
+            raise ValueError(f"CleanOptions: keep must be 'all' or 'largest', got {self.keep!r}")
+        for name in ("min_area", "max_hole_area"):
+            v = getattr(self, name)
+            if v is None and name == "max_hole_area":
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+                raise ValueError(f"CleanOptions: {name} must be a non-negative integer, got {v!r}")
+        if not isinstance(self.fill_holes, (bool, np.bool_)):
+            raise ValueError(f"CleanOptions: fill_holes must be a bool, got {self.fill_holes!r}")
+
+    def kernel_arguments(self) -> dict:
+        """The keywords of `ops.labelmap_clean`."""
+        return {"keep": self.keep, "min_area": int(self.min_area), "fill_holes": bool(self.fill_holes),
+                "max_hole_area": None if self.max_hole_area is None else int(self.max_hole_area)}
+
+
+def cleaned_segments_info(segments, new_id) -> list:
+    """The host half of `clean=`: `segments` (entries with ids 0 .. n-1) and `new_id`, column 7 of the kernel's stats for
+    one image (new_id[k]: the id instance k has in the cleaned map, -1 when it owns no pixel there) -> copies of the
+    surviving entries with "id" replaced; order, labels, scores and every other key unchanged."""
+    out = []
+    for info in segments:
+        k = int(new_id[int(info["id"])])
+        if k >= 0:
+            out.append({**info, "id": k})
+    return out
+
+
+def clean_label_maps(maps, n: int, options: CleanOptions | None = None, *, relabel: bool = False, return_stats: bool = False,
+                     **fields):
+    """Repair one (H, W) id map or a (B, H, W) stack -- fp32 with -1 background (the post-processor's map), int32 or
+    uint8, on the device or the host (a host map is moved to the current GPU).  The instances are the ids 0 .. n-1; every
+    other value is background.  `options` (or its fields as keywords: `clean_label_maps(m, n, keep="largest")`) says
+    what is done, see `CleanOptions`; `relabel=True` renumbers the ids that still own a pixel 0 .. n'-1 in ascending
+    order.
+
+    Returns an int32 device tensor of the input's shape with -1 background -- `instance_statistics`, `encode_label_maps`,
+    `trace_label_maps`, `render_label_overlay` and the metrics take it as it is.  `return_stats=True` returns
+    (map, stats): stats (..., n, 8) int64 on the device, per id [area_in, pieces_in, pieces_kept, area_kept,
+    holes_filled, pixels_filled, area_out, new_id] (new_id -1: the id is gone)."""
+    if options is None:
+        options = CleanOptions(**fields)
+    elif not isinstance(options, CleanOptions):
+        raise TypeError(f"clean_label_maps: options must be a CleanOptions, got {type(options).__name__}")
+    elif fields:
+        options = dataclasses.replace(options, **fields)
+    if not torch.cuda.is_available():
+        raise _lib.Wm2fError("clean_label_maps runs on a GPU only (no CPU fallback): no device is visible")
+    seg = torch.from_numpy(np.ascontiguousarray(maps)) if isinstance(maps, np.ndarray) else torch.as_tensor(maps)
+    if seg.dim() not in (2, 3):
+        raise ValueError(f"clean_label_maps: expected (H, W) or (B, H, W), got {tuple(seg.shape)}")
+    if seg.dtype not in (torch.float32, torch.int32, torch.uint8):
+        raise TypeError(f"clean_label_maps: maps fp32 / int32 / uint8, got {seg.dtype}")
+    dev = seg.device if seg.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    stack = seg.to(dev)
+    out, stats, _ = ops.labelmap_clean(stack.unsqueeze(0) if seg.dim() == 2 else stack, int(n), relabel=relabel,
+                                       **options.kernel_arguments())
+    if seg.dim() == 2:
+        out, stats = out[0], stats[0]
+    return (out, stats) if return_stats else out

@@ -24,6 +24,7 @@ CONV3X3_SPLIT = True
 from .._lib import check
 from ._core import KernelTimer, _p, _stream, set_kernel_timer
 from .ccl import label_components, resize_nearest_tables
+from .clean import labelmap_clean
 from .copy_paste import copy_paste
 from .fused import (add_broadcast, bias_act_, bias_relu_maxpool, group_norm_act_, group_norm_tokens_, resize_bilinear,
                     resize_pyramid, tokens_to_nchw)

@@ -107,8 +107,17 @@ class Mask2FormerInstancePostProcessor:
     def post_process_instance_segmentation(self, outputs, threshold: float = 0.5, mask_threshold: float = 0.5,
                                            overlap_mask_area_threshold: float = 0.8, target_sizes=None,
                                            return_coco_annotation: bool = False, return_binary_maps: bool = False,
-                                           return_instance_stats: bool = False, return_polygons: bool = False):
-        """`return_polygons=True` (not an argument of the dependency) adds "polygons" to every `segments_info` entry that
+                                           return_instance_stats: bool = False, return_polygons: bool = False,
+                                           clean=None):
+        """`clean=CleanOptions(...)` (not an argument of the dependency; `instances.CleanOptions`) repairs every id map on
+        the device before anything is taken from it: pieces below `min_area` dropped, with
+        keep="largest" one connected piece per instance, with fill_holes=True enclosed background painted.  Entries of
+        `segments_info` whose instance owns no pixel afterwards are dropped and the rest renumbered 0 .. n'-1 ("id" is
+        the value in the returned map; order, labels and scores unchanged); statistics, the `return_coco_annotation`
+        encoding and polygons all describe the cleaned map.  With `return_binary_maps=True` the stack is then cut from
+        the cleaned map (`map == id`, fp32, one map per remaining entry) and not from the logits -- otherwise stack and
+        `segments_info` would disagree.  clean=None changes nothing.
+        `return_polygons=True` (not an argument of the dependency) adds "polygons" to every `segments_info` entry that
         still owns a pixel of the returned id map: its boundary loops `{"points": (P, 2) int32 x, y, "hole": bool}` in
         pixel coordinates, as `contours.trace_label_maps` gives them, from one trace per distinct target size (DESIGN
         section 27).
@@ -119,6 +128,10 @@ class Mask2FormerInstancePostProcessor:
         device-to-host copy."""
         if return_coco_annotation and return_binary_maps:
             raise ValueError("return_coco_annotation and return_binary_maps can not be both set to True.")
+        if clean is not None:
+            from .instances import CleanOptions, cleaned_segments_info
+            if not isinstance(clean, CleanOptions):
+                raise TypeError(f"clean must be a CleanOptions or None, got {type(clean).__name__}")
         cls = outputs.class_queries_logits
         logits = outputs.masks_queries_logits
         if not logits.is_cuda:
@@ -155,6 +168,7 @@ class Mask2FormerInstancePostProcessor:
         keep_all = torch.zeros(B, Q, dtype=torch.bool, device=dev)
         kept_q_all = torch.zeros(B, Q, dtype=torch.int32, device=dev)
         stats_all = torch.zeros(B, Q, 8, dtype=torch.int64, device=dev) if return_instance_stats else None
+        new_id_all = torch.full((B, Q), -1, dtype=torch.int64, device=dev) if clean is not None else None
         for size in dict.fromkeys(sizes):  # one launch group per distinct target size
             rows = [i for i in range(B) if sizes[i] == size]
             ridx = torch.tensor(rows, device=dev)
@@ -169,6 +183,9 @@ class Mask2FormerInstancePostProcessor:
             kept_q = torch.gather(qi, 1, order).contiguous()
             n_kept = keep.sum(1).to(torch.int32)
             seg = ops.instance_segmentation(lg, kept_q, n_kept, size)
+            if clean is not None:  # in the map's own dtype, ids renumbered: everything below describes the cleaned map
+                seg, clean_stats, _ = ops.labelmap_clean(seg, Q, relabel=True, out_dtype=seg.dtype, **clean.kernel_arguments())
+                new_id_all[ridx] = clean_stats[:, :, 7]
             keep_all[ridx] = keep
             kept_q_all[ridx] = kept_q
             if return_instance_stats:
@@ -181,7 +198,11 @@ class Mask2FormerInstancePostProcessor:
                 seg_out[i] = seg[j]
 
         # ---- the one device-to-host copy
-        keep_cpu, score_cpu = keep_all.cpu(), pred_scores.cpu()
+        if clean is None:
+            keep_cpu, score_cpu = keep_all.cpu(), pred_scores.cpu()
+        else:  # the new ids travel with the flags
+            flags = torch.cat([keep_all.to(torch.int64), new_id_all], 1).cpu()
+            keep_cpu, new_id_cpu, score_cpu = flags[:, :Q].bool(), flags[:, Q:].numpy(), pred_scores.cpu()
         if return_instance_stats:
             from .instances import stats_to_boxes
             area, bbox, centroid = (t.tolist() for t in stats_to_boxes(stats_all.cpu()))
@@ -190,6 +211,8 @@ class Mask2FormerInstancePostProcessor:
             ks = torch.nonzero(keep_cpu[i]).flatten().tolist()
             segments = [{"id": r, "label_id": int(labels_cpu[i, j]), "was_fused": False, "score": round(float(score_cpu[i, j]), 6)}
                         for r, j in enumerate(ks)]
+            if clean is not None:  # the survivors are numbered 0 .. n'-1 in this order
+                segments = cleaned_segments_info(segments, new_id_cpu[i])
             if return_instance_stats:
                 for r, seg_info in enumerate(segments):
                     seg_info["area"] = area[i][r]
@@ -198,8 +221,11 @@ class Mask2FormerInstancePostProcessor:
             segmentation = seg_out[i]
             if return_coco_annotation:
                 segmentation = rle_out[i]
-            if return_binary_maps and ks:
+            if return_binary_maps and ks and clean is None:
                 segmentation = ops.instance_maps(logits[i], kept_q_all[i], len(ks), sizes[i])
+            elif return_binary_maps and segments:
+                ids = torch.arange(len(segments), device=dev, dtype=seg_out[i].dtype).view(-1, 1, 1)
+                segmentation = (seg_out[i].unsqueeze(0) == ids).to(torch.float32)
             results.append({"segmentation": segmentation, "segments_info": segments})
         if return_polygons:
             from .contours import _add_polygons

@@ -143,7 +143,8 @@ def _tile_tables(results, T: int):
     return n_ids, labels
 
 
-def merge_tile_results(results, grid: TileGrid, merge_threshold=(1, 2), return_instance_stats: bool = False) -> dict:
+def merge_tile_results(results, grid: TileGrid, merge_threshold=(1, 2), return_instance_stats: bool = False,
+                       clean=None) -> dict:
     """Merge the per-tile results of `post_process_instance_segmentation(target_sizes=[(grid.th, grid.tw)] * T)` (tiles in
     `grid` order) into one image's result: {"segmentation": (H, W) int32 on the device with -1 background,
     "segments_info": [...]}, entries as `merged_segments_info` gives them.
@@ -153,7 +154,12 @@ def merge_tile_results(results, grid: TileGrid, merge_threshold=(1, 2), return_i
     transitive.  Every output pixel shows the prediction of the tile that owns it (`grid.cuts_y`, `grid.cuts_x`),
     relabelled; an instance with no pixel in any owning cell is not reported.  `return_instance_stats=True` adds "area",
     "bbox" and "centroid" of the merged map's instances, as the post-processor does.  Four kernel calls, one host-to-device
-    and one device-to-host copy."""
+    and one device-to-host copy.
+
+    `clean=CleanOptions(...)` repairs the composed map as the post-processor's `clean=` does -- a
+    plant cut at a cell border can leave slivers that survive as pieces of the merged id: entries whose instance owns
+    no pixel afterwards are dropped, the rest renumbered 0 .. n'-1 in order, and the statistics are taken from the
+    cleaned map.  The new ids travel in the same device-to-host copy."""
     results = list(results)
     T = grid.n_tiles
     if len(results) != T:
@@ -168,6 +174,10 @@ def merge_tile_results(results, grid: TileGrid, merge_threshold=(1, 2), return_i
     num, den = (int(v) for v in merge_threshold)
     if num < 0 or den < 1:
         raise ValueError(f"merge_tile_results: merge_threshold (num, den) needs num >= 0 and den >= 1, got {(num, den)}")
+    if clean is not None:
+        from .instances import CleanOptions, cleaned_segments_info
+        if not isinstance(clean, CleanOptions):
+            raise TypeError(f"merge_tile_results: clean must be a CleanOptions or None, got {type(clean).__name__}")
     n_ids_h, labels_h = _tile_tables(results, T)
     N = int(labels_h.shape[1])
     tiles = torch.stack(maps)
@@ -186,13 +196,22 @@ def merge_tile_results(results, grid: TileGrid, merge_threshold=(1, 2), return_i
 
     back = [remap.reshape(-1).to(torch.int64), n_merged.to(torch.int64)]
     n_stats = min(int(n_ids_h.sum()), MAX_MERGED_IDS)  # an upper bound of n_merged known without a copy
+    cleaning = clean is not None and n_stats > 0
+    if cleaning:  # merged ids beyond n_stats (then merged_segments_info raises below) would count as background
+        cleaned, clean_stats, _ = ops.labelmap_clean(out.unsqueeze(0), n_stats, relabel=True, **clean.kernel_arguments())
+        out = cleaned[0]
+        back.append(clean_stats[0, :, 7])
     if return_instance_stats and n_stats:
         back.append(ops.labelmap_instance_stats(out.unsqueeze(0), N=n_stats).reshape(-1))
     host = torch.cat(back).cpu()  # the one device-to-host copy
     segments = merged_segments_info(host[:T * N].view(T, N).numpy(), int(host[T * N]), results)
+    rest = host[T * N + 1:]
+    if cleaning:
+        segments = cleaned_segments_info(segments, rest[:n_stats].numpy())
+        rest = rest[n_stats:]
     if return_instance_stats and segments:
         from .instances import stats_to_boxes
-        stats = host[T * N + 1:].view(-1, 8)[:len(segments)]
+        stats = rest.view(-1, 8)[:len(segments)]
         area, bbox, centroid = (v.tolist() for v in stats_to_boxes(stats))
         for k, info in enumerate(segments):
             info["area"] = area[k]
@@ -215,14 +234,15 @@ def _device_image(image) -> torch.Tensor:
 
 def segment_tiled(image, model, processor, tile: int = 1024, overlap: int = 256, batch_size: int = 4,
                   threshold: float = 0.5, mask_threshold: float = 0.5, overlap_mask_area_threshold: float = 0.8,
-                  merge_threshold=(1, 2), return_instance_stats: bool = False) -> dict:
+                  merge_threshold=(1, 2), return_instance_stats: bool = False, clean=None) -> dict:
     """Instance segmentation of an image of any size at native resolution: overlapping tiles (`tile_windows`), `batch_size`
     of them at a time through `processor(images=...)`, `model(pixel_values=...)` under no_grad and
     `processor.post_process_instance_segmentation(target_sizes=tile size)`, then `merge_tile_results`.  The image (PIL
     RGB, numpy or torch (H, W, 3) uint8) is moved to the device once and the tiles are slices of it.  An image no larger
     than one tile takes the same route with one tile.  `processor` is this package's `Mask2FormerImageProcessor` (or
     anything that takes a list of device uint8 (h, w, 3) tensors and post-processes into id maps on the device); it is
-    called with `images=` alone, so its own size settings decide how a tile is fed.  Returns `merge_tile_results`'s
+    called with `images=` alone, so its own size settings decide how a tile is fed.  `clean=CleanOptions(...)` repairs
+    the merged map (`merge_tile_results`); the tiles themselves are merged as predicted.  Returns `merge_tile_results`'s
     dictionary."""
     batch_size = int(batch_size)
     if batch_size < 1:
@@ -239,4 +259,5 @@ def segment_tiled(image, model, processor, tile: int = 1024, overlap: int = 256,
             results += processor.post_process_instance_segmentation(
                 outputs, threshold=threshold, mask_threshold=mask_threshold,
                 overlap_mask_area_threshold=overlap_mask_area_threshold, target_sizes=[(grid.th, grid.tw)] * len(batch))
-    return merge_tile_results(results, grid, merge_threshold=merge_threshold, return_instance_stats=return_instance_stats)
+    return merge_tile_results(results, grid, merge_threshold=merge_threshold, return_instance_stats=return_instance_stats,
+                              clean=clean)
