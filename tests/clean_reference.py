@@ -1,6 +1,8 @@
 """The contract of wm2f_labelmap_clean (include/wm2f.h) restated with numpy and scipy.ndimage: one
 `label` call per id with the 3 x 3 structure for the pieces, one with the default cross for the free components, the
 ring of a hole by one 4-neighbour dilation.  Also the generators the CPU and the GPU tests share."""
+import itertools
+
 import numpy as np
 from scipy import ndimage
 
@@ -225,3 +227,40 @@ def spiral(H, W, open_to_border=False):
     if open_to_border:
         m[1, W // 2] = -1
     return m
+
+
+def border_rule_map(c, o):
+    """A 96 x 96 map (3 x 3 tiles of 32) of the values 0-2 on which the merge rule across tile borders meets all 16
+    combinations of the four facts it reads, on the top border y = 32 and on the left border x = 64: the border pixel p
+    has value c, and of `chain` (the pixel before p along the border), `back`, `across` and `ahead` (the three pixels
+    across the border, in the border's direction) those of combination k have value c too, the others o."""
+    m = np.random.default_rng(0).integers(0, 3, (96, 96))
+    for k, (chain, back, across, ahead) in enumerate(itertools.product([0, 1], repeat=4)):
+        x = 4 * k + 2
+        m[31:33, x - 2:x + 3] = o
+        m[32, x] = c
+        for bit, at in ((chain, (32, x - 1)), (back, (31, x - 1)), (across, (31, x)), (ahead, (31, x + 1))):
+            if bit:
+                m[at] = c
+        y = 4 * k + 2
+        m[y - 2:y + 3, 63:65] = o
+        m[y, 64] = c
+        for bit, at in ((chain, (y - 1, 64)), (back, (y - 1, 63)), (across, (y, 63)), (ahead, (y + 1, 63))):
+            if bit:
+                m[at] = c
+    return m
+
+
+def border_rule_cases(m, c, tile=32):
+    """The distinct (chain, back, across, ahead) that pixels of value c show on tile top rows and on tile left columns
+    of m, as the merge kernels read them: chain only inside the pixel's own tile, back and ahead only inside the map."""
+    H, W = m.shape
+    top, left = set(), set()
+    for y, x in np.argwhere(m == c):
+        if y % tile == 0 and y > 0:
+            top.add((x % tile != 0 and m[y, x - 1] == c, x > 0 and m[y - 1, x - 1] == c, m[y - 1, x] == c,
+                     x + 1 < W and m[y - 1, x + 1] == c))
+        if x % tile == 0 and x > 0:
+            left.add((y % tile != 0 and m[y - 1, x] == c, y > 0 and m[y - 1, x - 1] == c, m[y, x - 1] == c,
+                      y + 1 < H and m[y + 1, x - 1] == c))
+    return top, left

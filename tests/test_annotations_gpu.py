@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+import clean_reference as R
 from test_annotations_cpu import restate_cc, restate_color, restate_resize, restate_semantic
 
 pytestmark = pytest.mark.gpu
@@ -82,6 +83,20 @@ def test_diagonals_through_tile_corners(A):
         sem[c + 8, c - 1] = sem[c + 7, c] = 3  # anti-diagonal pair across the column border
     got, d = _check_semantic(A, sem)
     assert len(d) == 9
+
+
+@pytest.mark.parametrize("c,o", [(1, 2), (1, 0)])
+def test_every_case_of_the_border_merge_rule(A, c, o):
+    """3 x 3 tiles on which border pixels of class c meet all 16 combinations of the four neighbour facts the merge rule
+    reads (previous pixel along the border, and the three across it), on a top border and on a left border."""
+    m = R.border_rule_map(c, o)
+    top, left = R.border_rule_cases(m, c)
+    assert len(top) == 16 and len(left) == 16  # a condition on the input
+    _check_semantic(A, m.astype(np.uint16))
+    binary = (m == c).astype(np.uint8)
+    n, lab = A.connected_components(_dev(binary))
+    exp_n, exp = restate_cc(binary)
+    assert n == exp_n and np.array_equal(lab.cpu().numpy(), exp)
 
 
 def test_serpentine_spans_many_tiles(A):

@@ -202,3 +202,10 @@ def test_the_gpu_tests_maps_exercise_every_branch(shape, dtype):
     plain = {}
     ref.run("all", 0, True, None, census=plain)
     assert plain["border"] >= 1 and plain["two_id"] >= 1
+
+
+@pytest.mark.parametrize("c,o", [(1, 2), (1, 0), (2, 0), (0, 1)])
+def test_the_border_rule_map_shows_every_case(c, o):
+    """The constructed map of the GPU tests holds all 16 combinations of the merge rule's four facts on both border kinds."""
+    top, left = R.border_rule_cases(R.border_rule_map(c, o), c)
+    assert len(top) == 16 and len(left) == 16

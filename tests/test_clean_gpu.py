@@ -73,6 +73,21 @@ def test_long_chains_across_tiles(kind):
     assert bool((got[0][0, 1:H - 1, 1:W - 1] == 0).all())
 
 
+@pytest.mark.parametrize("c,o", [(1, 2), (2, 0), (0, 1)])
+def test_every_case_of_the_border_merge_rule(c, o):
+    """3 x 3 tiles on which border pixels of value c meet all 16 combinations of the four neighbour facts the merge rule
+    reads, on a top border and on a left border.  The map minus one has the ids 0 and 1 and free pixels: (1, 2) and
+    (2, 0) put the pieces of an id there (next to another id, next to free pixels), (0, 1) the free components, whose
+    4-connected rule reads three of the four facts."""
+    from weed_instance_segmentation_amd import ops
+    m = R.border_rule_map(c, o)
+    top, left = R.border_rule_cases(m, c)
+    assert len(top) == 16 and len(left) == 16  # a condition on the input
+    maps = (m - 1).astype(np.int32)[None]
+    got = ops.labelmap_clean(torch.from_numpy(maps).to(DEV), 2, keep="all", fill_holes=True)
+    _check(got, R.clean(maps, 2, keep="all", fill_holes=True), ("border rule", c, o))
+
+
 def test_checkerboards():
     """Two ids on a checkerboard are one piece each under 8-connectivity.  On a checkerboard of one id and free pixels
     the id is one piece as well, and under 4-connectivity the free pixels do not join into a component that reaches the

@@ -1,11 +1,12 @@
 // Connected-component labelling of class maps with OpenCV's component numbering: the cv2 steps of
 // the reference's dataset loaders (datasets/pheno_bench/dataset.py:48-135, crop_weed dataset_from_png_annotations.py).
 //
-// Two pixels join when they are 8-neighbours and carry the same nonzero class.  Every phase is a lock-free union-find
-// whose union keeps the smaller root by atomicMin, so the root of a set is the smallest linear pixel index in it, and
-// the result does not depend on the schedule.  Phases are separate kernels (no inter-workgroup hand-off in a launch):
+// Two pixels join when they are 8-neighbours and carry the same nonzero class.  The union-find, the tile geometry and
+// the unions across tile borders are labelling.h's, which carries their arguments: the root of a set is the
+// smallest linear pixel index in it, whatever the schedule.  Phases are separate kernels (no inter-workgroup hand-off in
+// a launch):
 //   ccl_local_kernel     nearest resize + class mapping on load, union-find of one 32 x 32 tile in LDS;
-//   ccl_merge_kernel     unions across tile borders (corner diagonals included) on the global parent array;
+//   ccl_merge_kernel     labelling.h's merge step across tile borders (corner diagonals included);
 //   ccl_flatten_kernel   every tile root points at its final root (so the per-pixel pass below takes two hops, not a
 //                        walk along a chain of tiles);
 //   ccl_finalize_kernel  every pixel points at its root; the first 2 x 2 block of each component (atomicMin at its
@@ -15,13 +16,11 @@
 //   ccl_paint_kernel     out[p] = id[root(p)], or the background value.
 // wm2f_resize_nearest is the plain nearest resize (cv2.resize INTER_NEAREST) through the same index tables.
 #include "common.h"
+#include "labelling.h"
 
 namespace wm2f {
 namespace {
 
-constexpr int kTile = 32;                       // tile side of the local phase
-constexpr int kLocalThreads = 256;              // 4 rows of the tile per thread
-constexpr int kRowsPerThread = kTile * kTile / kLocalThreads;
 constexpr int kThreads = 256;
 
 struct Colors {
@@ -64,54 +63,21 @@ __device__ __forceinline__ int load_class(const T* __restrict__ src, int src_H, 
   }
 }
 
-// Lock-free union-find with atomicMin: parent[x] <= x always holds, so find() terminates and a root is the smallest
-// index of its set.  When the atomicMin meets a root that has just been linked elsewhere (old != b), the loop goes on
-// with that old parent, so the earlier link is never lost.
-template <int kScope>
-__device__ __forceinline__ int find_root(int32_t* parent, int x) {
-  int p = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, kScope);
-  while (p != x) {
-    x = p;
-    p = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, kScope);
-  }
-  return x;
-}
-
-template <int kScope>
-__device__ __forceinline__ void unite(int32_t* parent, int a, int b) {
-  for (;;) {
-    a = find_root<kScope>(parent, a);
-    b = find_root<kScope>(parent, b);
-    if (a == b) return;
-    if (a > b) {
-      const int t = a;
-      a = b;
-      b = t;
-    }
-    const int old = __hip_atomic_fetch_min(parent + b, a, __ATOMIC_RELAXED, kScope);
-    if (old == b) return;
-    b = old;
-  }
-}
-
 // Local phase: one workgroup per 32 x 32 tile.  Loads (and resizes / classifies) the tile, writes the class map, joins
-// 8-neighbours inside the tile in LDS and writes every pixel's tile-local root as a global linear index (the order of
-// local and global indices agrees inside a tile, so the minimum is kept).  Background pixels point at themselves.
+// 8-neighbours inside the tile in LDS and writes every pixel's tile-local root as a global linear index.  Background
+// pixels, and those outside the map (class 0 there too), point at themselves.
 template <typename T, int kMode>
-__global__ __launch_bounds__(kLocalThreads) void ccl_local_kernel(const T* __restrict__ src, int src_H, int src_W,
+__global__ __launch_bounds__(kLabelThreads) void ccl_local_kernel(const T* __restrict__ src, int src_H, int src_W,
                                                                   const int32_t* __restrict__ ty,
                                                                   const int32_t* __restrict__ tx, int H, int W, Ws ws,
                                                                   const Colors colors) {
-  __shared__ int32_t s_parent[kTile * kTile];
-  __shared__ int32_t s_cls[kTile * kTile];
-  const int x0 = blockIdx.x * kTile, y0 = blockIdx.y * kTile;
-  const int lx = threadIdx.x % kTile, ly0 = threadIdx.x / kTile;
-  const int x = x0 + lx;
+  __shared__ int32_t s_parent[kLabelTilePx];
+  __shared__ int32_t s_cls[kLabelTilePx];
+  const int x0 = blockIdx.x * kLabelTile, y0 = blockIdx.y * kLabelTile;
 #pragma unroll
-  for (int k = 0; k < kRowsPerThread; ++k) {
-    const int ly = ly0 + k * (kLocalThreads / kTile);
-    const int y = y0 + ly;
-    const int li = ly * kTile + lx;
+  for (int k = 0; k < kLabelRows; ++k) {
+    const auto [lx, ly, li] = tile_pixel(k);
+    const int y = y0 + ly, x = x0 + lx;
     int c = 0;
     if (y < H && x < W) {
       c = load_class<T, kMode>(src, src_H, src_W, ty, tx, y, x, colors);
@@ -122,72 +88,37 @@ __global__ __launch_bounds__(kLocalThreads) void ccl_local_kernel(const T* __res
   }
   __syncthreads();
 #pragma unroll
-  for (int k = 0; k < kRowsPerThread; ++k) {
-    const int ly = ly0 + k * (kLocalThreads / kTile);
-    const int li = ly * kTile + lx;
+  for (int k = 0; k < kLabelRows; ++k) {
+    const auto [lx, ly, li] = tile_pixel(k);
     const int c = s_cls[li];
     if (c == 0) continue;  // background, or outside the map (class 0 there too)
-    if (lx > 0 && s_cls[li - 1] == c) unite<__HIP_MEMORY_SCOPE_WORKGROUP>(s_parent, li, li - 1);
+    constexpr int kS = __HIP_MEMORY_SCOPE_WORKGROUP;
+    if (lx > 0 && s_cls[li - 1] == c) unite<kS>(s_parent, li, li - 1);
     if (ly > 0) {
-      if (lx > 0 && s_cls[li - kTile - 1] == c) unite<__HIP_MEMORY_SCOPE_WORKGROUP>(s_parent, li, li - kTile - 1);
-      if (s_cls[li - kTile] == c) unite<__HIP_MEMORY_SCOPE_WORKGROUP>(s_parent, li, li - kTile);
-      if (lx < kTile - 1 && s_cls[li - kTile + 1] == c) unite<__HIP_MEMORY_SCOPE_WORKGROUP>(s_parent, li, li - kTile + 1);
+      if (lx > 0 && s_cls[li - kLabelTile - 1] == c) unite<kS>(s_parent, li, li - kLabelTile - 1);
+      if (s_cls[li - kLabelTile] == c) unite<kS>(s_parent, li, li - kLabelTile);
+      if (lx < kLabelTile - 1 && s_cls[li - kLabelTile + 1] == c) unite<kS>(s_parent, li, li - kLabelTile + 1);
     }
   }
   __syncthreads();
 #pragma unroll
-  for (int k = 0; k < kRowsPerThread; ++k) {
-    const int ly = ly0 + k * (kLocalThreads / kTile);
-    const int y = y0 + ly;
+  for (int k = 0; k < kLabelRows; ++k) {
+    const auto [lx, ly, li] = tile_pixel(k);
+    const int y = y0 + ly, x = x0 + lx;
     if (y >= H || x >= W) continue;
-    const int li = ly * kTile + lx;
     const int r = find_root<__HIP_MEMORY_SCOPE_WORKGROUP>(s_parent, li);
-    const int g = (y0 + r / kTile) * W + x0 + r % kTile;
+    const int g = tile_to_image(r, y0, x0, W);
     ws.parent[(int64_t)y * W + x] = g;
     if (r == li && s_cls[li] != 0) ws.roots[atomicAdd(ws.n_tile_roots, 1)] = g;
   }
 }
 
 // Merge phase: one thread per pixel on the top row or the left column of a tile (other than the map's own edge), joined
-// with its 8-neighbours in the tile above or to the left.  The top row takes the three pixels above it (NE covers the
-// corner diagonal towards the tile up and to the right); the left column takes the three to its left.  A union that the
-// previous pixel q along the border already implies is skipped when q lies in p's tile: p and q are joined there, and
-// their neighbours across the border lie in one tile too, so one union per run of same-class pixels suffices.
-__global__ __launch_bounds__(kThreads) void ccl_merge_kernel(int H, int W, int n_rows, Ws ws) {
-  const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  const int64_t n_row_px = (int64_t)n_rows * W;
-  int y, x;
-  bool top;
-  if (t < n_row_px) {
-    y = (int)(t / W + 1) * kTile;
-    x = (int)(t % W);
-    top = true;
-  } else {
-    const int64_t u = t - n_row_px;
-    const int n_cols = ceil_div(W, kTile) - 1;
-    if (u >= (int64_t)n_cols * H) return;
-    x = (int)(u / H + 1) * kTile;
-    y = (int)(u % H);
-    top = false;
-  }
-  const int p = y * W + x;
-  const int c = ws.cls[p];
-  if (c == 0) return;
-  // across: the neighbour straight across the border; back / ahead: the diagonal ones before and after it along the
-  // border.  `chain`: the previous pixel along the border has class c and lies in this tile (joined to p by the local
-  // phase; its own neighbours across then lie in one tile too), so its unions stand for p's.  Inside one tile's border
-  // segment the chain ends at the segment's first pixel, which never skips.
-  const int step = top ? 1 : W;            // along the border
-  const int across = top ? p - W : p - 1;  // across the border
-  const int pos = top ? x : y, len = top ? W : H;
-  const bool chain = pos % kTile != 0 && ws.cls[p - step] == c;
-  const bool back_same = pos > 0 && ws.cls[across - step] == c;
-  if (ws.cls[across] == c) {
-    if (!(chain && back_same)) unite<__HIP_MEMORY_SCOPE_AGENT>(ws.parent, p, across);
-  } else {
-    if (back_same && !chain) unite<__HIP_MEMORY_SCOPE_AGENT>(ws.parent, p, across - step);
-    if (pos + 1 < len && ws.cls[across + step] == c) unite<__HIP_MEMORY_SCOPE_AGENT>(ws.parent, p, across + step);
-  }
+// with its 8-neighbours of the same class in the tile above or to the left by labelling.h's rule.
+__global__ __launch_bounds__(kThreads) void ccl_merge_kernel(int H, int W, Ws ws) {
+  BorderPixel b;
+  if (!border_pixel((int64_t)blockIdx.x * kThreads + threadIdx.x, H, W, b)) return;
+  border_unite<8>(ws.cls, ws.parent, H, W, b, [](int c) { return c != 0; });
 }
 
 // Every tile root (listed by the local phase) points at its final root; roots are final once the merge kernel has
@@ -261,8 +192,8 @@ __global__ __launch_bounds__(kThreads) void resize_nearest_kernel(const Px<kByte
 template <typename T, int kMode>
 void launch_local(const void* src, int src_H, int src_W, const int32_t* ty, const int32_t* tx, int H, int W, const Ws& ws,
                   const Colors& colors, hipStream_t s) {
-  const dim3 grid((unsigned)ceil_div(W, kTile), (unsigned)ceil_div(H, kTile));
-  hipLaunchKernelGGL((ccl_local_kernel<T, kMode>), grid, dim3(kLocalThreads), 0, s, (const T*)src, src_H, src_W, ty, tx,
+  const dim3 grid((unsigned)ceil_div(W, kLabelTile), (unsigned)ceil_div(H, kLabelTile));
+  hipLaunchKernelGGL((ccl_local_kernel<T, kMode>), grid, dim3(kLabelThreads), 0, s, (const T*)src, src_H, src_W, ty, tx,
                      H, W, ws, colors);
 }
 
@@ -328,11 +259,10 @@ extern "C" int wm2f_ccl_label(const void* src, int mode, int src_dtype, int src_
   else
     launch_local<int32_t, WM2F_CCL_BINARY>(src, src_H, src_W, ty, tx, H, W, ws, cl, s);
   WM2F_CHECK_LAUNCH(who);
-  const int n_rows = ceil_div(H, kTile) - 1, n_cols = ceil_div(W, kTile) - 1;
-  const int64_t n_border = (int64_t)n_rows * W + (int64_t)n_cols * H;
+  const int64_t n_border = border_count(H, W).n_border;
   if (n_border > 0) {
     hipLaunchKernelGGL(ccl_merge_kernel, dim3((unsigned)ceil_div64(n_border, kThreads)), dim3(kThreads), 0, s, H, W,
-                       n_rows, ws);
+                       ws);
     WM2F_CHECK_LAUNCH(who);
     hipLaunchKernelGGL(ccl_flatten_kernel, dim3((unsigned)ceil_div64(n_px, kThreads)), dim3(kThreads), 0, s, n_px, ws);
     WM2F_CHECK_LAUNCH(who);

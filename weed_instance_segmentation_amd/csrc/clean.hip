@@ -6,13 +6,14 @@
 // One labelling, written once as a template over two modes, runs twice:
 //   kPieces  pixels with an id, joined when 8-neighbours of equal id   (on the decoded map)
 //   kFree    pixels without an id, joined when 4-neighbours            (on the map after the pieces were chosen)
-// It is a lock-free union-find whose union links the larger root under the smaller by atomicMin, so the root of a set is
-// its smallest linear pixel index -- the piece's "first pixel" -- whatever the schedule.  Phases that need every
-// workgroup of the one before are separate launches; nothing polls or waits across workgroups:
+// Its union-find, tile geometry and unions across tile borders are labelling.h's, which carries their arguments and
+// loop bounds: the root of a set is its smallest linear pixel index -- the piece's "first pixel" -- whatever the
+// schedule.  Phases that need every workgroup of the one before are separate launches; nothing polls or waits across
+// workgroups:
 //   clean_init     stats and best <- 0
 //   clean_local    a 32 x 32 tile per workgroup: union-find in LDS, then per TILE root in LDS its pixel count (and in
 //                  kFree a border flag and the min / max of the 4-adjacent ids); written at the tile root's pixel
-//   clean_merge    unions across tile borders on the global parents (device-scope atomicMin)
+//   clean_merge    labelling.h's merge step across tile borders on the global parents
 //   clean_flatten  every tile root points at its final root and adds its tile's count (flag, min, max) there: one
 //                  integer atomic per (tile, tile root), never one per pixel
 //   clean_best     per final piece of id k: area_in, pieces_in, and one 64-bit atomicMax of
@@ -24,23 +25,16 @@
 //   clean_paint    out[p] = table[id of p, or of the hole p lies in], -1 when free
 // Everything is integer and every accumulation is an integer atomic: the result does not depend on the schedule.
 //
-// Loop bounds.  parent[x] <= x always holds (a parent is only ever lowered), so a find follows strictly decreasing
-// indices: at most 1023 steps in a tile, at most H * W - 1 on the global array.  A union retries only after its
-// atomicMin found the root already linked elsewhere, i.e. after that parent was lowered by another thread; every retry
-// continues from a strictly smaller index, so it ends after at most as many rounds as the index has predecessors.
 // No loop depends on a map value: a value is decoded to an id in [0, N) or to "free" before anything indexes with it.
 #include <type_traits>
 
 #include "common.h"
+#include "labelling.h"
 
 namespace wm2f {
 namespace {
 
-constexpr int kClTile = 32;                                   // tile side of the local phase
-constexpr int kClTilePx = kClTile * kClTile;
 constexpr int kClThreads = 256;
-constexpr int kClRows = kClTilePx / kClThreads;               // pixels of a tile per thread, kClThreads / kClTile rows apart
-constexpr int kClRowStep = kClThreads / kClTile;
 constexpr int kClMaxSide = 16384;
 constexpr int kClMaxBatch = 32;
 constexpr int kClMaxIds = 4096;
@@ -51,6 +45,8 @@ constexpr int kClNoId = 0x7fffffff;                           // min of no 4-adj
 constexpr int kClOutside = -2;                                // LDS key of a tile pixel beyond the image
 
 enum { kPieces = 0, kFree = 1 };
+template <int kMode>
+constexpr int kModeConn = kMode == kPieces ? 8 : 4;  // pieces are 8-connected, free components 4-connected
 
 // Workspace carve (include/wm2f.h).  Per image: best (N) and the id table (N); per pixel: the id (-1 free), the
 // union-find parent as a linear index inside the image, and at root pixels the count (kFree: | kClBorder) and the
@@ -98,36 +94,6 @@ __device__ __forceinline__ bool is_active(int key) {
   return kMode == kPieces ? key >= 0 : key == -1;
 }
 
-// at most x steps: parents strictly decrease
-template <int kScope>
-__device__ __forceinline__ int find_root(int32_t* parent, int x) {
-  int p = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, kScope);
-  while (p != x) {
-    x = p;
-    p = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, kScope);
-  }
-  return x;
-}
-
-// links the larger root under the smaller; a failed atomicMin (the root was linked elsewhere meanwhile) goes on from the
-// parent it found, which is smaller than the root it tried: at most max(a, b) rounds
-template <int kScope>
-__device__ __forceinline__ void unite(int32_t* parent, int a, int b) {
-  for (;;) {
-    a = find_root<kScope>(parent, a);
-    b = find_root<kScope>(parent, b);
-    if (a == b) return;
-    if (a > b) {
-      const int t = a;
-      a = b;
-      b = t;
-    }
-    const int old = __hip_atomic_fetch_min(parent + b, a, __ATOMIC_RELAXED, kScope);
-    if (old == b) return;
-    b = old;
-  }
-}
-
 // the id a free component is a hole of, -1 for none: no border flag, one id around it, and not above the limit
 __device__ __forceinline__ int hole_of(uint32_t area, int lo, int hi, long long max_hole) {
   if (area & kClBorder) return -1;
@@ -148,28 +114,25 @@ __global__ __launch_bounds__(kClThreads) void clean_init_kernel(long long* __res
 
 // Local phase: grid (tiles_x, tiles_y, B), a workgroup per 32 x 32 tile.  kPieces decodes the map (dtype DT) and writes
 // the id of every pixel; kFree reads those ids back.  Writes for every pixel of the image its tile-local root as a
-// linear index of the image (the order of local and image indices agrees inside a tile, so the minimum is kept; a
-// pixel that is not active points at itself), and at every pixel its tile's count if it is a tile root, 0 otherwise.
+// linear index of the image (a pixel that is not active points at itself), and at every pixel its tile's count if it is
+// a tile root, 0 otherwise.
 template <int kMode, int DT>
-__global__ __launch_bounds__(kClThreads) void clean_local_kernel(const void* __restrict__ map, ClWs ws, int H, int W,
+__global__ __launch_bounds__(kLabelThreads) void clean_local_kernel(const void* __restrict__ map, ClWs ws, int H, int W,
                                                                  int N) {
   using E = typename std::conditional<DT == WM2F_U8, uint8_t, uint32_t>::type;
-  constexpr int kAux = kMode == kFree ? kClTilePx : 1;
-  __shared__ int32_t s_parent[kClTilePx];
-  __shared__ int32_t s_key[kClTilePx];
-  __shared__ uint32_t s_cnt[kClTilePx];
+  constexpr int kAux = kMode == kFree ? kLabelTilePx : 1;
+  __shared__ int32_t s_parent[kLabelTilePx];
+  __shared__ int32_t s_key[kLabelTilePx];
+  __shared__ uint32_t s_cnt[kLabelTilePx];
   __shared__ int32_t s_lo[kAux];
   __shared__ int32_t s_hi[kAux];
-  const int x0 = blockIdx.x * kClTile, y0 = blockIdx.y * kClTile;
+  const int x0 = blockIdx.x * kLabelTile, y0 = blockIdx.y * kLabelTile;
   const int64_t img = (int64_t)blockIdx.z * H * W;
-  const int lx = threadIdx.x % kClTile, ly0 = threadIdx.x / kClTile;
-  const int x = x0 + lx;
   int32_t* key = ws.key + img;
 #pragma unroll
-  for (int k = 0; k < kClRows; ++k) {
-    const int ly = ly0 + k * kClRowStep;
-    const int y = y0 + ly;
-    const int li = ly * kClTile + lx;
+  for (int k = 0; k < kLabelRows; ++k) {
+    const auto [lx, ly, li] = tile_pixel(k);
+    const int y = y0 + ly, x = x0 + lx;
     int c = kClOutside;
     if (y < H && x < W) {
       const int64_t p = (int64_t)y * W + x;
@@ -189,30 +152,30 @@ __global__ __launch_bounds__(kClThreads) void clean_local_kernel(const void* __r
     }
   }
   __syncthreads();
+  // the neighbour loop stays in the kernel: through a function shared with ccl.hip the kFree instance measured about
+  // 1 % slower at B = 8
 #pragma unroll
-  for (int k = 0; k < kClRows; ++k) {
-    const int ly = ly0 + k * kClRowStep;
-    const int li = ly * kClTile + lx;
+  for (int k = 0; k < kLabelRows; ++k) {
+    const auto [lx, ly, li] = tile_pixel(k);
     const int c = s_key[li];
     if (!is_active<kMode>(c)) continue;
     constexpr int kS = __HIP_MEMORY_SCOPE_WORKGROUP;
     if (lx > 0 && s_key[li - 1] == c) unite<kS>(s_parent, li, li - 1);
     if (ly > 0) {
-      if (s_key[li - kClTile] == c) unite<kS>(s_parent, li, li - kClTile);
+      if (s_key[li - kLabelTile] == c) unite<kS>(s_parent, li, li - kLabelTile);
       if constexpr (kMode == kPieces) {
-        if (lx > 0 && s_key[li - kClTile - 1] == c) unite<kS>(s_parent, li, li - kClTile - 1);
-        if (lx < kClTile - 1 && s_key[li - kClTile + 1] == c) unite<kS>(s_parent, li, li - kClTile + 1);
+        if (lx > 0 && s_key[li - kLabelTile - 1] == c) unite<kS>(s_parent, li, li - kLabelTile - 1);
+        if (lx < kLabelTile - 1 && s_key[li - kLabelTile + 1] == c) unite<kS>(s_parent, li, li - kLabelTile + 1);
       }
     }
   }
   __syncthreads();
-  int root[kClRows];
+  int root[kLabelRows];
   const int lane = threadIdx.x & 63;
 #pragma unroll
-  for (int k = 0; k < kClRows; ++k) {
-    const int ly = ly0 + k * kClRowStep;
-    [[maybe_unused]] const int y = y0 + ly;
-    const int li = ly * kClTile + lx;
+  for (int k = 0; k < kLabelRows; ++k) {
+    const auto [lx, ly, li] = tile_pixel(k);
+    [[maybe_unused]] const int y = y0 + ly, x = x0 + lx;
     const bool act = is_active<kMode>(s_key[li]);
     const int r = act ? find_root<__HIP_MEMORY_SCOPE_WORKGROUP>(s_parent, li) : -1;
     root[k] = r;
@@ -234,9 +197,9 @@ __global__ __launch_bounds__(kClThreads) void clean_local_kernel(const void* __r
       const int64_t p = (int64_t)y * W + x;
       int nk[4];
       nk[0] = x > 0 ? (lx > 0 ? s_key[li - 1] : key[p - 1]) : -1;
-      nk[1] = x + 1 < W ? (lx < kClTile - 1 ? s_key[li + 1] : key[p + 1]) : -1;
-      nk[2] = y > 0 ? (ly > 0 ? s_key[li - kClTile] : key[p - W]) : -1;
-      nk[3] = y + 1 < H ? (ly < kClTile - 1 ? s_key[li + kClTile] : key[p + W]) : -1;
+      nk[1] = x + 1 < W ? (lx < kLabelTile - 1 ? s_key[li + 1] : key[p + 1]) : -1;
+      nk[2] = y > 0 ? (ly > 0 ? s_key[li - kLabelTile] : key[p - W]) : -1;
+      nk[3] = y + 1 < H ? (ly < kLabelTile - 1 ? s_key[li + kLabelTile] : key[p + W]) : -1;
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         if (nk[j] >= 0) {
@@ -247,15 +210,14 @@ __global__ __launch_bounds__(kClThreads) void clean_local_kernel(const void* __r
   }
   __syncthreads();
 #pragma unroll
-  for (int k = 0; k < kClRows; ++k) {
-    const int ly = ly0 + k * kClRowStep;
-    const int y = y0 + ly;
+  for (int k = 0; k < kLabelRows; ++k) {
+    const auto [lx, ly, li] = tile_pixel(k);
+    const int y = y0 + ly, x = x0 + lx;
     if (y >= H || x >= W) continue;
-    const int li = ly * kClTile + lx;
     const int64_t p = (int64_t)y * W + x;
     const int r = root[k];
     const bool is_root = r == li;
-    ws.parent[img + p] = r < 0 ? (int)p : (y0 + r / kClTile) * W + x0 + r % kClTile;
+    ws.parent[img + p] = r < 0 ? (int)p : tile_to_image(r, y0, x0, W);
     ws.area[img + p] = is_root ? s_cnt[li] : 0u;
     if constexpr (kMode == kFree) {
       ws.lo[img + p] = is_root ? s_lo[li] : kClNoId;
@@ -265,49 +227,16 @@ __global__ __launch_bounds__(kClThreads) void clean_local_kernel(const void* __r
 }
 
 // Merge phase: grid (ceil(n_border / 256), B), a thread per pixel on the top row or the left column of a tile (other than
-// the image's own edge), joined with its neighbours across that border.  kPieces: when the pixel straight across has
-// the same id, that one union stands for the two diagonal ones as well (the diagonal pixels are its neighbours along
-// the border, joined to it by their own tile or by their own border); otherwise the two diagonals are tried.  kFree:
-// the pixel straight across only.  (Measured on a 1024 x 1024 map whose background is one free component: one union
-// per border pixel kept this launch at 0.10 ms, 62k unions walking to one root; one per run is what is left.)
+// the image's own edge), joined with its neighbours across that border by labelling.h's rule, which makes one union per
+// run of pixels.  (Measured on a 1024 x 1024 map whose background is one free component: one union per border pixel
+// kept this launch at 0.10 ms, 62k unions walking to one root; one per run is what is left.)
 template <int kMode>
-__global__ __launch_bounds__(kClThreads) void clean_merge_kernel(ClWs ws, int H, int W, int n_rows) {
-  const int64_t t = (int64_t)blockIdx.x * kClThreads + threadIdx.x;
-  const int64_t n_row_px = (int64_t)n_rows * W;
-  int y, x;
-  bool top;
-  if (t < n_row_px) {
-    y = (int)(t / W + 1) * kClTile;
-    x = (int)(t % W);
-    top = true;
-  } else {
-    const int64_t u = t - n_row_px;
-    const int n_cols = ceil_div(W, kClTile) - 1;
-    if (u >= (int64_t)n_cols * H) return;
-    x = (int)(u / H + 1) * kClTile;
-    y = (int)(u % H);
-    top = false;
-  }
+__global__ __launch_bounds__(kClThreads) void clean_merge_kernel(ClWs ws, int H, int W) {
+  BorderPixel b;
+  if (!border_pixel((int64_t)blockIdx.x * kClThreads + threadIdx.x, H, W, b)) return;
   const int64_t img = (int64_t)blockIdx.y * H * W;
-  const int32_t* key = ws.key + img;
-  int32_t* parent = ws.parent + img;
-  const int p = y * W + x;
-  const int c = key[p];
-  if (!is_active<kMode>(c)) return;
-  constexpr int kS = __HIP_MEMORY_SCOPE_AGENT;
-  const int step = top ? 1 : W;            // along the border
-  const int across = top ? p - W : p - 1;  // across the border
-  const int pos = top ? x : y, len = top ? W : H;
-  if (key[across] == c) {
-    // inside one tile's border segment a run of pixels with runs of the same id across needs one union: p and the
-    // pixel before it are joined by their tile, the two across by theirs, and the pixel before p makes (or, by the
-    // same rule, inherits from the segment's first pixel, which never skips) the union of the two runs
-    const bool inherited = pos % kClTile != 0 && key[p - step] == c && key[across - step] == c;
-    if (!inherited) unite<kS>(parent, p, across);
-  } else if (kMode == kPieces) {
-    if (pos > 0 && key[across - step] == c) unite<kS>(parent, p, across - step);
-    if (pos + 1 < len && key[across + step] == c) unite<kS>(parent, p, across + step);
-  }
+  border_unite<kModeConn<kMode>>(ws.key + img, ws.parent + img, H, W, b,
+                                 [](int k) { return is_active<kMode>(k); });
 }
 
 // Flatten phase: grid (ceil(H * W / 256), B), a thread per pixel; only tile roots (count != 0) do anything.  Roots are
@@ -500,14 +429,13 @@ __global__ __launch_bounds__(kClThreads) void clean_paint_kernel(ClWs ws, O* __r
 
 template <int kMode, int DT>
 void launch_labelling(const void* map, const ClWs& ws, int B, int H, int W, int N, hipStream_t s) {
-  const dim3 tiles((unsigned)ceil_div(W, kClTile), (unsigned)ceil_div(H, kClTile), (unsigned)B);
-  hipLaunchKernelGGL((clean_local_kernel<kMode, DT>), tiles, dim3(kClThreads), 0, s, map, ws, H, W, N);
+  const dim3 tiles((unsigned)ceil_div(W, kLabelTile), (unsigned)ceil_div(H, kLabelTile), (unsigned)B);
+  hipLaunchKernelGGL((clean_local_kernel<kMode, DT>), tiles, dim3(kLabelThreads), 0, s, map, ws, H, W, N);
   // the merge and flatten launches are part of the chain at every size: a map of one tile runs them over nothing
-  const int n_rows = ceil_div(H, kClTile) - 1, n_cols = ceil_div(W, kClTile) - 1;
-  const int64_t n_border = (int64_t)n_rows * W + (int64_t)n_cols * H;
+  const int64_t n_border = border_count(H, W).n_border;
   const int n_px = H * W;
   hipLaunchKernelGGL((clean_merge_kernel<kMode>), dim3((unsigned)(n_border > 0 ? ceil_div64(n_border, kClThreads) : 1), (unsigned)B),
-                     dim3(kClThreads), 0, s, ws, H, W, n_rows);
+                     dim3(kClThreads), 0, s, ws, H, W);
   hipLaunchKernelGGL((clean_flatten_kernel<kMode>), dim3((unsigned)ceil_div(n_px, kClThreads), (unsigned)B),
                      dim3(kClThreads), 0, s, ws, n_px);
 }

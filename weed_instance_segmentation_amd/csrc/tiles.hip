@@ -5,13 +5,14 @@
 //                  the tiles read in place.  labelmap_pairs_kernel's fast path (coco_eval.hip): a wave inside one id pair
 //                  adds its ballot count once, the (none, none) bin is counted once per workgroup.
 //   tile_owned   : pixels of every id inside its tile's own cell.
-//   tile_link    : every bin of every pair against the link rule, lock-free union by atomicMin (ccl.hip: the root of a
-//                  set is its smallest node, whatever the arrival order); then, each its own launch: flatten and mark
+//   tile_link    : every bin of every pair against the link rule, labelling.h's lock-free union (the root of a set
+//                  is its smallest node, whatever the arrival order); then, each its own launch: flatten and mark
 //                  the sets that own a pixel, number the surviving roots in ascending order by a scan, write remap.
 //   tile_compose : out = remap[owner tile][local id], one workgroup per strip of rows of one cell.
 // All integer; no float takes part; every result is independent of the schedule.  Every index read from a device table
 // is clamped to the array it addresses before use.
 #include "common.h"
+#include "labelling.h"
 
 namespace wm2f {
 namespace {
@@ -258,33 +259,8 @@ __global__ __launch_bounds__(kTmThreads) void tile_compose_kernel(const uint32_t
   }
 }
 
-// ---- linking: union-find over the nodes g = t * N + i (ccl.hip's lock-free form) --------------------------------------
-__device__ __forceinline__ int find_root(int32_t* parent, int x) {
-  int p = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  while (p != x) {
-    x = p;
-    p = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  return x;
-}
-
-// parent[x] <= x always, so find_root terminates and a root is the smallest node of its set.  When the atomicMin meets
-// a root that has just been linked elsewhere (old != b), the loop goes on with that old parent: no link is lost.
-__device__ __forceinline__ void unite(int32_t* parent, int a, int b) {
-  for (;;) {
-    a = find_root(parent, a);
-    b = find_root(parent, b);
-    if (a == b) return;
-    if (a > b) {
-      const int t = a;
-      a = b;
-      b = t;
-    }
-    const int old = __hip_atomic_fetch_min(parent + b, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == b) return;
-    b = old;
-  }
-}
+// ---- linking: labelling.h's union-find over the nodes g = t * N + i, at device scope  -------------------------------
+constexpr int kTmScope = __HIP_MEMORY_SCOPE_AGENT;
 
 struct LinkWs {
   int32_t* parent;  // (M) union-find forest
@@ -340,7 +316,7 @@ __global__ __launch_bounds__(kTmThreads) void tile_link_kernel(const int32_t* __
     const int inter = hp[(i + 1) * NB + j + 1];
     if (inter <= 0 || la[i] != lb[j]) continue;
     const int smaller = imin(area_a[i + 1], area_b[j + 1]);
-    if ((int64_t)inter * den >= (int64_t)num * smaller) unite(ws.parent, a * N + i, b * N + j);
+    if ((int64_t)inter * den >= (int64_t)num * smaller) unite<kTmScope>(ws.parent, a * N + i, b * N + j);
   }
 }
 
@@ -349,7 +325,7 @@ __global__ __launch_bounds__(kTmThreads) void tile_flatten_kernel(const int32_t*
                                                                  int N) {
   const int g = blockIdx.x * kTmThreads + threadIdx.x;
   if (g >= M) return;
-  const int r = find_root(ws.parent, g);
+  const int r = find_root<kTmScope>(ws.parent, g);
   ws.root[g] = r;
   const int t = g / N, i = g - t * N;
   if (i < clamp_n(n_ids[t], N) && owned[g] > 0) atomicOr(ws.owns + r, 1);
