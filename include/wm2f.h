@@ -466,6 +466,30 @@ int wm2f_conv3x3_split_fwd(const void* x, const void* w_split, const void* bias,
                            int Wi, int stride, int relu, int config, void* stream);
 int wm2f_conv3x3_split_config(int N, int P, int B, int n_cu);
 
+/* GroupNorm folded into the convolutions around it (inference).  `out` of each is bit for bit what the entry
+ * point above stores, under every config; only the statistics carry the ordering freedom of their fp64 atomics.
+ * wm2f_conv1x1_split_gn_fwd: wm2f_conv1x1_split_fwd (epilogue none or + bias) with one of
+ *     stats_out != NULL: stats_out[(b * G_out + g) * 2 + {0, 1}] = (sum, sum of squares) of out over group g of image b --
+ *                        the workspace of wm2f_group_norm_act / wm2f_group_norm_tokens, zeroed here on the stream and
+ *                        filled from the epilogue.  N / G_out in {4, 8, 16}; any other group size is refused before
+ *                        anything is launched (the caller keeps the separate statistics pass).
+ *     norm_stats != NULL: x is read as act(GroupNorm_{norm_G}(x) * norm_gamma + norm_beta) from the FILLED workspace
+ *                        norm_stats of x, act = max(., 0) if norm_relu -- the bits wm2f_group_norm_act_apply would have
+ *                        written.  Needs bias, stride 1, K <= 2048.  The two together are not built.
+ * wm2f_conv3x3_split_stats_fwd: wm2f_conv3x3_split_fwd without bias, plus stats_out as above.
+ * wm2f_group_norm_act_apply, wm2f_group_norm_tokens_apply: wm2f_group_norm_act / wm2f_group_norm_tokens from a filled
+ *                        workspace `stats` (of x, resp. of x + bias): no statistics pass.  wm2f_group_norm_act_apply
+ *                        without `up` takes any W (W % 4 != 0: one element per thread, the same bits per element). */
+int wm2f_conv1x1_split_gn_fwd(const void* x, const void* w_split, const void* bias, void* out, void* stats_out, int G_out,
+                              const void* norm_stats, const void* norm_gamma, const void* norm_beta, int norm_G, float norm_eps,
+                              int norm_relu, int B, int K, int N, int Hi, int Wi, int stride, int config, void* stream);
+int wm2f_conv3x3_split_stats_fwd(const void* x, const void* w_split, void* out, void* stats_out, int G_out, int B, int Cin,
+                                 int N, int Hi, int Wi, int stride, int config, void* stream);
+int wm2f_group_norm_act_apply(const void* x, const void* gamma, const void* beta, const void* up, void* y, const void* stats,
+                              int B, int C, int G, int H, int W, int Hs, int Ws, float eps, int relu, void* stream);
+int wm2f_group_norm_tokens_apply(const void* x, const void* bias, const void* gamma, const void* beta, void* tokens,
+                                 const void* stats, int B, int C, int G, int HW, int S, int start, float eps, void* stream);
+
 /* wm2f_stem7x7_pool_fwd: the ResNet stem in one kernel, NCHW fp32, at fp32 accuracy on the bf16 matrix cores (the split
  *                        arithmetic of wm2f_conv1x1_split_fwd):  out (B, N, Hp, Wp) = MaxPool2d(3, stride 2,
  *                        pad 1)(ReLU(conv7x7(x (B, Cin, Hi, Wi), W (N, Cin, 7, 7), stride 2, pad 3) + bias[N])),

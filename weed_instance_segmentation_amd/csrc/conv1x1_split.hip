@@ -21,7 +21,13 @@
 //     by the host (fewest workgroup rounds on the device, weighted by the wave's work per k-step);
 //   * epilogue in the store: lane (j, g) holds channels 4g .. 4g + 3 of pixel j, stored as dwords, 64 contiguous bytes per
 //     channel row and wave-instruction.  Pixels p >= P (ragged tail) read zeros and store nothing.
+//
+// GroupNorm on either side (group_norm.h): the STATS instances also reduce the group statistics of what they
+// store (input projections, adapter_1), the NORM instance normalises its operand as it loads it (mask_projection).  The
+// stored output of a STATS instance is bit for bit that of the plain one; "no atomics" holds for the output, the
+// statistics are added into an fp64 workspace with one atomic pair per (workgroup, group).
 #include "common.h"
+#include "group_norm.h"
 
 namespace wm2f {
 namespace {
@@ -59,6 +65,14 @@ struct C1Args {
   float* out;
   int K, N;
   int Hi, Wi, Wo, P, stride;
+  // STATS: the group statistics of the stored output, stats[(b G + g) 2 + {0, 1}] += (sum, sum of squares); cpg = N / G
+  double* stats;
+  int G, cpg;
+  // NORM: x is read as act(GroupNorm_nG(x) * ngamma + nbeta) from the filled workspace nstats (stride 1)
+  const double* nstats;
+  const float *ngamma, *nbeta;
+  float neps;
+  int nG, nrelu;
 };
 
 __device__ __forceinline__ void c1_barrier() {
@@ -68,9 +82,12 @@ __device__ __forceinline__ void c1_barrier() {
 }
 
 // NRT row tiles per wave, WN waves along n: a workgroup tile is NT = WN * NRT * 16 channels by PT = (8 / WN) * 32 pixels.
-template <int NRT, int WN, int EPI>
+// STATS: the epilogue also reduces the group statistics of what it stores (gn_tile_stats; cpg in {4, 8, 16}).
+// NORM: every loaded element becomes act(scale[b][k] x + shift[b][k]) before the split, the K pairs computed once per
+// workgroup into LDS behind the ring (gn_affine / gn_apply: the bits group_norm_apply_kernel writes).
+template <int NRT, int WN, int EPI, bool STATS = false, bool NORM = false>
 __global__ __launch_bounds__(kThreads) void conv1x1_split_kernel(C1Args a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [2][NT / 16][3][64][16 B]
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [2][NT / 16][3][64][16 B] (+ NORM: [2][K] floats)
   constexpr int kRowTiles = WN * NRT;
   constexpr int kPanelBytes = kRowTiles * 3 * kFrag;
   constexpr int kPieces = kRowTiles * 3;
@@ -99,6 +116,18 @@ __global__ __launch_bounds__(kThreads) void conv1x1_split_kernel(C1Args a) {
   }
   const unsigned ch_bytes = (unsigned)HWi * 4;
 
+  float* ntab = reinterpret_cast<float*>(smem + 2 * kPanelBytes);  // NORM: scale[K], shift[K] of image b
+  if (NORM) {
+    const int ncpg = a.K / a.nG;
+    const double n = (double)ncpg * (double)HWi;
+    for (int c = tid; c < a.K; c += kThreads) {
+      const GnAffine f = gn_affine(a.nstats, b * a.nG + c / ncpg, n, a.neps, a.ngamma[c], a.nbeta[c]);
+      ntab[c] = f.scale;
+      ntab[a.K + c] = f.shift;
+    }
+    __syncthreads();
+  }
+
   f32x8 xr[kCT];
   auto issue = [&](int ks) {
     unsigned char* dst = smem + (ks & 1) * kPanelBytes;
@@ -126,6 +155,17 @@ __global__ __launch_bounds__(kThreads) void conv1x1_split_kernel(C1Args a) {
 
   for (int ks = 0; ks < n_ks; ++ks) {
     bf16x8 bh[kCT], bm[kCT], bl[kCT];
+    if (NORM) {  // channels 32 ks + 8 g .. + 7; the columns of pixels p >= P are never stored, their value is free
+      const f32x8 sc = *reinterpret_cast<const f32x8*>(ntab + ks * kKStep + 8 * g);
+      const f32x8 sh = *reinterpret_cast<const f32x8*>(ntab + a.K + ks * kKStep + 8 * g);
+#pragma unroll
+      for (int c = 0; c < kCT; ++c)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const GnAffine f = {sc[i], sh[i]};
+          xr[c][i] = a.nrelu ? gn_apply_relu(xr[c][i], f) : gn_apply(xr[c][i], f);
+        }
+    }
 #pragma unroll
     for (int c = 0; c < kCT; ++c) split3(xr[c], bh[c], bm[c], bl[c]);
     if (ks + 1 < n_ks) issue(ks + 1);  // the next step's loads fly under this step's MFMAs
@@ -165,8 +205,10 @@ __global__ __launch_bounds__(kThreads) void conv1x1_split_kernel(C1Args a) {
   __amdgpu_buffer_rsrc_t r_rs = o_rs;
   if (EPI == kBiasResRelu) r_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(a.residual + img), 0, a.N * a.P * 4, 0x00020000);
   const int n0 = n_wg + wn * NRT * 16 + 4 * g;
+  float gs[NRT], gss[NRT];  // STATS: this lane's sum and sum of squares per row tile
 #pragma unroll
   for (int rt = 0; rt < NRT; ++rt) {
+    gs[rt] = gss[rt] = 0.f;
     float bv[4] = {0.f, 0.f, 0.f, 0.f};
     if (EPI != kRaw) {
 #pragma unroll
@@ -189,9 +231,14 @@ __global__ __launch_bounds__(kThreads) void conv1x1_split_kernel(C1Args a) {
         if (EPI == kBiasResRelu) v += rv[e];
         if (EPI == kBiasRelu || EPI == kBiasResRelu) v = v < 0.f ? 0.f : v;  // a NaN stays a NaN
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), o_rs, ro, e * rs, 0);
+        if (STATS && p < a.P) {
+          gs[rt] += v;
+          gss[rt] = fmaf(v, v, gss[rt]);
+        }
       }
     }
   }
+  if (STATS) gn_tile_stats<NRT, WN, kWaves>(gs, gss, smem, a.stats, b * a.G, n_wg, a.cpg, tid);
 }
 
 // The configurations, (NRT, WN): workgroup tile NT x PT = (WN NRT 16) x (8 / WN x 32).  The LDS ring is 2 x NT x 192 B.
@@ -201,8 +248,13 @@ struct Cfg {
 constexpr Cfg kCfg[] = {{16, 1}, {8, 2}, {4, 4}, {8, 1}, {4, 1}};
 constexpr int kNumCfg = sizeof(kCfg) / sizeof(kCfg[0]);
 
+// The instances: the four epilogues; the statistics on raw and + bias; the normalised operand on + bias.
+enum : int { kPlain = 0, kStats = 1, kNorm = 2 };
+
 template <int NRT, int WN>
-void (*pick_epi(int epi))(C1Args) {
+void (*pick_epi(int epi, int opt))(C1Args) {
+  if (opt == kStats) return epi == kRaw ? conv1x1_split_kernel<NRT, WN, kRaw, true> : conv1x1_split_kernel<NRT, WN, kBias, true>;
+  if (opt == kNorm) return conv1x1_split_kernel<NRT, WN, kBias, false, true>;
   switch (epi) {
     case kRaw: return conv1x1_split_kernel<NRT, WN, kRaw>;
     case kBias: return conv1x1_split_kernel<NRT, WN, kBias>;
@@ -211,13 +263,13 @@ void (*pick_epi(int epi))(C1Args) {
   }
 }
 
-void (*pick_kernel(int ci, int epi))(C1Args) {
+void (*pick_kernel(int ci, int epi, int opt))(C1Args) {
   switch (ci) {
-    case 0: return pick_epi<16, 1>(epi);
-    case 1: return pick_epi<8, 2>(epi);
-    case 2: return pick_epi<4, 4>(epi);
-    case 3: return pick_epi<8, 1>(epi);
-    default: return pick_epi<4, 1>(epi);
+    case 0: return pick_epi<16, 1>(epi, opt);
+    case 1: return pick_epi<8, 2>(epi, opt);
+    case 2: return pick_epi<4, 4>(epi, opt);
+    case 3: return pick_epi<8, 1>(epi, opt);
+    default: return pick_epi<4, 1>(epi, opt);
   }
 }
 
@@ -260,9 +312,18 @@ extern "C" int wm2f_conv1x1_split_config(int N, int P, int B, int n_cu) {
   return choose_cfg(N, P, B, n_cu);
 }
 
-extern "C" int wm2f_conv1x1_split_fwd(const void* x, const void* w_split, const void* bias, const void* residual, void* out,
-                                      int B, int K, int N, int Hi, int Wi, int stride, int relu, int config, void* stream) {
-  const char* who = "wm2f_conv1x1_split_fwd";
+// The GroupNorm options of wm2f_conv1x1_split_gn_fwd (all zero: wm2f_conv1x1_split_fwd)
+struct C1Gn {
+  void* stats_out;
+  int G_out;
+  const void *nstats, *ngamma, *nbeta;
+  int nG;
+  float neps;
+  int nrelu;
+};
+
+static int conv1x1_launch(const char* who, const void* x, const void* w_split, const void* bias, const void* residual, void* out,
+                          const C1Gn& gn, int B, int K, int N, int Hi, int Wi, int stride, int relu, int config, void* stream) {
   WM2F_REQUIRE(x && w_split && out, "%s: null pointer", who);
   WM2F_REQUIRE(B > 0 && K > 0 && N > 0 && Hi > 0 && Wi > 0, "%s: non-positive size", who);
   WM2F_REQUIRE(K % kKStep == 0 && N % 64 == 0, "%s: K = %d must be a multiple of %d and N = %d of 64", who, K, kKStep, N);
@@ -274,6 +335,20 @@ extern "C" int wm2f_conv1x1_split_fwd(const void* x, const void* w_split, const 
   WM2F_REQUIRE((int64_t)N * K * 6 < (1ll << 31), "%s: the split weight must stay below 2 GiB", who);
   WM2F_REQUIRE(!residual || (bias && relu), "%s: the residual epilogue is bias + residual + ReLU", who);
   WM2F_REQUIRE(!relu || bias, "%s: the ReLU epilogues carry a bias", who);
+  const int opt = gn.stats_out ? kStats : (gn.nstats ? kNorm : kPlain);
+  if (opt == kStats) {
+    WM2F_REQUIRE(!gn.nstats, "%s: the statistics output and the normalised operand are not built together", who);
+    WM2F_REQUIRE(!relu && !residual, "%s: the statistics epilogue is built for raw and + bias", who);
+    WM2F_REQUIRE(gn.G_out > 0 && N % gn.G_out == 0 && gn_epilogue_cpg(N / gn.G_out),
+                 "%s: N = %d in %d groups: the epilogue reduces groups of 4, 8 or 16 channels", who, N, gn.G_out);
+  }
+  if (opt == kNorm) {
+    WM2F_REQUIRE(gn.ngamma && gn.nbeta, "%s: the normalised operand needs gamma and beta", who);
+    WM2F_REQUIRE(bias && !relu && !residual, "%s: the normalised operand is built for the + bias epilogue", who);
+    WM2F_REQUIRE(stride == 1, "%s: the normalised operand reads every pixel (stride 1)", who);
+    WM2F_REQUIRE(gn.nG > 0 && K % gn.nG == 0, "%s: K = %d is not a multiple of %d groups", who, K, gn.nG);
+    WM2F_REQUIRE(K <= 2048, "%s: the scale / shift table holds K <= 2048 channels, K = %d", who, K);
+  }
   int n_cu = 0;
   if (cu_count(&n_cu) != 0) {
     set_error("%s: cannot query the device", who);
@@ -297,15 +372,45 @@ extern "C" int wm2f_conv1x1_split_fwd(const void* x, const void* w_split, const 
   a.Wo = Wo;
   a.P = (int)P;
   a.stride = stride;
-  const size_t lds = (size_t)2 * (nt / 16) * 3 * kFrag;
-  void (*kfn)(C1Args) = pick_kernel(ci, epi);
+  a.stats = (double*)gn.stats_out;
+  a.G = opt == kStats ? gn.G_out : 1;
+  a.cpg = opt == kStats ? N / gn.G_out : 4;
+  a.nstats = (const double*)gn.nstats;
+  a.ngamma = (const float*)gn.ngamma;
+  a.nbeta = (const float*)gn.nbeta;
+  a.neps = gn.neps;
+  a.nG = opt == kNorm ? gn.nG : 1;
+  a.nrelu = gn.nrelu;
+  const size_t lds = (size_t)2 * (nt / 16) * 3 * kFrag + (opt == kNorm ? (size_t)2 * K * sizeof(float) : 0);
+  void (*kfn)(C1Args) = pick_kernel(ci, epi, opt);
   // per call: the attribute belongs to the current device
   hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) {
     set_error("%s: cannot raise dynamic LDS to %zu: %s", who, lds, hipGetErrorString(e));
     return WM2F_ELAUNCH;
   }
+  if (opt == kStats) {
+    e = hipMemsetAsync(gn.stats_out, 0, sizeof(double) * 2 * B * gn.G_out, (hipStream_t)stream);
+    WM2F_REQUIRE(e == hipSuccess, "%s: memset failed: %s", who, hipGetErrorString(e));
+  }
   hipLaunchKernelGGL(kfn, dim3(N / nt, ceil_div((int)P, pt), B), dim3(kThreads), lds, (hipStream_t)stream, a);
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;
+}
+
+extern "C" int wm2f_conv1x1_split_fwd(const void* x, const void* w_split, const void* bias, const void* residual, void* out,
+                                      int B, int K, int N, int Hi, int Wi, int stride, int relu, int config, void* stream) {
+  const C1Gn none = {nullptr, 0, nullptr, nullptr, nullptr, 0, 0.f, 0};
+  return conv1x1_launch("wm2f_conv1x1_split_fwd", x, w_split, bias, residual, out, none, B, K, N, Hi, Wi, stride, relu, config,
+                        stream);
+}
+
+extern "C" int wm2f_conv1x1_split_gn_fwd(const void* x, const void* w_split, const void* bias, void* out, void* stats_out,
+                                         int G_out, const void* norm_stats, const void* norm_gamma, const void* norm_beta,
+                                         int norm_G, float norm_eps, int norm_relu, int B, int K, int N, int Hi, int Wi,
+                                         int stride, int config, void* stream) {
+  const char* who = "wm2f_conv1x1_split_gn_fwd";
+  WM2F_REQUIRE(stats_out || norm_stats, "%s: neither a statistics output nor a normalised operand", who);
+  const C1Gn gn = {stats_out, G_out, norm_stats, norm_gamma, norm_beta, norm_G, norm_eps, norm_relu ? 1 : 0};
+  return conv1x1_launch(who, x, w_split, bias, nullptr, out, gn, B, K, N, Hi, Wi, stride, 0, config, stream);
 }

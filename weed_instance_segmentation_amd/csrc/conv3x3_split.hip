@@ -2,7 +2,8 @@
 //     y_b (N, P) = epilogue( W (N, 9 Cin) . im2col(x_b) (9 Cin, P) ),   P = Ho * Wo,  stride s in {1, 2},
 //     column k = (3 dy + dx) Cin + c of pixel p = (ho, wo) reads x_b[c, s ho + dy - 1, s wo + dx - 1] (zero outside the map)
 // for the ResNet bottlenecks' conv2 (BatchNorm folded into W and the bias by the caller, bias + ReLU in the store) and the
-// pixel decoder's FPN layer_1 (raw; GroupNorm + ReLU follow in group_norm_act_).
+// pixel decoder's FPN layer_1 (raw, with the GroupNorm statistics of the output from the epilogue: DESIGN §33; the
+// normalisation and the ReLU happen in mask_projection's operand load).
 //
 // Arithmetic: that of conv1x1_split.hip -- both operands written as three bf16 pieces (h clamped to the largest finite
 // bf16), the six products of a k-step summed from zero on v_mfma_f32_16x16x32_bf16, small terms first, and that sum added
@@ -26,6 +27,7 @@
 //     the tile table and the host's rule are those of the 1x1 kernel, ties broken towards WN = 1;
 //   * epilogue in the store: lane (j, g) holds channels 4g .. 4g + 3 of pixel j, stored as dwords.
 #include "common.h"
+#include "group_norm.h"
 
 namespace wm2f {
 namespace {
@@ -78,6 +80,9 @@ struct C3Args {
   float* out;
   int Cin, N;
   int Hi, Wi, Wo, P, stride;
+  // STATS: the group statistics of the stored output, stats[(b G + g) 2 + {0, 1}] += (sum, sum of squares); cpg = N / G
+  double* stats;
+  int G, cpg;
 };
 
 __device__ __forceinline__ void c3_barrier() {
@@ -87,7 +92,8 @@ __device__ __forceinline__ void c3_barrier() {
 }
 
 // NRT row tiles per wave, WN waves along n: a workgroup tile is NT = WN * NRT * 16 channels by PT = (8 / WN) * 32 pixels.
-template <int NRT, int WN, int EPI>
+// STATS: the epilogue also reduces the group statistics of what it stores (gn_tile_stats; cpg in {4, 8, 16}).
+template <int NRT, int WN, int EPI, bool STATS = false>
 __global__ __launch_bounds__(kThreads) void conv3x3_split_kernel(C3Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [2][NT / 16][3][64][16 B]
   constexpr int kRowTiles = WN * NRT;
@@ -197,8 +203,10 @@ __global__ __launch_bounds__(kThreads) void conv3x3_split_kernel(C3Args a) {
   const int64_t img = (int64_t)b * a.N * a.P;
   const __amdgpu_buffer_rsrc_t o_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + img), 0, a.N * a.P * 4, 0x00020000);
   const int n0 = n_wg + wn * NRT * 16 + 4 * g;
+  float gs[NRT], gss[NRT];  // STATS: this lane's sum and sum of squares per row tile
 #pragma unroll
   for (int rt = 0; rt < NRT; ++rt) {
+    gs[rt] = gss[rt] = 0.f;
     float bv[4] = {0.f, 0.f, 0.f, 0.f};
     if (EPI != kRaw) {
 #pragma unroll
@@ -215,9 +223,14 @@ __global__ __launch_bounds__(kThreads) void conv3x3_split_kernel(C3Args a) {
         if (EPI != kRaw) v += bv[e];
         if (EPI == kBiasRelu) v = v < 0.f ? 0.f : v;  // a NaN stays a NaN
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), o_rs, ro, e * rs, 0);
+        if (STATS && p < a.P) {
+          gs[rt] += v;
+          gss[rt] = fmaf(v, v, gss[rt]);
+        }
       }
     }
   }
+  if (STATS) gn_tile_stats<NRT, WN, kWaves>(gs, gss, smem, a.stats, b * a.G, n_wg, a.cpg, tid);
 }
 
 // The configurations, (NRT, WN): workgroup tile NT x PT = (WN NRT 16) x (8 / WN x 32).  The LDS ring is 2 x NT x 192 B.
@@ -228,7 +241,8 @@ constexpr Cfg kCfg[] = {{16, 1}, {8, 2}, {4, 4}, {8, 1}, {4, 1}};
 constexpr int kNumCfg = sizeof(kCfg) / sizeof(kCfg[0]);
 
 template <int NRT, int WN>
-void (*pick_epi(int epi))(C3Args) {
+void (*pick_epi(int epi, bool stats))(C3Args) {
+  if (stats) return conv3x3_split_kernel<NRT, WN, kRaw, true>;  // the statistics are built on the raw epilogue
   switch (epi) {
     case kRaw: return conv3x3_split_kernel<NRT, WN, kRaw>;
     case kBias: return conv3x3_split_kernel<NRT, WN, kBias>;
@@ -236,13 +250,13 @@ void (*pick_epi(int epi))(C3Args) {
   }
 }
 
-void (*pick_kernel(int ci, int epi))(C3Args) {
+void (*pick_kernel(int ci, int epi, bool stats))(C3Args) {
   switch (ci) {
-    case 0: return pick_epi<16, 1>(epi);
-    case 1: return pick_epi<8, 2>(epi);
-    case 2: return pick_epi<4, 4>(epi);
-    case 3: return pick_epi<8, 1>(epi);
-    default: return pick_epi<4, 1>(epi);
+    case 0: return pick_epi<16, 1>(epi, stats);
+    case 1: return pick_epi<8, 2>(epi, stats);
+    case 2: return pick_epi<4, 4>(epi, stats);
+    case 3: return pick_epi<8, 1>(epi, stats);
+    default: return pick_epi<4, 1>(epi, stats);
   }
 }
 
@@ -288,9 +302,9 @@ extern "C" int wm2f_conv3x3_split_config(int N, int P, int B, int n_cu) {
   return choose_cfg(N, P, B, n_cu);
 }
 
-extern "C" int wm2f_conv3x3_split_fwd(const void* x, const void* w_split, const void* bias, void* out, int B, int Cin, int N,
-                                      int Hi, int Wi, int stride, int relu, int config, void* stream) {
-  const char* who = "wm2f_conv3x3_split_fwd";
+// stats_out != NULL: the group statistics of the (raw) output in G_out groups (wm2f_conv3x3_split_stats_fwd)
+static int conv3x3_launch(const char* who, const void* x, const void* w_split, const void* bias, void* out, void* stats_out,
+                          int G_out, int B, int Cin, int N, int Hi, int Wi, int stride, int relu, int config, void* stream) {
   WM2F_REQUIRE(x && w_split && out, "%s: null pointer", who);
   WM2F_REQUIRE(B > 0 && Cin > 0 && N > 0 && Hi > 0 && Wi > 0, "%s: non-positive size", who);
   WM2F_REQUIRE(Cin % kKStep == 0 && N % 64 == 0, "%s: Cin = %d must be a multiple of %d and N = %d of 64", who, Cin, kKStep, N);
@@ -301,6 +315,11 @@ extern "C" int wm2f_conv3x3_split_fwd(const void* x, const void* w_split, const 
                "%s: one image of x / out must stay below 2 GiB (32-bit buffer offsets)", who);
   WM2F_REQUIRE((int64_t)N * 9 * Cin * 6 < (1ll << 31), "%s: the split weight must stay below 2 GiB", who);
   WM2F_REQUIRE(!relu || bias, "%s: the ReLU epilogue carries a bias", who);
+  if (stats_out) {
+    WM2F_REQUIRE(!bias && !relu, "%s: the statistics epilogue is built for the raw output", who);
+    WM2F_REQUIRE(G_out > 0 && N % G_out == 0 && gn_epilogue_cpg(N / G_out),
+                 "%s: N = %d in %d groups: the epilogue reduces groups of 4, 8 or 16 channels", who, N, G_out);
+  }
   int n_cu = 0;
   if (cu_count(&n_cu) != 0) {
     set_error("%s: cannot query the device", who);
@@ -323,15 +342,35 @@ extern "C" int wm2f_conv3x3_split_fwd(const void* x, const void* w_split, const 
   a.Wo = Wo;
   a.P = (int)P;
   a.stride = stride;
+  a.stats = (double*)stats_out;
+  a.G = stats_out ? G_out : 1;
+  a.cpg = stats_out ? N / G_out : 4;
   const size_t lds = (size_t)2 * (nt / 16) * 3 * kFrag;
-  void (*kfn)(C3Args) = pick_kernel(ci, epi);
+  void (*kfn)(C3Args) = pick_kernel(ci, epi, stats_out != nullptr);
   // per call: the attribute belongs to the current device
   hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) {
     set_error("%s: cannot raise dynamic LDS to %zu: %s", who, lds, hipGetErrorString(e));
     return WM2F_ELAUNCH;
   }
+  if (stats_out) {
+    e = hipMemsetAsync(stats_out, 0, sizeof(double) * 2 * B * G_out, (hipStream_t)stream);
+    WM2F_REQUIRE(e == hipSuccess, "%s: memset failed: %s", who, hipGetErrorString(e));
+  }
   hipLaunchKernelGGL(kfn, dim3(N / nt, ceil_div((int)P, pt), B), dim3(kThreads), lds, (hipStream_t)stream, a);
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;
+}
+
+extern "C" int wm2f_conv3x3_split_fwd(const void* x, const void* w_split, const void* bias, void* out, int B, int Cin, int N,
+                                      int Hi, int Wi, int stride, int relu, int config, void* stream) {
+  return conv3x3_launch("wm2f_conv3x3_split_fwd", x, w_split, bias, out, nullptr, 0, B, Cin, N, Hi, Wi, stride, relu, config,
+                        stream);
+}
+
+extern "C" int wm2f_conv3x3_split_stats_fwd(const void* x, const void* w_split, void* out, void* stats_out, int G_out, int B,
+                                            int Cin, int N, int Hi, int Wi, int stride, int config, void* stream) {
+  const char* who = "wm2f_conv3x3_split_stats_fwd";
+  WM2F_REQUIRE(stats_out, "%s: null pointer", who);
+  return conv3x3_launch(who, x, w_split, nullptr, out, stats_out, G_out, B, Cin, N, Hi, Wi, stride, 0, config, stream);
 }

@@ -10,6 +10,7 @@
 //                  registers, exactly torch's formula (biased variance, eps inside the sqrt).
 // Both move each byte once: read x (+res) and write y -> bound by HBM.
 #include "common.h"
+#include "group_norm.h"
 
 namespace wm2f {
 
@@ -303,12 +304,7 @@ __global__ __launch_bounds__(256) void group_norm_apply_kernel(const float* __re
   const int cpg = C / G, g = c / cpg;
   const int HW4 = (H * W) >> 2, W4 = W >> 2;
   const double n = (double)cpg * (double)H * (double)W;
-  const double mean_d = stats[2 * (b * G + g)] / n;
-  double var_d = stats[2 * (b * G + g) + 1] / n - mean_d * mean_d;
-  var_d = var_d < 0.0 ? 0.0 : var_d;
-  const float rstd = (float)(1.0 / sqrt(var_d + (double)eps));
-  const float scale = rstd * gamma[c];
-  const float shift = beta[c] - (float)mean_d * scale;
+  const GnAffine aff = gn_affine(stats, b * G + g, n, eps, gamma[c], beta[c]);
   const float4* xp = reinterpret_cast<const float4*>(x) + (int64_t)row * HW4;
   float4* yp = reinterpret_cast<float4*>(y) + (int64_t)row * HW4;
   const float* sp = up != nullptr ? up + (int64_t)row * Hs * Ws : nullptr;
@@ -324,7 +320,7 @@ __global__ __launch_bounds__(256) void group_norm_apply_kernel(const float* __re
   for (int u = 0; u < kGnU; ++u) {
     const int i = i0 + u * 256;
     if (i >= HW4) continue;
-    float o[4] = {v[u].x * scale + shift, v[u].y * scale + shift, v[u].z * scale + shift, v[u].w * scale + shift};
+    float o[4] = {gn_apply(v[u].x, aff), gn_apply(v[u].y, aff), gn_apply(v[u].z, aff), gn_apply(v[u].w, aff)};
     if (sp != nullptr) {
       const int py = i / W4, px = (i - py * W4) * 4;
       const UpIdx iy = up_index(py, sy, Hs);
@@ -344,6 +340,22 @@ __global__ __launch_bounds__(256) void group_norm_apply_kernel(const float* __re
   }
 }
 
+// The same map, one element per thread, for maps whose rows are no multiple of four floats (no upsampled operand): the
+// apply-only entry point takes any map, so that what the normalising loader of conv1x1_split.hip feeds its GEMM can be
+// written out and compared at any size.
+__global__ __launch_bounds__(256) void group_norm_apply_any_kernel(const float* __restrict__ x, const double* __restrict__ stats,
+                                                                   const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                   float* __restrict__ y, int C, int G, int HW, float eps, int relu,
+                                                                   int64_t total) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int row = (int)(i / HW);  // b * C + c
+  const int b = row / C, c = row - b * C;
+  const int cpg = C / G;
+  const GnAffine aff = gn_affine(stats, b * G + c / cpg, (double)cpg * (double)HW, eps, gamma[c], beta[c]);
+  y[i] = relu ? gn_apply_relu(x[i], aff) : gn_apply(x[i], aff);
+}
+
 // tokens[b][start + p][c] = GroupNorm(x + bias)[b][c][p]: the input projections of the pixel decoder (HF:1341-1357:
 // Conv2d 1x1 + GroupNorm per level, then flatten(2).transpose(1, 2) and a concatenation over levels) written straight
 // into the (B, S, C) token buffer.  32 x 32 LDS tile transpose, both sides coalesced.
@@ -358,25 +370,19 @@ __global__ __launch_bounds__(256) void group_norm_tokens_kernel(const float* __r
   const int cpg = C / G;
   if (threadIdx.x < 32) {
     const int c = c0 + threadIdx.x;
-    float scale = 0.f, shift = 0.f;
-    if (c < C) {
-      const int g = c / cpg;
-      const double n = (double)cpg * (double)HW;
-      const double mean_d = stats[2 * (b * G + g)] / n;
-      double var_d = stats[2 * (b * G + g) + 1] / n - mean_d * mean_d;
-      var_d = var_d < 0.0 ? 0.0 : var_d;
-      scale = (float)(1.0 / sqrt(var_d + (double)eps)) * gamma[c];
-      shift = beta[c] + ((bias != nullptr ? bias[c] : 0.f) - (float)mean_d) * scale;
-    }
-    sc[threadIdx.x] = scale;
-    sh[threadIdx.x] = shift;
+    GnAffine aff = {0.f, 0.f};
+    if (c < C)
+      aff = gn_affine(stats, b * G + c / cpg, (double)cpg * (double)HW, eps, gamma[c], beta[c], true,
+                      bias != nullptr ? bias[c] : 0.f);
+    sc[threadIdx.x] = aff.scale;
+    sh[threadIdx.x] = aff.shift;
   }
   __syncthreads();
   const float* src = x + (int64_t)b * C * HW;
 #pragma unroll
   for (int r = 0; r < 32; r += 8) {
     const int c = c0 + ty + r, p = p0 + tx;
-    tile[ty + r][tx] = (c < C && p < HW) ? src[(int64_t)c * HW + p] * sc[ty + r] + sh[ty + r] : 0.f;
+    tile[ty + r][tx] = (c < C && p < HW) ? gn_apply(src[(int64_t)c * HW + p], GnAffine{sc[ty + r], sh[ty + r]}) : 0.f;
   }
   __syncthreads();
   float* dst = tok + ((int64_t)b * S + start) * C;
@@ -389,14 +395,25 @@ __global__ __launch_bounds__(256) void group_norm_tokens_kernel(const float* __r
 }  // namespace
 }  // namespace wm2f
 
-extern "C" int wm2f_group_norm_act(const void* x, const void* gamma, const void* beta, const void* up, void* y,
-                                   void* stats_ws, int B, int C, int G, int H, int W, int Hs, int Ws, float eps, int relu,
-                                   void* stream) {
+// with_stats: the statistics pass runs first; else stats_ws is already filled (a convolution epilogue wrote it)
+static int group_norm_act_launch(const char* who, bool with_stats, const void* x, const void* gamma, const void* beta,
+                                 const void* up, void* y, void* stats_ws, int B, int C, int G, int H, int W, int Hs, int Ws,
+                                 float eps, int relu, void* stream) {
   using namespace wm2f;
-  const char* who = "wm2f_group_norm_act";
   WM2F_REQUIRE(x && gamma && beta && y && stats_ws, "%s: null pointer", who);
   WM2F_REQUIRE(B > 0 && C > 0 && G > 0 && H > 0 && W > 0, "%s: non-positive size", who);
   WM2F_REQUIRE(C % G == 0, "%s: C=%d is not a multiple of G=%d", who, C, G);
+  if (!with_stats && up == nullptr && W % 4 != 0) {  // apply only, any map: one element per thread
+    const int64_t total = (int64_t)B * C * H * W;
+    WM2F_REQUIRE((int64_t)H * W < (int64_t(1) << 31) && (int64_t)B * C < (int64_t(1) << 31) &&
+                     ceil_div64(total, 256) < (int64_t(1) << 31),
+                 "%s: sizes exceed the grid limits", who);
+    hipLaunchKernelGGL(group_norm_apply_any_kernel, dim3((unsigned)ceil_div64(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)x, (const double*)stats_ws, (const float*)gamma, (const float*)beta, (float*)y, C, G, H * W,
+                       eps, relu, total);
+    WM2F_CHECK_LAUNCH(who);
+    return WM2F_OK;
+  }
   WM2F_REQUIRE(W % 4 == 0, "%s: W=%d must be a multiple of 4", who, W);
   WM2F_REQUIRE(up == nullptr || (Hs > 0 && Ws > 0), "%s: the upsampled operand needs its size", who);
   const int64_t span4 = (int64_t)(C / G) * H * W / 4;
@@ -406,11 +423,13 @@ extern "C" int wm2f_group_norm_act(const void* x, const void* gamma, const void*
                    HW4 < (int64_t(1) << 30),
                "%s: sizes exceed the grid limits", who);
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(stats_ws, 0, sizeof(double) * 2 * B * G, st);
-  WM2F_REQUIRE(e == hipSuccess, "%s: memset failed: %s", who, hipGetErrorString(e));
-  hipLaunchKernelGGL(group_stats_kernel, dim3((unsigned)((int64_t)B * G * s_chunks)), dim3(256), 0, st, (const float*)x,
-                     (const float*)nullptr, (double*)stats_ws, span4, (int)s_chunks, G, C / G, (int)HW4);
-  WM2F_CHECK_LAUNCH(who);
+  if (with_stats) {
+    hipError_t e = hipMemsetAsync(stats_ws, 0, sizeof(double) * 2 * B * G, st);
+    WM2F_REQUIRE(e == hipSuccess, "%s: memset failed: %s", who, hipGetErrorString(e));
+    hipLaunchKernelGGL(group_stats_kernel, dim3((unsigned)((int64_t)B * G * s_chunks)), dim3(256), 0, st, (const float*)x,
+                       (const float*)nullptr, (double*)stats_ws, span4, (int)s_chunks, G, C / G, (int)HW4);
+    WM2F_CHECK_LAUNCH(who);
+  }
   hipLaunchKernelGGL(group_norm_apply_kernel, dim3((unsigned)((int64_t)B * C * a_chunks)), dim3(256), 0, st, (const float*)x,
                      (const double*)stats_ws, (const float*)gamma, (const float*)beta, (const float*)up, (float*)y, C, G, H, W,
                      Hs, Ws, eps, relu, (int)a_chunks);
@@ -418,10 +437,24 @@ extern "C" int wm2f_group_norm_act(const void* x, const void* gamma, const void*
   return WM2F_OK;
 }
 
-extern "C" int wm2f_group_norm_tokens(const void* x, const void* bias, const void* gamma, const void* beta, void* tokens,
-                                      void* stats_ws, int B, int C, int G, int HW, int S, int start, float eps, void* stream) {
+extern "C" int wm2f_group_norm_act(const void* x, const void* gamma, const void* beta, const void* up, void* y,
+                                   void* stats_ws, int B, int C, int G, int H, int W, int Hs, int Ws, float eps, int relu,
+                                   void* stream) {
+  return group_norm_act_launch("wm2f_group_norm_act", true, x, gamma, beta, up, y, stats_ws, B, C, G, H, W, Hs, Ws, eps, relu,
+                               stream);
+}
+
+extern "C" int wm2f_group_norm_act_apply(const void* x, const void* gamma, const void* beta, const void* up, void* y,
+                                         const void* stats, int B, int C, int G, int H, int W, int Hs, int Ws, float eps,
+                                         int relu, void* stream) {
+  return group_norm_act_launch("wm2f_group_norm_act_apply", false, x, gamma, beta, up, y, const_cast<void*>(stats), B, C, G, H,
+                               W, Hs, Ws, eps, relu, stream);
+}
+
+static int group_norm_tokens_launch(const char* who, bool with_stats, const void* x, const void* bias, const void* gamma,
+                                    const void* beta, void* tokens, void* stats_ws, int B, int C, int G, int HW, int S,
+                                    int start, float eps, void* stream) {
   using namespace wm2f;
-  const char* who = "wm2f_group_norm_tokens";
   WM2F_REQUIRE(x && gamma && beta && tokens && stats_ws, "%s: null pointer", who);
   WM2F_REQUIRE(B > 0 && B < 65536 && C > 0 && G > 0 && HW > 0 && S > 0, "%s: bad size", who);
   WM2F_REQUIRE(C % G == 0, "%s: C=%d is not a multiple of G=%d", who, C, G);
@@ -433,16 +466,31 @@ extern "C" int wm2f_group_norm_tokens(const void* x, const void* bias, const voi
   WM2F_REQUIRE((int64_t)B * G * s_chunks < (int64_t(1) << 31) && ceil_div(C, 32) < 65536 && span4 < (int64_t(1) << 31),
                "%s: sizes exceed the grid limits", who);
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(stats_ws, 0, sizeof(double) * 2 * B * G, st);
-  WM2F_REQUIRE(e == hipSuccess, "%s: memset failed: %s", who, hipGetErrorString(e));
-  hipLaunchKernelGGL(group_stats_kernel, dim3((unsigned)((int64_t)B * G * s_chunks)), dim3(256), 0, st, (const float*)x,
-                     (const float*)bias, (double*)stats_ws, span4, (int)s_chunks, G, C / G, HW / 4);
-  WM2F_CHECK_LAUNCH(who);
+  if (with_stats) {
+    hipError_t e = hipMemsetAsync(stats_ws, 0, sizeof(double) * 2 * B * G, st);
+    WM2F_REQUIRE(e == hipSuccess, "%s: memset failed: %s", who, hipGetErrorString(e));
+    hipLaunchKernelGGL(group_stats_kernel, dim3((unsigned)((int64_t)B * G * s_chunks)), dim3(256), 0, st, (const float*)x,
+                       (const float*)bias, (double*)stats_ws, span4, (int)s_chunks, G, C / G, HW / 4);
+    WM2F_CHECK_LAUNCH(who);
+  }
   hipLaunchKernelGGL(group_norm_tokens_kernel, dim3(ceil_div(HW, 32), ceil_div(C, 32), B), dim3(256), 0, st, (const float*)x,
                      (const float*)bias, (const double*)stats_ws, (const float*)gamma, (const float*)beta, (float*)tokens, C, G,
                      HW, S, start, eps);
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;
+}
+
+extern "C" int wm2f_group_norm_tokens(const void* x, const void* bias, const void* gamma, const void* beta, void* tokens,
+                                      void* stats_ws, int B, int C, int G, int HW, int S, int start, float eps, void* stream) {
+  return group_norm_tokens_launch("wm2f_group_norm_tokens", true, x, bias, gamma, beta, tokens, stats_ws, B, C, G, HW, S, start,
+                                  eps, stream);
+}
+
+extern "C" int wm2f_group_norm_tokens_apply(const void* x, const void* bias, const void* gamma, const void* beta, void* tokens,
+                                            const void* stats, int B, int C, int G, int HW, int S, int start, float eps,
+                                            void* stream) {
+  return group_norm_tokens_launch("wm2f_group_norm_tokens_apply", false, x, bias, gamma, beta, tokens, const_cast<void*>(stats),
+                                  B, C, G, HW, S, start, eps, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -324,8 +324,11 @@ class Mask2FormerPixelDecoder(nn.Module):
             start = 0
             for lvl, x in enumerate(levels):
                 conv, gn = self.input_projections[lvl]
-                raw = self._conv1x1(conv, x, f"in{lvl}", bias=False)
-                ops.group_norm_tokens_(raw, conv.bias, gn.num_groups, gn.weight, gn.bias, gn.eps, hidden, start)
+                raw, st = self._conv1x1_stats(conv, x, f"in{lvl}", gn.num_groups, bias=False)
+                if st is not None:  # bias added and statistics taken in the convolution's epilogue
+                    ops.group_norm_tokens_from_stats_(raw, st, None, gn.num_groups, gn.weight, gn.bias, gn.eps, hidden, start)
+                else:
+                    ops.group_norm_tokens_(raw, conv.bias, gn.num_groups, gn.weight, gn.bias, gn.eps, hidden, start)
                 start += level_hw[lvl][0] * level_hw[lvl][1]
         else:
             embeds = [self.input_projections[lvl](x) for lvl, x in enumerate(levels)]
@@ -342,22 +345,59 @@ class Mask2FormerPixelDecoder(nn.Module):
             start += h * w
         self._last_tokens = tokens
         n = self.num_fpn_levels
+        norm = None  # (stats, groups, gamma, beta, eps, relu) of outs[-1] when it is a raw layer_k output
         for idx, feat in enumerate(features[:n][::-1]):  # HF:1395-1405
             k = n - idx
             adapter, layer = getattr(self, f"adapter_{k}"), getattr(self, f"layer_{k}")
             if fast and feat.shape[-1] % 4 == 0 and feat.dtype == torch.float32:
                 # GroupNorm + upsample-add and GroupNorm + ReLU as one statistics pass and one fused pass each
+                # (the statistics come out of the convolutions' epilogues where they can, and the last layer's
+                # GroupNorm + ReLU moves into mask_projection's operand load)
                 gn_a, gn_l = adapter[1], layer[1]
-                out = ops.group_norm_act_(self._conv1x1(adapter[0], feat, "adapter"), gn_a.num_groups, gn_a.weight, gn_a.bias, gn_a.eps,
-                                          up=outs[-1].contiguous())
-                outs.append(ops.group_norm_act_(self._conv3x3(layer[0], out, f"layer_{k}"), gn_l.num_groups, gn_l.weight, gn_l.bias, gn_l.eps, relu=True))
+                lat, st = self._conv1x1_stats(adapter[0], feat, "adapter", gn_a.num_groups, bias=True)
+                if st is not None:
+                    out = ops.group_norm_act_from_stats_(lat, st, gn_a.num_groups, gn_a.weight, gn_a.bias, gn_a.eps,
+                                                         up=outs[-1].contiguous())
+                else:
+                    out = ops.group_norm_act_(lat, gn_a.num_groups, gn_a.weight, gn_a.bias, gn_a.eps, up=outs[-1].contiguous())
+                y, st = self._conv3x3_stats(layer[0], out, f"layer_{k}", gn_l.num_groups)
+                if st is None:
+                    y = ops.group_norm_act_(y, gn_l.num_groups, gn_l.weight, gn_l.bias, gn_l.eps, relu=True)
+                elif idx == n - 1 and self._mask_projection_normalises(y):
+                    norm = (st, gn_l.num_groups, gn_l.weight, gn_l.bias, gn_l.eps, True)  # y stays raw: no write-back
+                else:
+                    y = ops.group_norm_act_from_stats_(y, st, gn_l.num_groups, gn_l.weight, gn_l.bias, gn_l.eps, relu=True)
+                outs.append(y)
                 continue
             lat = adapter(feat)
             out = lat + F.interpolate(outs[-1], size=lat.shape[-2:], mode="bilinear", align_corners=False)
             outs.append(layer(out))
+        if norm is not None:
+            mp = self.mask_projection
+            ws = ops.split_weight_cached(self, "mask_projection", mp.weight.view(mp.weight.shape[0], mp.weight.shape[1]), base=mp.weight)
+            return ops.conv1x1_gn(outs[-1], mp.weight, mp.bias, w_split=ws, norm=norm), outs[:3]
         if fast:
             return self._conv1x1(self.mask_projection, outs[-1], "mask_projection"), outs[:3]
         return self.mask_projection(outs[-1]), outs[:3]
+
+    def _split1x1(self, conv: nn.Conv2d, x: torch.Tensor) -> bool:
+        return (ops.CONV1X1_SPLIT and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
+                and conv.groups == 1 and ops.conv1x1_applies(x, conv.weight))
+
+    def _mask_projection_normalises(self, x: torch.Tensor) -> bool:
+        """mask_projection can read x through the normalising loader of the split kernel (ops.conv1x1_gn, norm=...)."""
+        mp = self.mask_projection
+        return ops.CONV_GN_FUSED and mp.bias is not None and mp.weight.shape[1] <= 2048 and self._split1x1(mp, x)
+
+    def _conv1x1_stats(self, conv: nn.Conv2d, x: torch.Tensor, name: str, groups: int, bias: bool):
+        """Inference: (conv(x) + its bias, the GroupNorm statistics of that in `groups` groups) from the split kernel where
+        its epilogue produces them (ops.conv1x1_gn), else (_conv1x1(conv, x, name, bias), None): the route with a separate
+        statistics pass, which for the input projections also adds the bias (bias=False)."""
+        w = conv.weight
+        if ops.CONV_GN_FUSED and ops.conv_group_stats_applies(w.shape[0], groups) and self._split1x1(conv, x):
+            ws = ops.split_weight_cached(self, name, w.view(w.shape[0], w.shape[1]), base=w)
+            return ops.conv1x1_gn(x, w, conv.bias, w_split=ws, stats_groups=groups)
+        return self._conv1x1(conv, x, name, bias=bias), None
 
     def _conv1x1(self, conv: nn.Conv2d, x: torch.Tensor, name: str, bias: bool = True) -> torch.Tensor:
         """Inference: a 1x1 convolution on the split-bf16 kernel (ops.conv1x1) where it applies, else the module's own
@@ -369,14 +409,25 @@ class Mask2FormerPixelDecoder(nn.Module):
             return ops.conv1x1(x, w, conv.bias if bias else None, w_split=ws)
         return F.conv2d(x, w, conv.bias if bias else None, conv.stride, conv.padding)
 
+    def _split3x3(self, conv: nn.Conv2d, x: torch.Tensor) -> bool:
+        return (ops.CONV3X3_SPLIT and conv.bias is None and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
+                and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and ops.conv3x3_applies(x, conv.weight))
+
     def _conv3x3(self, conv: nn.Conv2d, x: torch.Tensor, name: str) -> torch.Tensor:
         """Inference: a 3x3 convolution (padding 1, no bias) on the split-bf16 kernel (ops.conv3x3) where it applies, else
         the module's own convolution."""
         w = conv.weight
-        if (ops.CONV3X3_SPLIT and conv.bias is None and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
-                and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and ops.conv3x3_applies(x, w)):
+        if Mask2FormerPixelDecoder._split3x3(self, conv, x):
             return ops.conv3x3(x, w, w_split=ops.split_weight_cached(self, name, w, tap_major=True))
         return conv(x)
+
+    def _conv3x3_stats(self, conv: nn.Conv2d, x: torch.Tensor, name: str, groups: int):
+        """Inference: (_conv3x3's result, its GroupNorm statistics in `groups` groups from the split kernel's epilogue
+        (ops.conv3x3_stats), or None where that does not produce them)."""
+        w = conv.weight
+        if ops.CONV_GN_FUSED and ops.conv_group_stats_applies(w.shape[0], groups) and self._split3x3(conv, x):
+            return ops.conv3x3_stats(x, w, groups, w_split=ops.split_weight_cached(self, name, w, tap_major=True))
+        return self._conv3x3(conv, x, name), None
 
 
 class Mask2FormerPixelLevelModule(nn.Module):

@@ -3,7 +3,7 @@
 PyTorch is used for device memory, streams and autograd bookkeeping only.  Every function here launches hand-written HIP
 through the C ABI (include/wm2f.h) on the caller's current stream and RAISES if the tensors are not on a GPU or the library
 is missing -- there is no eager fallback.  One module per kernel family; each launch goes through `_core._launch`.  This
-package re-exports them all and owns the three switches below: callers assign and read them as `ops.<FLAG>`.
+package re-exports them all and owns the switches below: callers assign and read them as `ops.<FLAG>`.
 """
 from __future__ import annotations
 
@@ -20,15 +20,21 @@ CONV1X1_SPLIT = True
 # reference of the tests).
 CONV3X3_SPLIT = True
 
+# The pixel decoder's inference forward folds GroupNorm into the convolutions around it while this is True: the
+# group statistics come out of the convolution epilogues (conv1x1_gn, conv3x3_stats) and mask_projection normalises
+# layer_1's raw output in its operand load.  False keeps the separate statistics and apply passes (the reference of the tests).
+CONV_GN_FUSED = True
+
 # The flags come first: k1 reads K1_BWD_DETERMINISTIC off this package.
 from .._lib import check
 from ._core import KernelTimer, _p, _stream, set_kernel_timer
 from .ccl import label_components, resize_nearest_tables
 from .clean import labelmap_clean
 from .copy_paste import copy_paste
-from .fused import (add_broadcast, bias_act_, bias_relu_maxpool, group_norm_act_, group_norm_tokens_, resize_bilinear,
-                    resize_pyramid, tokens_to_nchw)
-from .gemm import (conv1x1, conv1x1_applies, conv3x3, conv3x3_applies, linear_tokens, split_weight, split_weight_3x3,
+from .fused import (add_broadcast, bias_act_, bias_relu_maxpool, group_norm_act_, group_norm_act_from_stats_, group_norm_tokens_,
+                    group_norm_tokens_from_stats_, resize_bilinear, resize_pyramid, tokens_to_nchw)
+from .gemm import (conv1x1, conv1x1_applies, conv1x1_gn, conv3x3, conv3x3_applies, conv3x3_stats, conv_group_stats_applies,
+                   linear_tokens, split_weight, split_weight_3x3,
                    split_weight_cached, split_weight_stem, stem_conv_pool, stem_conv_pool_applies, stem_weight_columns,
                    stem_weight_matrix, token_linear, token_linear_applies, token_wgrad, token_wgrad_applies)
 from .k1 import (k1_bwd_deterministic, k1_lane_order, k1_lane_rows, k1_lanes_applies, k1_rows_applies, ms_deform_attn,

@@ -61,6 +61,48 @@ def group_norm_tokens_(x: torch.Tensor, bias: torch.Tensor | None, groups: int, 
     return tokens
 
 
+def group_norm_tokens_from_stats_(x: torch.Tensor, stats: torch.Tensor, bias: torch.Tensor | None, groups: int, gamma: torch.Tensor,
+                                  beta: torch.Tensor, eps: float, tokens: torch.Tensor, start: int) -> torch.Tensor:
+    """group_norm_tokens_ from a filled statistics workspace `stats` (B, groups, 2) fp64 = (sum, sum of squares) of x + bias
+    per image and group (a convolution epilogue wrote it: conv1x1_gn): no statistics pass."""
+    if not x.is_contiguous() or not tokens.is_contiguous():
+        raise ValueError("group_norm_tokens_from_stats_: x and tokens must be contiguous")
+    _req(x, "x"), _req(tokens, "tokens")
+    gamma, beta, stats = _req(gamma, "gamma"), _req(beta, "beta"), _req(stats, "stats", torch.float64)
+    if bias is not None:
+        bias = _req(bias, "bias")
+    B, C, H, W = x.shape
+    if tokens.dim() != 3 or tokens.shape[0] != B or tokens.shape[2] != C:
+        raise ValueError("group_norm_tokens_from_stats_: tokens must be (B, S, C)")
+    if stats.numel() != 2 * B * int(groups):
+        raise ValueError("group_norm_tokens_from_stats_: stats must be (B, groups, 2)")
+    _launch("wm2f_group_norm_tokens_apply", x, _p(x), _p(bias), _p(gamma), _p(beta), _p(tokens), _p(stats), B, C, int(groups),
+            H * W, int(tokens.shape[1]), int(start), float(eps))
+    return tokens
+
+
+def group_norm_act_from_stats_(x: torch.Tensor, stats: torch.Tensor, groups: int, gamma: torch.Tensor, beta: torch.Tensor,
+                               eps: float, up: torch.Tensor | None = None, relu: bool = False) -> torch.Tensor:
+    """group_norm_act_ from a filled statistics workspace `stats` (B, groups, 2) fp64 = (sum, sum of squares) of x per image
+    and group (a convolution epilogue wrote it: conv1x1_gn, conv3x3_stats): no statistics pass."""
+    if not x.is_contiguous():
+        raise ValueError("group_norm_act_from_stats_: x must be NCHW-contiguous")
+    _req(x, "x")
+    gamma, beta, stats = _req(gamma, "gamma"), _req(beta, "beta"), _req(stats, "stats", torch.float64)
+    B, C, H, W = x.shape
+    if stats.numel() != 2 * B * int(groups):
+        raise ValueError("group_norm_act_from_stats_: stats must be (B, groups, 2)")
+    Hs = Ws = 0
+    if up is not None:
+        up = _req(up, "up")
+        if up.dim() != 4 or up.shape[:2] != x.shape[:2]:
+            raise ValueError("group_norm_act_from_stats_: up must be (B, C, Hs, Ws)")
+        Hs, Ws = int(up.shape[2]), int(up.shape[3])
+    _launch("wm2f_group_norm_act_apply", x, _p(x), _p(gamma), _p(beta), _p(up), _p(x), _p(stats), B, C, int(groups), H, W, Hs,
+            Ws, float(eps), 1 if relu else 0)
+    return x
+
+
 def resize_bilinear(x: torch.Tensor, size: Sequence[int]) -> torch.Tensor:
     """F.interpolate(x, size=size, mode="bilinear", align_corners=False) for an NCHW fp32 map (inference, no autograd)."""
     if not x.is_contiguous():

@@ -165,6 +165,78 @@ def conv1x1(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = N
     return out
 
 
+def conv_group_stats_applies(channels: int, groups: int) -> bool:
+    """Group sizes for which the split convolutions' epilogue produces the GroupNorm statistics of its output
+    (conv1x1_gn, conv3x3_stats): groups of 4, 8 or 16 channels, each inside one 16-channel row tile of the kernel.  Any
+    other size keeps the separate statistics pass (group_norm_act_, group_norm_tokens_)."""
+    return groups > 0 and channels % groups == 0 and channels // groups in (4, 8, 16)
+
+
+def conv1x1_gn(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None, stride: int = 1,
+               w_split: torch.Tensor | None = None, config: int = -1, stats_groups: int = 0, norm: tuple | None = None):
+    """conv1x1 on the split kernel (raw or + bias; the shapes of conv1x1_applies) with GroupNorm folded in on one side:
+    stats_groups = G > 0: returns (out, stats), stats (B, G, 2) fp64 = (sum, sum of squares) of out per image and group, from
+        the kernel's epilogue -- the filled workspace group_norm_act_from_stats_ / group_norm_tokens_from_stats_ read.
+        Needs conv_group_stats_applies(N, G).
+    norm = (stats, groups, gamma, beta, eps, relu): x is read as act(GroupNorm(x)) from the filled workspace `stats` of x --
+        bit for bit conv1x1 of group_norm_act_from_stats_(x, ...), without that pass over x.  Needs bias and stride 1.
+        Returns out.
+    `out` is bit for bit conv1x1's.  Inference, no autograd; exactly one of the two options."""
+    if (stats_groups > 0) == (norm is not None):
+        raise ValueError("conv1x1_gn: exactly one of stats_groups and norm")
+    if not conv1x1_applies(x, weight, stride):
+        raise ValueError("conv1x1_gn: shapes outside conv1x1_applies take conv1x1 and the separate GroupNorm passes")
+    N, K = int(weight.shape[0]), int(weight.shape[1])
+    x = _req(x, "x")
+    w2 = _req(weight.reshape(N, K), "weight")
+    B, _, H, W = x.shape
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if bias is not None:
+        bias = _req(bias, "bias")
+        if bias.shape != (N,):
+            raise ValueError(f"conv1x1_gn: bias {tuple(bias.shape)} for {N} channels")
+    if w_split is None:
+        w_split = split_weight(w2)
+    elif w_split.dtype != torch.uint8 or w_split.numel() != N * K * 6 or w_split.device != x.device:
+        raise ValueError("conv1x1_gn: w_split is not split_weight(weight)")
+    stats = nstats = ngamma = nbeta = None
+    nG, neps, nrelu = 0, 0.0, False
+    if norm is not None:
+        nstats, nG, ngamma, nbeta, neps, nrelu = norm
+        nstats, ngamma, nbeta = _req(nstats, "norm stats", torch.float64), _req(ngamma, "gamma"), _req(nbeta, "beta")
+        if nstats.numel() != 2 * B * int(nG) or ngamma.shape != (K,) or nbeta.shape != (K,):
+            raise ValueError("conv1x1_gn: norm = (stats (B, G, 2) fp64, G, gamma (K), beta (K), eps, relu)")
+    else:
+        stats = torch.empty(B, int(stats_groups), 2, device=x.device, dtype=torch.float64)
+    out = torch.empty(B, N, Ho, Wo, device=x.device, dtype=torch.float32)
+    _launch("wm2f_conv1x1_split_gn_fwd", x, _p(x), _p(w_split), _p(bias), _p(out), _p(stats), int(stats_groups), _p(nstats),
+            _p(ngamma), _p(nbeta), int(nG), float(neps), 1 if nrelu else 0, B, K, N, H, W, int(stride), int(config),
+            tag=f"conv1x1_K{K}_N{N}_P{Ho * Wo}")
+    return out if norm is not None else (out, stats)
+
+
+def conv3x3_stats(x: torch.Tensor, weight: torch.Tensor, groups: int, stride: int = 1, w_split: torch.Tensor | None = None,
+                  config: int = -1):
+    """conv3x3 on the split kernel without bias (the shapes of conv3x3_applies), plus the GroupNorm statistics of its output
+    from the epilogue: returns (out, stats), stats (B, groups, 2) fp64 as conv1x1_gn's.  `out` is bit for bit conv3x3's.
+    Needs conv_group_stats_applies(N, groups).  Inference, no autograd."""
+    if not conv3x3_applies(x, weight, stride):
+        raise ValueError("conv3x3_stats: shapes outside conv3x3_applies take conv3x3 and the separate GroupNorm passes")
+    x = _req(x, "x")
+    N, Cin = int(weight.shape[0]), int(weight.shape[1])
+    B, _, H, W = x.shape
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if w_split is None:
+        w_split = split_weight_3x3(_req(weight, "weight"))
+    elif w_split.dtype != torch.uint8 or w_split.numel() != N * 9 * Cin * 6 or w_split.device != x.device:
+        raise ValueError("conv3x3_stats: w_split is not split_weight_3x3(weight)")
+    out = torch.empty(B, N, Ho, Wo, device=x.device, dtype=torch.float32)
+    stats = torch.empty(B, int(groups), 2, device=x.device, dtype=torch.float64)
+    _launch("wm2f_conv3x3_split_stats_fwd", x, _p(x), _p(w_split), _p(out), _p(stats), int(groups), B, Cin, N, H, W, int(stride),
+            int(config), tag=f"conv3x3_C{Cin}_N{N}_P{Ho * Wo}")
+    return out, stats
+
+
 def conv3x3_applies(x: torch.Tensor, weight: torch.Tensor, stride: int = 1) -> bool:
     """Shapes wm2f_conv3x3_split_fwd is built for: fp32 NCHW on a GPU, weight (N, Cin, 3, 3) with Cin % 32 == 0 and
     N % 64 == 0, stride 1 or 2 (padding 1, dilation 1, one group), one image of x / out below 2 GiB, the split weight
