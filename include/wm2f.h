@@ -1268,6 +1268,50 @@ int wm2f_tile_link(const int32_t* hist, const int32_t* pairs, const int32_t* lab
 int wm2f_tile_compose(const void* tiles, int dtype, const int32_t* n_ids, const int32_t* geom, const int32_t* remap,
                       int32_t* out, int T, int th, int tw, int N, int H, int W, void* stream);
 
+/* ---- blending the class scores of overlapping tiles into one semantic map --------------------
+ * The semantic counterpart of the merge above: tiles carry class SCORES, not ids, and where tiles overlap their scores
+ * are blended under a feathering window before the argmax.  A view is one score grid per tile: the tiles as they are, or
+ * the result computed on a flipped tile (test-time augmentation), which is read at the mirrored pixel.
+ * tests/tile_blend_reference.py restates this contract in numpy, operation by operation.
+ * Arguments (every array is DEVICE memory; the call does not wait for the device):
+ *   scores (F, R * Cn, C, gh, gw) fp32: the (gh, gw) score grid of every class of every tile of every view; tiles are
+ *     numbered row-major over R tile rows and Cn tile columns, all of size (th, tw).
+ *   ys (R), xs (Cn) int32: the tile row / column origins in the image, ascending.
+ *   flips (F) int32: bit 0 -- the view was computed on the horizontally flipped tile, bit 1 -- on the vertically flipped
+ *     tile (other bits are ignored).
+ *   seg (H, W) int32 and out_scores (C, H, W) fp32 or NULL, both 8-byte aligned, overwritten.
+ * For output pixel (Y, X), in fp32 with every product, sum, difference and quotient below rounded on its own (no fused
+ * multiply-add anywhere; the file is built with -ffp-contract=off):
+ *   COVERING VIEWS  the covering rows are the r with ys[r] <= Y < ys[r] + th, the covering columns the c with
+ *                   xs[c] <= X < xs[c] + tw; n = F * #rows * #columns.
+ *   ORDER           views are visited with f ascending, then r ascending, then c ascending.
+ *   WEIGHT          y = Y - ys[r], x = X - xs[c]; the integers wy = min(y + 1, th - y, ramp_y) and
+ *                   wx = min(x + 1, tw - x, ramp_x); w = (float)(wy * wx) (an int32 product, converted once): a tent
+ *                   that rises by 1 per pixel from each tile border and is capped at the ramp.
+ *   SOLE VIEW       w = 1.0f when n == 1: a pixel that one view alone covers reproduces that tile's own sample.
+ *   SAMPLE          v_k = the bilinear resize (align_corners = False) of class k's grid scores[f][r * Cn + c][k] to
+ *                   (th, tw), taken at (sy, sx) = (bit 1 of flips[f] ? th - 1 - y : y, bit 0 ? tw - 1 - x : x) by the
+ *                   function the semantic post-processing resizes with (grid_logit of csrc/postprocess_grid.h):
+ *                     s = (float)gh / (float)th;  a = s * ((float)sy + 0.5f) - 0.5f;  a = a < 0 ? 0 : a;
+ *                     y0 = min((int)a, gh - 1);  y1 = y0 + (y0 < gh - 1);  ly = min(max(a - (float)y0, 0), 1);
+ *                     hy = 1 - ly; the same along x with gw, tw, sx -> x0, x1, lx, hx;
+ *                     t0 = hx * p[y0][x0] + lx * p[y0][x1];  t1 = hx * p[y1][x0] + lx * p[y1][x1];
+ *                     v = hy * t0 + ly * t1.
+ *   ACCUMULATION    acc_k and wsum start at 0; per view acc_k = acc_k + w * v_k and wsum = wsum + w.
+ *   OUTPUTS         seg = the first-max argmax over k of acc_k (k == 0 || acc_k > best, the rule of
+ *                   wm2f_semantic_resize_argmax); out_scores[k] = acc_k / wsum, correctly rounded, and acc_k itself
+ *                   when n == 1.
+ *   UNCOVERED       n == 0: seg = -1 and out_scores = 0.  Every output pixel is written.
+ * One launch, no workspace and no atomics: every result is bit-identical from run to run.  A lane owns two consecutive
+ * pixels of a row and stores 8 bytes at a time when W is even, pixel by pixel otherwise, with the same values; classes
+ * are held four at a time.  ys and xs need not be ascending for the result to follow the rules above, and no value in
+ * them makes the kernel read outside scores.
+ * F, R, Cn, C >= 1, ramp_y, ramp_x >= 1 and positive sizes, else WM2F_EINVAL; gh, gw, th, tw, H, W <= WM2F_TILE_MAX_SIDE
+ * and R * Cn <= WM2F_TILE_MAX_TILES, else WM2F_EUNSUPPORTED. */
+int wm2f_tile_blend(const void* scores, const int32_t* ys, const int32_t* xs, const int32_t* flips, int32_t* seg,
+                    void* out_scores, int F, int R, int Cn, int C, int gh, int gw, int th, int tw, int ramp_y, int ramp_x,
+                    int H, int W, void* stream);
+
 /* ---- repairing id maps: small pieces, largest piece, holes -----------------------------------
  * A predicted id map paints thresholded masks over one another: an id often owns one plant-sized piece plus detached
  * specks, and plants have pinholes.  This call repairs a whole (B, H, W) stack in a fixed chain of launches, whatever

@@ -181,6 +181,7 @@ SIGNATURES = {
     "wm2f_tile_owned_counts": (c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     "wm2f_tile_link": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "wm2f_tile_compose": (c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "wm2f_tile_blend": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_labelmap_clean_workspace": (c_int64, [_I, _I, _I, _I]),
     "wm2f_labelmap_clean": (c_int, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, c_int64, _I, c_int64, _I, _I, _P]),
 }

@@ -26,6 +26,38 @@ def _table(t: torch.Tensor, name: str, rows: int | None, cols: int, who: str) ->
     return t
 
 
+def tile_blend(scores: torch.Tensor, ys: torch.Tensor, xs: torch.Tensor, flips: torch.Tensor, size, tile_size, ramp,
+               want_scores: bool = False):
+    """scores (F, R * Cn, C, gh, gw) fp32 -- the score grid of every class of every tile of every view --, ys (R) and xs
+    (Cn) int32 tile origins, flips (F) int32 (bit 0: the view was computed on the horizontally flipped tile, bit 1: on the
+    vertically flipped one), size (H, W), tile_size (th, tw), ramp (ramp_y, ramp_x) -> seg (H, W) int32 and, with
+    want_scores, the blended scores (C, H, W) fp32, else None (wm2f_tile_blend): per output pixel the bilinear samples of
+    the covering views under a tent window capped at the ramp, summed in a fixed order, first-max argmax; -1 and zero
+    scores where no tile covers."""
+    scores = _req(scores, "scores", torch.float32)
+    ys, xs, flips = _req(ys, "ys", torch.int32), _req(xs, "xs", torch.int32), _req(flips, "flips", torch.int32)
+    if scores.dim() != 5 or 0 in scores.shape or ys.dim() != 1 or xs.dim() != 1 or flips.dim() != 1:
+        raise ValueError(f"tile_blend: scores must be a non-empty (F, T, C, gh, gw) stack and ys, xs, flips vectors, got "
+                         f"{tuple(scores.shape)}, {tuple(ys.shape)}, {tuple(xs.shape)}, {tuple(flips.shape)}")
+    F, T, C, gh, gw = (int(v) for v in scores.shape)
+    R, Cn = int(ys.shape[0]), int(xs.shape[0])
+    if R * Cn != T or int(flips.shape[0]) != F:
+        raise ValueError(f"tile_blend: {T} tiles and {F} views in scores, but {R} x {Cn} origins and {int(flips.shape[0])} flips")
+    for t, name in ((ys, "ys"), (xs, "xs"), (flips, "flips")):
+        if t.device != scores.device:
+            raise ValueError(f"tile_blend: {name} is on {t.device}, scores on {scores.device}")
+    (H, W), (th, tw), (ramp_y, ramp_x) = ((int(v[0]), int(v[1])) for v in (size, tile_size, ramp))
+    if H <= 0 or W <= 0 or th <= 0 or tw <= 0:
+        raise ValueError(f"tile_blend: bad size {(H, W)} or tile size {(th, tw)}")
+    if ramp_y < 1 or ramp_x < 1:
+        raise ValueError(f"tile_blend: the ramps must be at least 1, got {(ramp_y, ramp_x)}")
+    seg = torch.empty(H, W, device=scores.device, dtype=torch.int32)
+    out = torch.empty(C, H, W, device=scores.device, dtype=torch.float32) if want_scores else None
+    _launch("wm2f_tile_blend", scores, _p(scores), _p(ys), _p(xs), _p(flips), _p(seg), _p(out), F, R, Cn, C, gh, gw, th, tw,
+            ramp_y, ramp_x, H, W, tag="tile_blend")
+    return seg, out
+
+
 def tile_pair_counts(tiles: torch.Tensor, n_ids: torch.Tensor, pairs: torch.Tensor, N: int) -> torch.Tensor:
     """(T, th, tw) id maps (fp32 with -1 background, or int32), n_ids (T) int32, pairs (P, 8) int32 rows
     (a, b, ay, ax, by, bx, h, w) -> hist (P, N+1, N+1) int32, the joint histogram of tiles a and b over the rectangle they

@@ -11,8 +11,18 @@ neighbouring tiles are the same object, gives them one id and writes one id map 
 read each tile once, whatever the number of tiles, pairs and instances.  The contract of the merge is written out in
 include/wm2f.h.  Two instances of one tile may end up merged when a neighbour's instance links both.
 
-Not covered: rescaling before tiling (resize first), semantic and panoptic tiling (those blend logits, not ids), and
-test-time augmentation.
+The semantic task takes the same tiles but blends class scores, not ids:
+
+    result = segment_tiled_semantic(image, model, processor, flips=("none", "h"))
+    result["segmentation"]     # (H, W) int32 class ids on the device
+
+Every tile's (C, 384, 384) scores from `post_process_semantic_segmentation` are kept as they are; one kernel
+(csrc/tile_blend.hip) samples, per output pixel, every tile that covers it, weights the samples by a feathering window and
+takes the argmax.  Views computed on flipped tiles (horizontal / vertical flip test-time augmentation) are further
+covering views, read at the mirrored pixel.
+
+Not covered: rescaling before tiling (resize first), panoptic tiling, multi-scale test-time augmentation, and test-time
+augmentation for the instance route.
 """
 from __future__ import annotations
 
@@ -261,3 +271,118 @@ def segment_tiled(image, model, processor, tile: int = 1024, overlap: int = 256,
                 overlap_mask_area_threshold=overlap_mask_area_threshold, target_sizes=[(grid.th, grid.tw)] * len(batch))
     return merge_tile_results(results, grid, merge_threshold=merge_threshold, return_instance_stats=return_instance_stats,
                               clean=clean)
+
+
+# ---------------------------------------------------------------------------------------------- the semantic route
+FLIP_CODES = {"none": 0, "h": 1, "v": 2, "hv": 3}  # bit 0: horizontal flip, bit 1: vertical flip (include/wm2f.h)
+
+
+def _flip_codes(flips, who: str) -> list:
+    flips = [flips] if isinstance(flips, str) else list(flips)
+    if not flips:
+        raise ValueError(f"{who}: flips must name at least one view")
+    bad = [f for f in flips if f not in FLIP_CODES]
+    if bad:
+        raise ValueError(f"{who}: unknown flip {bad[0]!r}, expected one of {tuple(FLIP_CODES)}")
+    return [FLIP_CODES[f] for f in flips]
+
+
+def _axis_ramp(origins, side: int) -> int:
+    """The default ramp of one axis: the smallest overlap of two neighbouring tiles, at least 1 (1 with one tile)."""
+    gaps = [origins[i] + side - origins[i + 1] for i in range(len(origins) - 1)]
+    return max(1, min(gaps)) if gaps else 1
+
+
+def _check_cover(origins, side: int, length: int, axis: str) -> None:
+    o = [int(v) for v in origins]
+    if not o or o[0] != 0 or o[-1] + side < length or any(b <= a or b > a + side for a, b in zip(o, o[1:])):
+        raise ValueError(f"blend_tile_scores: the grid's {axis} origins {o[:8]} with side {side} do not cover [0, {length}) "
+                         "in ascending order without a gap")
+
+
+def blend_tile_scores(scores, grid: TileGrid, flips=("none",), ramp=None, return_scores: bool = False) -> dict:
+    """Blend per-tile class scores into one image's semantic result: {"segmentation": (H, W) int32 class ids on the
+    device, "scores": (C, H, W) fp32 with return_scores}.
+
+    `scores` is (F, T, C, gh, gw) fp32 on the device, or (T, C, gh, gw) for one view: for every view in `flips` (names out
+    of "none", "h", "v", "hv") and every tile in `grid` order, the (C, gh, gw) scores `post_process_semantic_segmentation(
+    target_sizes=None, return_segmentation_scores=True)` gave for that tile -- for a flipped view, computed on the flipped
+    tile and stored as they came out; the kernel reads them at the mirrored pixel.
+
+    Per output pixel every covering view is resized bilinearly (align_corners=False, as the post-processor resizes) to the
+    tile size on demand, weighted by a tent that rises by 1 per pixel from each tile border and is capped at `ramp`, and
+    summed in a fixed order; the map is the first-max argmax of the sums, the scores their weighted mean.  A pixel that one
+    view alone covers gets that tile's own result bit for bit.  `ramp` is an integer or (ramp_y, ramp_x); the default per
+    axis is the smallest overlap of two neighbouring tiles of `grid` (`TileGrid` does not record the overlap it was asked
+    for; `tile_windows` squeezes the origins, so the actual overlaps are at least that), and at least 1: the window then
+    reaches its plateau exactly where the narrowest overlap ends, and no seam is visible where tiles disagree.  The
+    contract is written out in include/wm2f.h (wm2f_tile_blend).  One kernel call; the (R + Cn + F) origins and flip codes
+    are the only host-to-device copy."""
+    who = "blend_tile_scores"
+    codes = _flip_codes(flips, who)
+    if not isinstance(scores, torch.Tensor):
+        raise TypeError(f"{who}: scores must be a tensor")
+    if scores.dim() == 4:
+        scores = scores.unsqueeze(0)
+    if scores.dim() != 5:
+        raise ValueError(f"{who}: scores must be (F, T, C, gh, gw) or (T, C, gh, gw), got {tuple(scores.shape)}")
+    if scores.shape[0] != len(codes) or scores.shape[1] != grid.n_tiles:
+        raise ValueError(f"{who}: scores hold {scores.shape[0]} views of {scores.shape[1]} tiles, expected {len(codes)} "
+                         f"views ({', '.join(flips) if not isinstance(flips, str) else flips}) of {grid.n_tiles} tiles")
+    _check_cover(grid.ys, grid.th, grid.height, "row")
+    _check_cover(grid.xs, grid.tw, grid.width, "column")
+    if ramp is None:
+        ramp = (_axis_ramp(grid.ys, grid.th), _axis_ramp(grid.xs, grid.tw))
+    elif isinstance(ramp, (int, np.integer)):
+        ramp = (int(ramp), int(ramp))
+    ramp = tuple(int(v) for v in ramp)
+    if len(ramp) != 2 or min(ramp) < 1:
+        raise ValueError(f"{who}: ramp must be an integer or (ramp_y, ramp_x), each at least 1, got {ramp}")
+    ops._core._on_gpu(scores, "scores")
+    R, Cn = len(grid.ys), len(grid.xs)
+    packed = np.asarray([*grid.ys, *grid.xs, *codes], dtype=np.int32)
+    d = torch.from_numpy(packed).pin_memory().to(scores.device, non_blocking=True)
+    seg, out = ops.tile_blend(scores, d[:R], d[R:R + Cn], d[R + Cn:], (grid.height, grid.width), (grid.th, grid.tw), ramp,
+                              want_scores=return_scores)
+    result = {"segmentation": seg}
+    if return_scores:
+        result["scores"] = out
+    return result
+
+
+def segment_tiled_semantic(image, model, processor, tile: int = 1024, overlap: int = 256, batch_size: int = 4,
+                           flips=("none",), return_scores: bool = False) -> dict:
+    """Semantic segmentation of an image of any size at native resolution: overlapping tiles (`tile_windows`), and per view
+    in `flips` (names out of "none", "h", "v", "hv": the tiles as they are, flipped horizontally, vertically, both)
+    `batch_size` tiles at a time -- flipped on the device with `torch.flip` -- through `processor(images=...)`,
+    `model(pixel_values=...)` under no_grad and `processor.post_process_semantic_segmentation(target_sizes=None,
+    return_segmentation_scores=True)`, whose (C, gh, gw) scores go straight into one preallocated (F, T, C, gh, gw) fp32
+    buffer of F * T * C * gh * gw * 4 bytes (6000 x 4000 at tile 1024, overlap 256: T = 40 tiles on the 384 x 384 grid,
+    71 MB per view at C = 3); then one `blend_tile_scores` call with the default ramp.  Image and processor as for
+    `segment_tiled`.  Returns {"segmentation": (H, W) int32 class ids, "scores": (C, H, W) fp32 with return_scores}, on
+    the device; nothing is copied to the host."""
+    who = "segment_tiled_semantic"
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f"{who}: batch_size must be at least 1, got {batch_size}")
+    codes = _flip_codes(flips, who)
+    img = _device_image(image)
+    grid = tile_windows(int(img.shape[0]), int(img.shape[1]), tile, overlap)
+    crops = [img[y0:y1, x0:x1] for y0, x0, y1, x1 in grid.windows]
+    buf = None
+    with torch.no_grad(), torch.cuda.device(img.device):
+        for v, code in enumerate(codes):
+            dims = [d for bit, d in ((2, 0), (1, 1)) if code & bit]
+            for s in range(0, len(crops), batch_size):
+                batch = crops[s:s + batch_size]
+                if dims:
+                    batch = [torch.flip(c, dims) for c in batch]
+                inputs = processor(images=batch)
+                outputs = model(pixel_values=inputs["pixel_values"])
+                res = processor.post_process_semantic_segmentation(outputs, target_sizes=None, return_segmentation_scores=True)
+                for j, r in enumerate(res):
+                    S = r["segmentation_scores"]
+                    if buf is None:
+                        buf = torch.empty(len(codes), len(crops), *S.shape, device=S.device, dtype=torch.float32)
+                    buf[v, s + j].copy_(S)
+    return blend_tile_scores(buf, grid, flips=flips, return_scores=return_scores)
