@@ -1,6 +1,8 @@
 """Training augmentation on the GPU: csrc/augment.hip through the processor, bit for bit against the
 Pillow fixture and against the composed route -- the host-flipped image through the un-augmented call at the full
-(h, w) frame, then a slice and a pad in torch.  Every comparison is torch.equal.  Needs an MI355X (-m gpu)."""
+(h, w) frame, then a slice and a pad in torch -- and, at the smallest shapes that reach every branch of the two
+kernels, against the numpy restatement (augment_reference.restate).  Every comparison is torch.equal.  Needs an MI355X
+(-m gpu)."""
 import json
 
 import numpy as np
@@ -180,14 +182,56 @@ def test_device_tensors_as_inputs(proc):
     _assert_equal(out, exp)
 
 
+def _restated(images, maps, id2sem, params, pad_size=None):
+    """The numpy restatement of the contract (augment_reference.restate) as device tensors."""
+    pv, pm, ml, cl = R.restate(images, maps, id2sem, params, pad_size, IG)
+    T = lambda a: torch.from_numpy(a).cuda()  # noqa: E731
+    return T(pv), T(pm), [T(a) for a in ml], [T(a) for a in cl]
+
+
 def test_identity_parameters_equal_the_unaugmented_call(proc):
+    """The two routes share their host rows and differ in the kernels the dispatch picks; the numpy restatement is the
+    expectation both are held to, so the equalities do not rest on either kernel."""
     im, m, d = _inputs(91, 333, 500)
     kw = dict(size={"height": 416, "width": 640}, size_divisor=0, ignore_index=IG)
     base = proc.preprocess([im], [m], d, **kw)
+    _assert_equal(base, _restated([im], [m], d, [AugmentParams.identity(416, 640)]))
     out = proc.preprocess([im], [m], d, augment=AugmentParams.identity(416, 640), ignore_index=IG)
     _assert_equal(out, (base["pixel_values"], base["pixel_mask"], base["mask_labels"], base["class_labels"]))
     none = proc.preprocess([im], [m], d, augment=None, **kw)  # bit-identical to a call without the keyword
     _assert_equal(none, (base["pixel_values"], base["pixel_mask"], base["mask_labels"], base["class_labels"]))
+
+
+# ------------------------------------------------------------------------------------------------ every kernel branch
+# source (H, W), flip, frame, origin, window, pad: the smallest shapes that reach each branch of the two kernels
+BRANCH_CASES = [
+    # upscale, 3 row tiles x 3 column tiles, Wp % 4 = 2 (scalar stores), padding rows and columns
+    ("upscale_scalar_stores", (37, 150), 0, (61, 391), (3, 5), (45, 263), {"height": 48, "width": 270}),
+    ("upscale_mirrored_vector_stores", (37, 150), 1, (61, 391), (3, 5), (45, 263), {"height": 48, "width": 272}),
+    # 7 column taps (coefficients read from the table), a 16-row tile reaching 297 source rows (5 rounds of 64), and
+    # a last tile of one round
+    ("table_taps_five_rounds_mirrored", (700, 520), 1, (40, 150), (5, 7), (33, 140), None),
+    ("identity_window", (700, 520), 0, (40, 150), (0, 0), (40, 150), None),  # what a plain call fills in
+]
+
+
+@pytest.mark.parametrize("case", BRANCH_CASES, ids=lambda c: c[0])
+def test_every_kernel_branch_equals_the_restatement(proc, case):
+    _, hw, flip, frame, origin, window, pad = case
+    im, m, d = _inputs(95, *hw)
+    p = [AugmentParams(flip, frame, origin, window)]
+    out = proc.preprocess([im], [m], d, augment=p, pad_size=pad, ignore_index=IG)
+    _assert_equal(out, _restated([im], [m], d, p, pad))
+
+
+def test_plain_call_with_several_row_rounds_equals_its_own_restatement(proc):
+    """The identity case above without `augment`, against the restatement of DESIGN section 12."""
+    from test_preprocess_cpu import restate
+    im, m, d = _inputs(95, 700, 520)
+    kw = dict(size={"height": 40, "width": 150}, size_divisor=0, ignore_index=IG)
+    pv, pm, ml, cl = restate([im], [m], d, **kw)
+    T = lambda a: torch.from_numpy(a).cuda()  # noqa: E731
+    _assert_equal(proc.preprocess([im], [m], d, **kw), (T(pv), T(pm), [T(a) for a in ml], [T(a) for a in cl]))
 
 
 def test_kernel_rejects_what_it_does_not_build(proc):

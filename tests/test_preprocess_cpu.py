@@ -226,6 +226,34 @@ def test_only_bilinear_images():
         Mask2FormerImageProcessor(resample=0)
 
 
+def test_plain_rows_are_the_identity_window_rows_in_the_plain_layout():
+    """The processor builds one set of rows (16 and 12 columns, the identity window for a call without `augment`) and
+    hands the plain kernels their (B, 12) / (B, 7) layout through `_plain_rows`.  The expected rows are written out
+    here column by column, table offsets in the order the tables are laid out and workspace offsets as a running sum."""
+    sizes_in = [(37, 150), (700, 520), (64, 48)]   # an upscale, a heavy downscale, an unchanged size
+    frames = [(61, 391), (40, 150), (64, 48)]
+    plain, lplain, n_tab, ws_off, in_off = [], [], 0, 0, 0
+    for (H, W), (h, w) in zip(sizes_in, frames):
+        (bx, cx), (by, cy) = P.bilinear_tables(W, w), P.bilinear_tables(H, h)
+        sizes = [bx.size, cx.size, by.size, cy.size, w, h]
+        tx, ox, ty, oy, xi, yi = (n_tab + int(v) for v in np.cumsum([0] + sizes[:-1]))
+        n_tab += sum(sizes)
+        plain.append([in_off * 3, ws_off, H, W, h, w, tx, ox, cx.shape[1], ty, oy, cy.shape[1]])
+        lplain.append([in_off, H, W, h, w, xi, yi])
+        ws_off += H * w * 3
+        in_off += H * W
+    desc, ldesc, tables = P._descriptors(sizes_in, frames, [[0, 0, 0, h, w] for h, w in frames], True)
+    assert tables.dtype == np.int32 and tables.size == n_tab
+    assert desc.shape == (3, 16) and ldesc.shape == (3, 12)
+    for d in (desc, ldesc):
+        assert np.array_equal(d[:, -5:], [[0, 0, 0, h, w] for h, w in frames])
+    desc[:, 0] = [r[0] for r in plain]
+    ldesc[:, 0] = [r[0] for r in lplain]
+    got, lgot = P._plain_rows(desc, ldesc)
+    assert got.dtype == np.int64 and np.array_equal(got, plain)
+    assert lgot.dtype == np.int64 and np.array_equal(lgot, lplain)
+
+
 def test_package_exports_the_processor():
     import weed_instance_segmentation_amd as pkg
     from weed_instance_segmentation_amd.postprocess import Mask2FormerInstancePostProcessor

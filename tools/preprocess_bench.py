@@ -1,13 +1,16 @@
-"""Device preprocessing timing: `Mask2FormerImageProcessor` at B = 8 for 1024 x 768 -> 800 x 1088
-and 1024 x 1024 -> 1024 x 1024 (`size={"height": 1024, "width": 1024}`), without and with 16-instance maps.  One JSON
-line per case, appended to profiles/r05_preprocess_bench.jsonl.
+"""Device preprocessing timing: `Mask2FormerImageProcessor` at B = 8 for 1024 x 768 -> 800 x 1088,
+1024 x 1024 -> 1024 x 1024 (`size={"height": 1024, "width": 1024}`) and the reference's field-image size 4000 x 3000 ->
+800 x 1088, each without and with 16-instance maps.  One JSON line per case, appended to
+profiles/r05_preprocess_bench.jsonl.
 
-    python tools/preprocess_bench.py [--reps 20] [--out profiles/r05_preprocess_bench.jsonl]
+    python tools/preprocess_bench.py [--reps 20] [--out profiles/r05_preprocess_bench.jsonl] [--tree NAME]
 
-`kernel_ms`: HIP events around the two resize kernels alone (the image call of ops.resize_normalize_u8, inputs already
-on the device); `gbps`: 3 B/px read at the input size plus 3 B/px written and read for the intermediate and 12 + 8 B/px
-written at the output size, over kernel_ms.  `wall_ms`: the whole processor call, synchronised, with the uint8
-host-to-device copy.  `dependency_ms`: Mask2FormerImageProcessorPil on the host for the same batch, only where
+`kernel_ms`: HIP events around the image call of ops.resize_normalize_u8 alone (inputs already on the device);
+`gbps`: 3 B/px read at the input size plus 3 B/px written and read for the row-pass intermediate and 12 + 8 B/px
+written at the output size, over kernel_ms (the byte count of the two-pass kernels, kept so that records compare).
+`label_kernel_ms`: the same around ops.resize_nearest_labels alone, on the lines with maps.  `wall_ms`: the whole
+processor call, synchronised, with the uint8 host-to-device copy.  `--tree` adds a `tree` field to every line, for
+records that compare two builds.  `dependency_ms`: Mask2FormerImageProcessorPil on the host for the same batch, only where
 transformers imports (`host_cores` says how many the host has).
 """
 from __future__ import annotations
@@ -43,8 +46,33 @@ def batch(B, H, W, n_ids, seed=0):
     return ims, maps
 
 
+def event_ms(call, reps):
+    for _ in range(3):
+        call()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        call()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return float(np.median(ts))
+
+
+def label_kernel_ms(maps, size, reps):
+    """The label call alone on device-resident maps, index tables built once."""
+    H, W = maps[0].shape
+    h, w = P.output_size(H, W, size, 32)
+    tab = np.concatenate([P.nearest_table(W, w), P.nearest_table(H, h)]).astype(np.int32)
+    desc = np.array([[b * H * W, H, W, h, w, 0, w] for b in range(len(maps))], np.int64)
+    dev = torch.from_numpy(np.stack(maps).reshape(-1)).cuda()
+    t_tab = torch.from_numpy(tab).cuda()
+    return event_ms(lambda: ops.resize_nearest_labels(dev, desc, t_tab, h, w, 255), reps)
+
+
 def kernel_ms(ims, size, reps):
-    """The image kernels alone on device-resident inputs, tables built once."""
+    """The image call alone on device-resident inputs, tables built once."""
     H, W = ims[0].shape[:2]
     h, w = P.output_size(H, W, size, 32)
     bx, cx = P.bilinear_tables(W, w)
@@ -57,17 +85,7 @@ def kernel_ms(ims, size, reps):
     img = torch.from_numpy(np.stack(ims).reshape(-1)).cuda()
     t_tab = torch.from_numpy(tab).cuda()
     lut = torch.from_numpy(P.normalize_table(True, 1 / 255, True, P.IMAGENET_DEFAULT_MEAN, P.IMAGENET_DEFAULT_STD)).cuda()
-    for _ in range(3):
-        ops.resize_normalize_u8(img, desc, t_tab, lut, h, w)
-    ts = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        ops.resize_normalize_u8(img, desc, t_tab, lut, h, w)
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b))
-    ms = float(np.median(ts))
+    ms = event_ms(lambda: ops.resize_normalize_u8(img, desc, t_tab, lut, h, w), reps)
     nbytes = B * (H * W * 3 + 2 * H * w * 3 + h * w * (12 + 8))
     return ms, nbytes / ms / 1e6, (h, w)
 
@@ -76,6 +94,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r05_preprocess_bench.jsonl"))
+    ap.add_argument("--tree", default=None)
     args = ap.parse_args()
     try:
         from transformers.models.mask2former.image_processing_pil_mask2former import Mask2FormerImageProcessorPil
@@ -86,7 +105,8 @@ def main():
     B = 8
     recs = []
     for (H, W, size) in [(768, 1024, {"shortest_edge": 800, "longest_edge": 1333}),
-                         (1024, 1024, {"height": 1024, "width": 1024})]:
+                         (1024, 1024, {"height": 1024, "width": 1024}),
+                         (3000, 4000, {"shortest_edge": 800, "longest_edge": 1333})]:
         for n_ids in (0, 16):
             ims, maps = batch(B, H, W, n_ids)
             kw = dict(images=ims, segmentation_maps=maps, size=size, ignore_index=255,
@@ -105,6 +125,10 @@ def main():
                    "n_ids": n_ids, "kernel_ms": round(k_ms, 4), "kernel_gbps": round(gbps, 1),
                    "kernel_frac_of_8TBps": round(gbps / 8000, 3), "wall_ms": round(float(np.median(ts)), 3),
                    "device": torch.cuda.get_device_name(0), "reps": args.reps}
+            if maps:
+                rec["label_kernel_ms"] = round(label_kernel_ms(maps, size, args.reps), 4)
+            if args.tree:
+                rec["tree"] = args.tree
             if dep is not None:
                 t0 = time.perf_counter()
                 dep(return_tensors="pt", **kw)

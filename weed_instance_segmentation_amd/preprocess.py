@@ -15,7 +15,9 @@ count and 22-bit fixed-point coefficients per output column and row; nearest: on
 row) and a (3, 256) float32 table of the rescaled, normalised value of every (channel, byte).  These, the uint8 images
 and the uint8 maps travel in ONE pinned host buffer per call.  The pixels are touched only by the HIP kernels of
 csrc/preprocess.hip (`wm2f_resize_normalize_u8`, `wm2f_resize_nearest_labels`) and `wm2f_labelmap_to_masks`; the
-unique ids of the resized maps come back as (B, 256) presence flags in one device-to-host copy.
+unique ids of the resized maps come back as (B, 256) presence flags in one device-to-host copy.  A call without
+`augment` is described as the identity window of the augmentation (no flip, origin (0, 0), the whole resized frame;
+DESIGN section 20), so one set of host rows serves both; only the dispatch tells the two pairs of kernels apart.
 """
 from __future__ import annotations
 
@@ -207,6 +209,38 @@ def _aligned(n: int) -> int:
     return (n + 63) // 64 * 64
 
 
+def _descriptors(sizes_in, frames, wins, with_maps: bool):
+    """The host rows of include/wm2f.h for (H, W) sources resized to (h, w) `frames` and cut to `wins` = (flip, y0, x0,
+    ch, cw): (desc (B, 16) int64, ldesc (B, 12) int64, tables int32), column 0 (the input offsets) left 0.  The tables
+    are those of the whole frame; the kernels index them at the window's origin."""
+    parts, n_tab = [], 0
+
+    def put(a):
+        nonlocal n_tab
+        a = np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+        off = n_tab
+        parts.append(a)
+        n_tab += a.size
+        return off
+
+    desc = np.zeros((len(sizes_in), 16), dtype=np.int64)
+    ldesc = np.zeros((len(sizes_in), 12), dtype=np.int64)
+    for b, ((H, W), (h, w)) in enumerate(zip(sizes_in, frames)):
+        bx, cx = bilinear_tables(W, w)
+        by, cy = bilinear_tables(H, h)
+        desc[b, 1:] = [H, W, h, w, put(bx), put(cx), cx.shape[1], put(by), put(cy), cy.shape[1], *wins[b]]
+        if with_maps:
+            ldesc[b, 1:] = [H, W, h, w, put(nearest_table(W, w)), put(nearest_table(H, h)), *wins[b]]
+    return desc, ldesc, np.concatenate(parts)
+
+
+def _plain_rows(desc: np.ndarray, ldesc: np.ndarray):
+    """The rows of `_descriptors` at the identity window as the plain kernels of csrc/preprocess.hip take them: (B, 12)
+    with the running workspace offset of the (H, w, 3) intermediates behind column 0, and (B, 7)."""
+    ws_off = np.cumsum(desc[:, 1] * desc[:, 4] * 3) - desc[:, 1] * desc[:, 4] * 3
+    return np.column_stack([desc[:, 0], ws_off, desc[:, 1:11]]), ldesc[:, :7]
+
+
 # ------------------------------------------------------------------------------------------------ processor
 class Mask2FormerImageProcessor(Mask2FormerInstancePostProcessor):
     """`Mask2FormerImageProcessorPil` of transformers 5.15.0 on the GPU: same keywords and defaults, same outputs bit
@@ -342,9 +376,11 @@ class Mask2FormerImageProcessor(Mask2FormerInstancePostProcessor):
         if augs is not None:
             frames = [a.size for a in augs]
             sizes_out = [a.window for a in augs]  # what the image occupies in the padded output
-        else:
-            sizes_out = [output_size(H, W, s["size"], s["size_divisor"]) if s["do_resize"] else (H, W)
-                         for H, W in sizes_in]
+            wins = [[a.flip, *a.origin, *a.window] for a in augs]
+        else:  # the identity window: no flip, the whole resized frame
+            frames = sizes_out = [output_size(H, W, s["size"], s["size_divisor"]) if s["do_resize"] else (H, W)
+                                  for H, W in sizes_in]
+            wins = [[0, 0, 0, h, w] for h, w in frames]
         if s["pad_size"] is not None:
             ps = s["pad_size"]
             Hp, Wp = (int(ps["height"]), int(ps["width"])) if isinstance(ps, dict) else (int(ps[0]), int(ps[1]))
@@ -355,34 +391,7 @@ class Mask2FormerImageProcessor(Mask2FormerInstancePostProcessor):
                 raise ValueError(f"Padding dimensions are negative. Please make sure that the padded size is larger than "
                                  f"the original size. Got padded size: {(Hp, Wp)}, original size: {(h, w)}.")
 
-        # host tables: int32, one array; descriptors stay on the host
-        parts, n_tab = [], 0
-
-        def put(a):
-            nonlocal n_tab
-            a = np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
-            off = n_tab
-            parts.append(a)
-            n_tab += a.size
-            return off
-
-        desc = np.zeros((B, 12 if augs is None else 16), dtype=np.int64)
-        ldesc = np.zeros((B, 7 if augs is None else 12), dtype=np.int64)
-        ws_off = 0
-        for b, ((H, W), (h, w)) in enumerate(zip(sizes_in, sizes_out if augs is None else frames)):
-            bx, cx = bilinear_tables(W, w)
-            by, cy = bilinear_tables(H, h)
-            if augs is not None:  # whole tables of the (h, w) frame; the kernels index them at the window's origin
-                win = [augs[b].flip, *augs[b].origin, *augs[b].window]
-                desc[b, 1:] = [H, W, h, w, put(bx), put(cx), cx.shape[1], put(by), put(cy), cy.shape[1], *win]
-                if maps is not None:
-                    ldesc[b, 1:] = [H, W, h, w, put(nearest_table(W, w)), put(nearest_table(H, h)), *win]
-                continue
-            desc[b, 1:] = [ws_off, H, W, h, w, put(bx), put(cx), cx.shape[1], put(by), put(cy), cy.shape[1]]
-            ws_off += H * w * 3
-            if maps is not None:
-                ldesc[b, 1:] = [H, W, h, w, put(nearest_table(W, w)), put(nearest_table(H, h))]
-        tables = np.concatenate(parts)
+        desc, ldesc, tables = _descriptors(sizes_in, frames, wins, maps is not None)
         lut = normalize_table(s["do_rescale"], s["rescale_factor"], s["do_normalize"], s["image_mean"], s["image_std"])
 
         # one pinned buffer: tables | lut | host images | host maps
@@ -440,10 +449,13 @@ class Mask2FormerImageProcessor(Mask2FormerInstancePostProcessor):
                              dtype=np.int64)
             ops.orient_u8(buf[o_img:o_img + int(img_off[-1])], buf[o_rimg:o_rimg + int(img_off[-1])], odesc)
             o_img = o_rimg
+        # One descriptor layout up to here.  The plain call keeps kernels of its own only because they measured faster
+        # than the identity window of the augmentation kernels at field-image sizes.
+        resize_images, resize_labels = ops.augment_resize_normalize_u8, ops.augment_nearest_labels
         if augs is None:
-            pv, pm = ops.resize_normalize_u8(buf[o_img:o_img + int(img_off[-1])], desc, t_tab, t_lut, Hp, Wp)
-        else:
-            pv, pm = ops.augment_resize_normalize_u8(buf[o_img:o_img + int(img_off[-1])], desc, t_tab, t_lut, Hp, Wp)
+            resize_images, resize_labels = ops.resize_normalize_u8, ops.resize_nearest_labels
+            desc, ldesc = _plain_rows(desc, ldesc)
+        pv, pm = resize_images(buf[o_img:o_img + int(img_off[-1])], desc, t_tab, t_lut, Hp, Wp)
         out = BatchFeature(pixel_values=pv, pixel_mask=pm)
         if maps is None:
             return out
@@ -463,7 +475,6 @@ class Mask2FormerImageProcessor(Mask2FormerInstancePostProcessor):
             odesc[:, 19] = fills
             ops.orient_labels(buf[o_map:o_map + int(map_off[-1])], buf[o_rmap:o_rmap + int(map_off[-1])], odesc)
             o_map = o_rmap
-        resize_labels = ops.resize_nearest_labels if augs is None else ops.augment_nearest_labels
         lab, present = resize_labels(buf[o_map:o_map + int(map_off[-1])], ldesc, t_tab, Hp, Wp,
                                      255 if ig is None else int(ig))
         flags = present.cpu().numpy()
