@@ -507,6 +507,45 @@ int wm2f_group_norm_tokens_apply(const void* x, const void* bias, const void* ga
 int wm2f_stem7x7_pool_fwd(const void* x, const void* w_split, const void* bias, void* out, int B, int Cin, int N, int Hi,
                           int Wi, int grid, void* stream);
 
+/* Selectable precision of the split-bf16 GEMMs and convolutions (inference).  Every forward entry point above
+ * has a variant that takes a trailing `int pieces` before `stream`; the entry point without it means pieces = 3.  With the
+ * operands written as three bf16 pieces a = h + m + l (h = bf16 of a clamped to the largest finite bf16, m = bf16(a - h),
+ * l = bf16(a - h - m)), W pieces first, a 32-deep k-step sums
+ *     pieces = 3  "highest"  all six products  m.m, l.h, h.l, m.h, h.m, h.h          e <= 2 e32 + 2^-23   (§13)
+ *     pieces = 2  "high"     three products    m.h, h.m, h.h  (in this order, the one they have in the six-product chain)
+ *                                                                                  e <= 2 e32 + 2^-14
+ *     pieces = 1  "medium"   one product       h.h                                  e <= 2 e32 + 2^-6
+ * where e = max |out - ref64| / (sum_k |x_k w_k| + |bias| + |residual|) and e32 is the same measure of an fp32 computation.
+ * The floors: at two pieces the dropped h.l, l.h and m.m are each at most 2^-16 (1 + 2^-7) sum |x_k w_k| (|m| <= 2^-8 |a|,
+ * |a - h - m| <= 2^-16 |a|), three of them stay below 2^-14; at one piece |a - h| <= 2^-8 |a| (with the clamp) on both
+ * operands gives 2^-7 + 2^-16 < 2^-6.  Operands that are exact in bf16 (small integers, bf16 data) give the same bits at
+ * every level.  pieces = 1 computes, bit for bit, what pieces = 3 computes on the operands rounded to their h piece.
+ * Everything else is per level what it is at pieces = 3: the accumulation structure of each kernel (the convolutions and the
+ * stem sum a k-step from zero and add it to the accumulator once, the token kernel chains into the accumulator), the
+ * epilogues, the tile tables and the host's choice among them, the refusals, the determinism (no split-K, no output atomics:
+ * one MFMA sequence per output under every tile configuration, batch and sub-batch) and the non-finite rule: an inf or a NaN
+ * in x makes every output it touches non-finite (at pieces = 1, where no residual piece carries it on, the h piece itself is
+ * made NaN for a non-finite x; finite values as large as FLT_MAX stay finite, clamped).
+ * w_split is ALWAYS the three-piece split of wm2f_token_linear_split_weight, N * K * 6 bytes: its first `pieces` pieces per
+ * row tile are the `pieces`-piece split, and a kernel loads and stages only those (x is split into `pieces` pieces only).
+ * A `pieces` value outside {1, 2, 3} returns WM2F_EINVAL with nothing launched and the outputs untouched. */
+int wm2f_token_linear_split_fwd_p(const void* x, const void* w_split, const void* bias, const void* residual,
+                                  const void* ln_gamma, const void* ln_beta, const void* pos, void* out, void* out_plus_pos,
+                                  int64_t M, int K, int N, int relu, int64_t pos_rows, float eps, int out_group, int pieces,
+                                  void* stream);
+int wm2f_conv1x1_split_fwd_p(const void* x, const void* w_split, const void* bias, const void* residual, void* out, int B, int K,
+                             int N, int Hi, int Wi, int stride, int relu, int config, int pieces, void* stream);
+int wm2f_conv1x1_split_gn_fwd_p(const void* x, const void* w_split, const void* bias, void* out, void* stats_out, int G_out,
+                                const void* norm_stats, const void* norm_gamma, const void* norm_beta, int norm_G, float norm_eps,
+                                int norm_relu, int B, int K, int N, int Hi, int Wi, int stride, int config, int pieces,
+                                void* stream);
+int wm2f_conv3x3_split_fwd_p(const void* x, const void* w_split, const void* bias, void* out, int B, int Cin, int N, int Hi,
+                             int Wi, int stride, int relu, int config, int pieces, void* stream);
+int wm2f_conv3x3_split_stats_fwd_p(const void* x, const void* w_split, void* out, void* stats_out, int G_out, int B, int Cin,
+                                   int N, int Hi, int Wi, int stride, int config, int pieces, void* stream);
+int wm2f_stem7x7_pool_fwd_p(const void* x, const void* w_split, const void* bias, void* out, int B, int Cin, int N, int Hi,
+                            int Wi, int grid, int pieces, void* stream);
+
 /* wm2f_token_wgrad_bf16: the weight / bias gradient of such a Linear (the backward autograd derives for nn.Linear; train
  *                        step of HF:1036-1103 under bf16 autocast):  dw (N, K) fp32 = dy (M, N)^T . x (M, K),
  *                        db (N) fp32 = column sums of dy (NULL: skipped); dy, x bf16 row-major, fp32 accumulation on the bf16

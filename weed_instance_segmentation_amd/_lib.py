@@ -119,6 +119,13 @@ SIGNATURES = {
     "wm2f_group_norm_act_apply": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, c_float, _I, _P]),
     "wm2f_group_norm_tokens_apply": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, c_float, _P]),
     "wm2f_stem7x7_pool_fwd":(c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    # the same entry points with a trailing `pieces` before the stream
+    "wm2f_token_linear_split_fwd_p": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _I, _I, _I, c_int64, c_float, _I, _I, _P]),
+    "wm2f_conv1x1_split_fwd_p": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "wm2f_conv1x1_split_gn_fwd_p": (c_int, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, c_float, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "wm2f_conv3x3_split_fwd_p": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "wm2f_conv3x3_split_stats_fwd_p": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "wm2f_stem7x7_pool_fwd_p": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_token_wgrad_workspace": (c_int64, [c_int64, _I, _I]),
     "wm2f_token_wgrad_bf16": (c_int, [_P, _P, _P, _P, _P, c_int64, _I, _I, _P]),
     "wm2f_token_wgrad_f32": (c_int, [_P, _P, _P, _P, _P, c_int64, _I, _I, _P]),

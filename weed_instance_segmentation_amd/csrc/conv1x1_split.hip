@@ -48,15 +48,25 @@ constexpr float kBf16Max = 3.38953139e38f;  // largest finite bf16, 0x7F7F
 // epilogues, fixed at compile time
 enum : int { kRaw = 0, kBias = 1, kBiasRelu = 2, kBiasResRelu = 3 };
 
+// the first P pieces of the three-piece split (the pieces past P are left untouched and never read)
+template <int P>
 __device__ __forceinline__ void split3(const f32x8 x, bf16x8& h, bf16x8& m, bf16x8& l) {
   f32x8 xc;
 #pragma unroll
   for (int i = 0; i < 8; ++i) xc[i] = __builtin_amdgcn_fmed3f(x[i], -kBf16Max, kBf16Max);
+  if constexpr (P == 1) {  // no residual piece carries an inf or a NaN on: x * 0 (0, or NaN) keeps h non-finite with x
+#pragma unroll
+    for (int i = 0; i < 8; ++i) xc[i] = __builtin_fmaf(x[i], 0.f, xc[i]);
+  }
   h = __builtin_convertvector(xc, bf16x8);
-  const f32x8 r1 = x - __builtin_convertvector(h, f32x8);
-  m = __builtin_convertvector(r1, bf16x8);
-  const f32x8 r2 = r1 - __builtin_convertvector(m, f32x8);
-  l = __builtin_convertvector(r2, bf16x8);
+  if constexpr (P >= 2) {
+    const f32x8 r1 = x - __builtin_convertvector(h, f32x8);
+    m = __builtin_convertvector(r1, bf16x8);
+    if constexpr (P >= 3) {
+      const f32x8 r2 = r1 - __builtin_convertvector(m, f32x8);
+      l = __builtin_convertvector(r2, bf16x8);
+    }
+  }
 }
 
 struct C1Args {
@@ -85,12 +95,15 @@ __device__ __forceinline__ void c1_barrier() {
 // STATS: the epilogue also reduces the group statistics of what it stores (gn_tile_stats; cpg in {4, 8, 16}).
 // NORM: every loaded element becomes act(scale[b][k] x + shift[b][k]) before the split, the K pairs computed once per
 // workgroup into LDS behind the ring (gn_affine / gn_apply: the bits group_norm_apply_kernel writes).
-template <int NRT, int WN, int EPI, bool STATS = false, bool NORM = false>
+// P = the pieces of each operand that take part: 3 = all six products, 2 = h and m (m.h, h.m, h.h), 1 = h
+// alone (h.h).  The split weight is the three-piece one at every P; the ring holds the first P pieces of each row tile.
+template <int NRT, int WN, int EPI, bool STATS = false, bool NORM = false, int P = 3>
 __global__ __launch_bounds__(kThreads) void conv1x1_split_kernel(C1Args a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [2][NT / 16][3][64][16 B] (+ NORM: [2][K] floats)
+  static_assert(P >= 1 && P <= 3, "one, two or three pieces");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [2][NT / 16][P][64][16 B] (+ NORM: [2][K] floats)
   constexpr int kRowTiles = WN * NRT;
-  constexpr int kPanelBytes = kRowTiles * 3 * kFrag;
-  constexpr int kPieces = kRowTiles * 3;
+  constexpr int kPanelBytes = kRowTiles * P * kFrag;
+  constexpr int kPieces = kRowTiles * P;
   constexpr int kPT = (kWaves / WN) * kCT * 16;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wn = wave % WN, wp = wave / WN;
@@ -132,8 +145,10 @@ __global__ __launch_bounds__(kThreads) void conv1x1_split_kernel(C1Args a) {
   auto issue = [&](int ks) {
     unsigned char* dst = smem + (ks & 1) * kPanelBytes;
     const int src = (ks * (a.N / 16) + n_wg / 16) * 3 * kFrag;
-    for (int f = wave; f < kPieces; f += kWaves)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rs, (lds_ptr_t)(dst + f * kFrag), 16, lane * 16, src + f * kFrag, 0, 0);
+    for (int f = wave; f < kPieces; f += kWaves) {
+      const int fs = P == 3 ? f : (f / P) * 3 + f % P;  // ring piece f = piece f % P of row tile f / P
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rs, (lds_ptr_t)(dst + f * kFrag), 16, lane * 16, src + fs * kFrag, 0, 0);
+    }
     const unsigned kb = (unsigned)(ks * kKStep) * ch_bytes;
 #pragma unroll
     for (int c = 0; c < kCT; ++c) {
@@ -167,23 +182,28 @@ __global__ __launch_bounds__(kThreads) void conv1x1_split_kernel(C1Args a) {
         }
     }
 #pragma unroll
-    for (int c = 0; c < kCT; ++c) split3(xr[c], bh[c], bm[c], bl[c]);
+    for (int c = 0; c < kCT; ++c) split3<P>(xr[c], bh[c], bm[c], bl[c]);
     if (ks + 1 < n_ks) issue(ks + 1);  // the next step's loads fly under this step's MFMAs
 
-    const unsigned char* panel = smem + (ks & 1) * kPanelBytes + wn * NRT * 3 * kFrag;
+    const unsigned char* panel = smem + (ks & 1) * kPanelBytes + wn * NRT * P * kFrag;
     auto read_a = [&](bf16x8 (&dst)[3], int rt) {
 #pragma unroll
-      for (int p = 0; p < 3; ++p) dst[p] = *reinterpret_cast<const bf16x8*>(panel + (rt * 3 + p) * kFrag + lane * 16);
+      for (int p = 0; p < P; ++p) dst[p] = *reinterpret_cast<const bf16x8*>(panel + (rt * P + p) * kFrag + lane * 16);
     };
     // the six products of one (row tile, column tile), the small terms first, summed from zero and added to the
     // accumulator once per k-step: the accumulator takes K / 32 roundings, not 6 K / 32 (at K = 2048 the six MFMAs
     // straight into it measured 2.6x the error of the fp32 library convolution against fp64)
     auto six = [&](f32x4 acc_in, const bf16x8 (&av)[3], int cc) {
-      f32x4 c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1], bm[cc], (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[2], bh[cc], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bl[cc], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1], bh[cc], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bm[cc], c, 0, 0, 0);
+      f32x4 c = {0.f, 0.f, 0.f, 0.f};
+      if constexpr (P == 3) {
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1], bm[cc], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[2], bh[cc], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bl[cc], c, 0, 0, 0);
+      }
+      if constexpr (P >= 2) {  // P = 2: m.h, h.m, h.h, the order they have in the six-product chain
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1], bh[cc], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bm[cc], c, 0, 0, 0);
+      }
       return acc_in + __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bh[cc], c, 0, 0, 0);
     };
     bf16x8 av[2][3];
@@ -241,7 +261,7 @@ __global__ __launch_bounds__(kThreads) void conv1x1_split_kernel(C1Args a) {
   if (STATS) gn_tile_stats<NRT, WN, kWaves>(gs, gss, smem, a.stats, b * a.G, n_wg, a.cpg, tid);
 }
 
-// The configurations, (NRT, WN): workgroup tile NT x PT = (WN NRT 16) x (8 / WN x 32).  The LDS ring is 2 x NT x 192 B.
+// The configurations, (NRT, WN): workgroup tile NT x PT = (WN NRT 16) x (8 / WN x 32).  The LDS ring is 2 x NT x 64 P B.
 struct Cfg {
   int nrt, wn;
 };
@@ -251,26 +271,32 @@ constexpr int kNumCfg = sizeof(kCfg) / sizeof(kCfg[0]);
 // The instances: the four epilogues; the statistics on raw and + bias; the normalised operand on + bias.
 enum : int { kPlain = 0, kStats = 1, kNorm = 2 };
 
-template <int NRT, int WN>
+template <int NRT, int WN, int P>
 void (*pick_epi(int epi, int opt))(C1Args) {
-  if (opt == kStats) return epi == kRaw ? conv1x1_split_kernel<NRT, WN, kRaw, true> : conv1x1_split_kernel<NRT, WN, kBias, true>;
-  if (opt == kNorm) return conv1x1_split_kernel<NRT, WN, kBias, false, true>;
+  if (opt == kStats)
+    return epi == kRaw ? conv1x1_split_kernel<NRT, WN, kRaw, true, false, P> : conv1x1_split_kernel<NRT, WN, kBias, true, false, P>;
+  if (opt == kNorm) return conv1x1_split_kernel<NRT, WN, kBias, false, true, P>;
   switch (epi) {
-    case kRaw: return conv1x1_split_kernel<NRT, WN, kRaw>;
-    case kBias: return conv1x1_split_kernel<NRT, WN, kBias>;
-    case kBiasRelu: return conv1x1_split_kernel<NRT, WN, kBiasRelu>;
-    default: return conv1x1_split_kernel<NRT, WN, kBiasResRelu>;
+    case kRaw: return conv1x1_split_kernel<NRT, WN, kRaw, false, false, P>;
+    case kBias: return conv1x1_split_kernel<NRT, WN, kBias, false, false, P>;
+    case kBiasRelu: return conv1x1_split_kernel<NRT, WN, kBiasRelu, false, false, P>;
+    default: return conv1x1_split_kernel<NRT, WN, kBiasResRelu, false, false, P>;
   }
 }
 
-void (*pick_kernel(int ci, int epi, int opt))(C1Args) {
+template <int P>
+void (*pick_cfg(int ci, int epi, int opt))(C1Args) {
   switch (ci) {
-    case 0: return pick_epi<16, 1>(epi, opt);
-    case 1: return pick_epi<8, 2>(epi, opt);
-    case 2: return pick_epi<4, 4>(epi, opt);
-    case 3: return pick_epi<8, 1>(epi, opt);
-    default: return pick_epi<4, 1>(epi, opt);
+    case 0: return pick_epi<16, 1, P>(epi, opt);
+    case 1: return pick_epi<8, 2, P>(epi, opt);
+    case 2: return pick_epi<4, 4, P>(epi, opt);
+    case 3: return pick_epi<8, 1, P>(epi, opt);
+    default: return pick_epi<4, 1, P>(epi, opt);
   }
+}
+
+void (*pick_kernel(int ci, int epi, int opt, int pieces))(C1Args) {
+  return pieces == 3 ? pick_cfg<3>(ci, epi, opt) : (pieces == 2 ? pick_cfg<2>(ci, epi, opt) : pick_cfg<1>(ci, epi, opt));
 }
 
 // The configuration of a shape: fewest rounds of workgroups over the CUs (one 8-wave workgroup per CU) times the wave's
@@ -323,7 +349,9 @@ struct C1Gn {
 };
 
 static int conv1x1_launch(const char* who, const void* x, const void* w_split, const void* bias, const void* residual, void* out,
-                          const C1Gn& gn, int B, int K, int N, int Hi, int Wi, int stride, int relu, int config, void* stream) {
+                          const C1Gn& gn, int B, int K, int N, int Hi, int Wi, int stride, int relu, int config, int pieces,
+                          void* stream) {
+  WM2F_REQUIRE(pieces >= 1 && pieces <= 3, "%s: pieces = %d (1, 2 and 3 are built)", who, pieces);
   WM2F_REQUIRE(x && w_split && out, "%s: null pointer", who);
   WM2F_REQUIRE(B > 0 && K > 0 && N > 0 && Hi > 0 && Wi > 0, "%s: non-positive size", who);
   WM2F_REQUIRE(K % kKStep == 0 && N % 64 == 0, "%s: K = %d must be a multiple of %d and N = %d of 64", who, K, kKStep, N);
@@ -381,8 +409,8 @@ static int conv1x1_launch(const char* who, const void* x, const void* w_split, c
   a.neps = gn.neps;
   a.nG = opt == kNorm ? gn.nG : 1;
   a.nrelu = gn.nrelu;
-  const size_t lds = (size_t)2 * (nt / 16) * 3 * kFrag + (opt == kNorm ? (size_t)2 * K * sizeof(float) : 0);
-  void (*kfn)(C1Args) = pick_kernel(ci, epi, opt);
+  const size_t lds = (size_t)2 * (nt / 16) * pieces * kFrag + (opt == kNorm ? (size_t)2 * K * sizeof(float) : 0);
+  void (*kfn)(C1Args) = pick_kernel(ci, epi, opt, pieces);
   // per call: the attribute belongs to the current device
   hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) {
@@ -402,7 +430,15 @@ extern "C" int wm2f_conv1x1_split_fwd(const void* x, const void* w_split, const 
                                       int B, int K, int N, int Hi, int Wi, int stride, int relu, int config, void* stream) {
   const C1Gn none = {nullptr, 0, nullptr, nullptr, nullptr, 0, 0.f, 0};
   return conv1x1_launch("wm2f_conv1x1_split_fwd", x, w_split, bias, residual, out, none, B, K, N, Hi, Wi, stride, relu, config,
-                        stream);
+                        3, stream);
+}
+
+extern "C" int wm2f_conv1x1_split_fwd_p(const void* x, const void* w_split, const void* bias, const void* residual, void* out,
+                                        int B, int K, int N, int Hi, int Wi, int stride, int relu, int config, int pieces,
+                                        void* stream) {
+  const C1Gn none = {nullptr, 0, nullptr, nullptr, nullptr, 0, 0.f, 0};
+  return conv1x1_launch("wm2f_conv1x1_split_fwd_p", x, w_split, bias, residual, out, none, B, K, N, Hi, Wi, stride, relu, config,
+                        pieces, stream);
 }
 
 extern "C" int wm2f_conv1x1_split_gn_fwd(const void* x, const void* w_split, const void* bias, void* out, void* stats_out,
@@ -412,5 +448,15 @@ extern "C" int wm2f_conv1x1_split_gn_fwd(const void* x, const void* w_split, con
   const char* who = "wm2f_conv1x1_split_gn_fwd";
   WM2F_REQUIRE(stats_out || norm_stats, "%s: neither a statistics output nor a normalised operand", who);
   const C1Gn gn = {stats_out, G_out, norm_stats, norm_gamma, norm_beta, norm_G, norm_eps, norm_relu ? 1 : 0};
-  return conv1x1_launch(who, x, w_split, bias, nullptr, out, gn, B, K, N, Hi, Wi, stride, 0, config, stream);
+  return conv1x1_launch(who, x, w_split, bias, nullptr, out, gn, B, K, N, Hi, Wi, stride, 0, config, 3, stream);
+}
+
+extern "C" int wm2f_conv1x1_split_gn_fwd_p(const void* x, const void* w_split, const void* bias, void* out, void* stats_out,
+                                           int G_out, const void* norm_stats, const void* norm_gamma, const void* norm_beta,
+                                           int norm_G, float norm_eps, int norm_relu, int B, int K, int N, int Hi, int Wi,
+                                           int stride, int config, int pieces, void* stream) {
+  const char* who = "wm2f_conv1x1_split_gn_fwd_p";
+  WM2F_REQUIRE(stats_out || norm_stats, "%s: neither a statistics output nor a normalised operand", who);
+  const C1Gn gn = {stats_out, G_out, norm_stats, norm_gamma, norm_beta, norm_G, norm_eps, norm_relu ? 1 : 0};
+  return conv1x1_launch(who, x, w_split, bias, nullptr, out, gn, B, K, N, Hi, Wi, stride, 0, config, pieces, stream);
 }

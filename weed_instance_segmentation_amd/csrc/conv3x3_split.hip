@@ -62,16 +62,25 @@ __device__ __forceinline__ f32x8 widen(const bf16x8 v) {
   return r;
 }
 
-// the split of conv1x1_split.hip, the same bits
+// the split of conv1x1_split.hip, the same bits: its first P pieces (the pieces past P are left untouched and never read)
+template <int P>
 __device__ __forceinline__ void split3(const f32x8 x, bf16x8& h, bf16x8& m, bf16x8& l) {
   f32x8 xc;
 #pragma unroll
   for (int i = 0; i < 8; ++i) xc[i] = __builtin_amdgcn_fmed3f(x[i], -kBf16Max, kBf16Max);
+  if constexpr (P == 1) {  // no residual piece carries an inf or a NaN on: x * 0 (0, or NaN) keeps h non-finite with x
+#pragma unroll
+    for (int i = 0; i < 8; ++i) xc[i] = __builtin_fmaf(x[i], 0.f, xc[i]);
+  }
   h = __builtin_convertvector(xc, bf16x8);
-  const f32x8 r1 = x - widen(h);
-  m = __builtin_convertvector(r1, bf16x8);
-  const f32x8 r2 = r1 - widen(m);
-  l = __builtin_convertvector(r2, bf16x8);
+  if constexpr (P >= 2) {
+    const f32x8 r1 = x - widen(h);
+    m = __builtin_convertvector(r1, bf16x8);
+    if constexpr (P >= 3) {
+      const f32x8 r2 = r1 - widen(m);
+      l = __builtin_convertvector(r2, bf16x8);
+    }
+  }
 }
 
 struct C3Args {
@@ -93,12 +102,15 @@ __device__ __forceinline__ void c3_barrier() {
 
 // NRT row tiles per wave, WN waves along n: a workgroup tile is NT = WN * NRT * 16 channels by PT = (8 / WN) * 32 pixels.
 // STATS: the epilogue also reduces the group statistics of what it stores (gn_tile_stats; cpg in {4, 8, 16}).
-template <int NRT, int WN, int EPI, bool STATS = false>
+// P = the pieces of each operand that take part: 3 = all six products, 2 = h and m (m.h, h.m, h.h), 1 = h
+// alone (h.h).  The split weight is the three-piece one at every P; the ring holds the first P pieces of each row tile.
+template <int NRT, int WN, int EPI, bool STATS = false, int P = 3>
 __global__ __launch_bounds__(kThreads) void conv3x3_split_kernel(C3Args a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [2][NT / 16][3][64][16 B]
+  static_assert(P >= 1 && P <= 3, "one, two or three pieces");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [2][NT / 16][P][64][16 B]
   constexpr int kRowTiles = WN * NRT;
-  constexpr int kPanelBytes = kRowTiles * 3 * kFrag;
-  constexpr int kPieces = kRowTiles * 3;
+  constexpr int kPanelBytes = kRowTiles * P * kFrag;
+  constexpr int kPieces = kRowTiles * P;
   constexpr int kPT = (kWaves / WN) * kCT * 16;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wn = wave % WN, wp = wave / WN;
@@ -144,8 +156,10 @@ __global__ __launch_bounds__(kThreads) void conv3x3_split_kernel(C3Args a) {
     const int dy = tap / 3, dx = tap - 3 * dy;
     unsigned char* dst = smem + (it & 1) * kPanelBytes;
     const int src = ((tap * n_cb + cb) * (a.N / 16) + n_wg / 16) * 3 * kFrag;
-    for (int f = wave; f < kPieces; f += kWaves)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rs, (lds_ptr_t)(dst + f * kFrag), 16, lane * 16, src + f * kFrag, 0, 0);
+    for (int f = wave; f < kPieces; f += kWaves) {
+      const int fs = P == 3 ? f : (f / P) * 3 + f % P;  // ring piece f = piece f % P of row tile f / P
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rs, (lds_ptr_t)(dst + f * kFrag), 16, lane * 16, src + fs * kFrag, 0, 0);
+    }
     const int kb = (cb * kKStep * HWi + dy * a.Wi + dx) * 4;
 #pragma unroll
     for (int c = 0; c < kCT; ++c) {
@@ -168,22 +182,27 @@ __global__ __launch_bounds__(kThreads) void conv3x3_split_kernel(C3Args a) {
   for (int it = 0; it < n_ks; ++it) {
     bf16x8 bh[kCT], bm[kCT], bl[kCT];
 #pragma unroll
-    for (int c = 0; c < kCT; ++c) split3(xr[c], bh[c], bm[c], bl[c]);
+    for (int c = 0; c < kCT; ++c) split3<P>(xr[c], bh[c], bm[c], bl[c]);
     if (it + 1 < n_ks) issue(it + 1);  // the next step's loads fly under this step's MFMAs
 
-    const unsigned char* panel = smem + (it & 1) * kPanelBytes + wn * NRT * 3 * kFrag;
+    const unsigned char* panel = smem + (it & 1) * kPanelBytes + wn * NRT * P * kFrag;
     auto read_a = [&](bf16x8 (&dst)[3], int rt) {
 #pragma unroll
-      for (int p = 0; p < 3; ++p) dst[p] = *reinterpret_cast<const bf16x8*>(panel + (rt * 3 + p) * kFrag + lane * 16);
+      for (int p = 0; p < P; ++p) dst[p] = *reinterpret_cast<const bf16x8*>(panel + (rt * P + p) * kFrag + lane * 16);
     };
     // the six products of one (row tile, column tile), the small terms first, summed from zero and added to the
     // accumulator once per k-step (conv1x1_split.hip)
     auto six = [&](f32x4 acc_in, const bf16x8 (&av)[3], int cc) {
-      f32x4 c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1], bm[cc], (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[2], bh[cc], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bl[cc], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1], bh[cc], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bm[cc], c, 0, 0, 0);
+      f32x4 c = {0.f, 0.f, 0.f, 0.f};
+      if constexpr (P == 3) {
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1], bm[cc], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[2], bh[cc], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bl[cc], c, 0, 0, 0);
+      }
+      if constexpr (P >= 2) {  // P = 2: m.h, h.m, h.h, the order they have in the six-product chain
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1], bh[cc], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bm[cc], c, 0, 0, 0);
+      }
       return acc_in + __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bh[cc], c, 0, 0, 0);
     };
     bf16x8 av[2][3];
@@ -233,31 +252,36 @@ __global__ __launch_bounds__(kThreads) void conv3x3_split_kernel(C3Args a) {
   if (STATS) gn_tile_stats<NRT, WN, kWaves>(gs, gss, smem, a.stats, b * a.G, n_wg, a.cpg, tid);
 }
 
-// The configurations, (NRT, WN): workgroup tile NT x PT = (WN NRT 16) x (8 / WN x 32).  The LDS ring is 2 x NT x 192 B.
+// The configurations, (NRT, WN): workgroup tile NT x PT = (WN NRT 16) x (8 / WN x 32).  The LDS ring is 2 x NT x 64 P B.
 struct Cfg {
   int nrt, wn;
 };
 constexpr Cfg kCfg[] = {{16, 1}, {8, 2}, {4, 4}, {8, 1}, {4, 1}};
 constexpr int kNumCfg = sizeof(kCfg) / sizeof(kCfg[0]);
 
-template <int NRT, int WN>
+template <int NRT, int WN, int P>
 void (*pick_epi(int epi, bool stats))(C3Args) {
-  if (stats) return conv3x3_split_kernel<NRT, WN, kRaw, true>;  // the statistics are built on the raw epilogue
+  if (stats) return conv3x3_split_kernel<NRT, WN, kRaw, true, P>;  // the statistics are built on the raw epilogue
   switch (epi) {
-    case kRaw: return conv3x3_split_kernel<NRT, WN, kRaw>;
-    case kBias: return conv3x3_split_kernel<NRT, WN, kBias>;
-    default: return conv3x3_split_kernel<NRT, WN, kBiasRelu>;
+    case kRaw: return conv3x3_split_kernel<NRT, WN, kRaw, false, P>;
+    case kBias: return conv3x3_split_kernel<NRT, WN, kBias, false, P>;
+    default: return conv3x3_split_kernel<NRT, WN, kBiasRelu, false, P>;
   }
 }
 
-void (*pick_kernel(int ci, int epi, bool stats))(C3Args) {
+template <int P>
+void (*pick_cfg(int ci, int epi, bool stats))(C3Args) {
   switch (ci) {
-    case 0: return pick_epi<16, 1>(epi, stats);
-    case 1: return pick_epi<8, 2>(epi, stats);
-    case 2: return pick_epi<4, 4>(epi, stats);
-    case 3: return pick_epi<8, 1>(epi, stats);
-    default: return pick_epi<4, 1>(epi, stats);
+    case 0: return pick_epi<16, 1, P>(epi, stats);
+    case 1: return pick_epi<8, 2, P>(epi, stats);
+    case 2: return pick_epi<4, 4, P>(epi, stats);
+    case 3: return pick_epi<8, 1, P>(epi, stats);
+    default: return pick_epi<4, 1, P>(epi, stats);
   }
+}
+
+void (*pick_kernel(int ci, int epi, bool stats, int pieces))(C3Args) {
+  return pieces == 3 ? pick_cfg<3>(ci, epi, stats) : (pieces == 2 ? pick_cfg<2>(ci, epi, stats) : pick_cfg<1>(ci, epi, stats));
 }
 
 // The configuration of a shape: fewest rounds of workgroups over the CUs (one 8-wave workgroup per CU) times the wave's
@@ -304,7 +328,9 @@ extern "C" int wm2f_conv3x3_split_config(int N, int P, int B, int n_cu) {
 
 // stats_out != NULL: the group statistics of the (raw) output in G_out groups (wm2f_conv3x3_split_stats_fwd)
 static int conv3x3_launch(const char* who, const void* x, const void* w_split, const void* bias, void* out, void* stats_out,
-                          int G_out, int B, int Cin, int N, int Hi, int Wi, int stride, int relu, int config, void* stream) {
+                          int G_out, int B, int Cin, int N, int Hi, int Wi, int stride, int relu, int config, int pieces,
+                          void* stream) {
+  WM2F_REQUIRE(pieces >= 1 && pieces <= 3, "%s: pieces = %d (1, 2 and 3 are built)", who, pieces);
   WM2F_REQUIRE(x && w_split && out, "%s: null pointer", who);
   WM2F_REQUIRE(B > 0 && Cin > 0 && N > 0 && Hi > 0 && Wi > 0, "%s: non-positive size", who);
   WM2F_REQUIRE(Cin % kKStep == 0 && N % 64 == 0, "%s: Cin = %d must be a multiple of %d and N = %d of 64", who, Cin, kKStep, N);
@@ -345,8 +371,8 @@ static int conv3x3_launch(const char* who, const void* x, const void* w_split, c
   a.stats = (double*)stats_out;
   a.G = stats_out ? G_out : 1;
   a.cpg = stats_out ? N / G_out : 4;
-  const size_t lds = (size_t)2 * (nt / 16) * 3 * kFrag;
-  void (*kfn)(C3Args) = pick_kernel(ci, epi, stats_out != nullptr);
+  const size_t lds = (size_t)2 * (nt / 16) * pieces * kFrag;
+  void (*kfn)(C3Args) = pick_kernel(ci, epi, stats_out != nullptr, pieces);
   // per call: the attribute belongs to the current device
   hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) {
@@ -365,12 +391,25 @@ static int conv3x3_launch(const char* who, const void* x, const void* w_split, c
 extern "C" int wm2f_conv3x3_split_fwd(const void* x, const void* w_split, const void* bias, void* out, int B, int Cin, int N,
                                       int Hi, int Wi, int stride, int relu, int config, void* stream) {
   return conv3x3_launch("wm2f_conv3x3_split_fwd", x, w_split, bias, out, nullptr, 0, B, Cin, N, Hi, Wi, stride, relu, config,
-                        stream);
+                        3, stream);
+}
+
+extern "C" int wm2f_conv3x3_split_fwd_p(const void* x, const void* w_split, const void* bias, void* out, int B, int Cin, int N,
+                                        int Hi, int Wi, int stride, int relu, int config, int pieces, void* stream) {
+  return conv3x3_launch("wm2f_conv3x3_split_fwd_p", x, w_split, bias, out, nullptr, 0, B, Cin, N, Hi, Wi, stride, relu, config,
+                        pieces, stream);
 }
 
 extern "C" int wm2f_conv3x3_split_stats_fwd(const void* x, const void* w_split, void* out, void* stats_out, int G_out, int B,
                                             int Cin, int N, int Hi, int Wi, int stride, int config, void* stream) {
   const char* who = "wm2f_conv3x3_split_stats_fwd";
   WM2F_REQUIRE(stats_out, "%s: null pointer", who);
-  return conv3x3_launch(who, x, w_split, nullptr, out, stats_out, G_out, B, Cin, N, Hi, Wi, stride, 0, config, stream);
+  return conv3x3_launch(who, x, w_split, nullptr, out, stats_out, G_out, B, Cin, N, Hi, Wi, stride, 0, config, 3, stream);
+}
+
+extern "C" int wm2f_conv3x3_split_stats_fwd_p(const void* x, const void* w_split, void* out, void* stats_out, int G_out, int B,
+                                              int Cin, int N, int Hi, int Wi, int stride, int config, int pieces, void* stream) {
+  const char* who = "wm2f_conv3x3_split_stats_fwd_p";
+  WM2F_REQUIRE(stats_out, "%s: null pointer", who);
+  return conv3x3_launch(who, x, w_split, nullptr, out, stats_out, G_out, B, Cin, N, Hi, Wi, stride, 0, config, pieces, stream);
 }

@@ -60,7 +60,6 @@ constexpr int kN = 64;             // output channels
 constexpr int kRT = kN / 16;       // row tiles
 constexpr int kKPad = 160;         // K of the split weight
 constexpr int kFrag = 1024;        // bytes of one A fragment piece (64 lanes x 8 bf16)
-constexpr int kPanel = kRT * 3 * kFrag;  // bytes of one k-step of the split W
 constexpr int kStripP = 15;        // pooled columns of a strip
 constexpr int kStripW = 69;        // input columns of a strip: 2 * 31 + 7
 constexpr int kPlaneF = 70;        // floats between the planes of a ring slot
@@ -68,8 +67,9 @@ constexpr int kRowF = 256;         // floats of a ring slot (Cin * 70 <= 210 use
 constexpr int kRingBytes = 8 * kRowF * 4;
 constexpr unsigned kRingMask = kRingBytes - 1;
 constexpr int kWOff = kWaves * kRingBytes;
-constexpr int kBiasOff = kWOff + (kKPad / 32) * kPanel;
-constexpr int kLds = kBiasOff + kN * 4;
+// the bias behind the first P pieces of the split W; the bytes of dynamic LDS
+constexpr int stem_bias_off(int P) { return kWOff + (kKPad / 32) * kRT * P * kFrag; }
+constexpr int stem_lds(int P) { return stem_bias_off(P) + kN * 4; }
 constexpr unsigned kOob = 0x80000000u;
 constexpr float kBf16Max = 3.38953139e38f;  // largest finite bf16, 0x7F7F
 
@@ -95,16 +95,25 @@ __device__ __forceinline__ f32x8 widen(const bf16x8 v) {
   return r;
 }
 
-// the split of conv1x1_split.hip, the same bits
+// the split of conv1x1_split.hip, the same bits: its first P pieces (the pieces past P are left untouched and never read)
+template <int P>
 __device__ __forceinline__ void split3(const f32x8 x, bf16x8& h, bf16x8& m, bf16x8& l) {
   f32x8 xc;
 #pragma unroll
   for (int i = 0; i < 8; ++i) xc[i] = __builtin_amdgcn_fmed3f(x[i], -kBf16Max, kBf16Max);
+  if constexpr (P == 1) {  // no residual piece carries an inf or a NaN on: x * 0 (0, or NaN) keeps h non-finite with x
+#pragma unroll
+    for (int i = 0; i < 8; ++i) xc[i] = __builtin_fmaf(x[i], 0.f, xc[i]);
+  }
   h = __builtin_convertvector(xc, bf16x8);
-  const f32x8 r1 = x - widen(h);
-  m = __builtin_convertvector(r1, bf16x8);
-  const f32x8 r2 = r1 - widen(m);
-  l = __builtin_convertvector(r2, bf16x8);
+  if constexpr (P >= 2) {
+    const f32x8 r1 = x - widen(h);
+    m = __builtin_convertvector(r1, bf16x8);
+    if constexpr (P >= 3) {
+      const f32x8 r2 = r1 - widen(m);
+      l = __builtin_convertvector(r2, bf16x8);
+    }
+  }
 }
 
 struct StemArgs {
@@ -118,9 +127,14 @@ struct StemArgs {
   int units;   // B * nchunk * S
 };
 
-template <int CIN>
+// P = the pieces of each operand that take part: 3 = all six products, 2 = h and m (m.h, h.m, h.h), 1 = h
+// alone (h.h).  The split weight is the three-piece one at every P; LDS holds the first P pieces of each row tile.
+template <int CIN, int P = 3>
 __global__ __launch_bounds__(kThreads) void stem7x7_pool_kernel(StemArgs a) {
+  static_assert(P >= 1 && P <= 3, "one, two or three pieces");
   extern __shared__ __attribute__((aligned(8192))) unsigned char smem[];  // [8 rings][8 slots][256 f32] | W | bias
+  constexpr int kPanelP = kRT * P * kFrag;  // bytes of one k-step of W in LDS
+  constexpr int kBiasOff = stem_bias_off(P);
   constexpr int NG = 7 * CIN < 20 ? 7 * CIN : 20;  // kernel rows held as groups of 8 columns
   constexpr int NKS = (NG + 3) / 4;                // k-steps that hold any
   constexpr int N7 = 7 * CIN > 20 ? 7 : 0;         // groups whose eighth column is a tap of kernel row 20
@@ -132,7 +146,10 @@ __global__ __launch_bounds__(kThreads) void stem7x7_pool_kernel(StemArgs a) {
   {
     const u32x4* src = reinterpret_cast<const u32x4*>(a.ws);
     u32x4* dst = reinterpret_cast<u32x4*>(smem + kWOff);
-    for (int i = tid; i < NKS * kPanel / 16; i += kThreads) dst[i] = src[i];
+    for (int i = tid; i < NKS * kPanelP / 16; i += kThreads) {
+      const int f = i >> 6;  // LDS piece f = piece f % P of (k-step, row tile) f / P
+      dst[i] = src[P == 3 ? i : (((f / P) * 3 + f % P) << 6) + (i & 63)];
+    }
     if (tid < kN) reinterpret_cast<float*>(smem + kBiasOff)[tid] = a.bias[tid];
   }
   __syncthreads();
@@ -261,22 +278,27 @@ __global__ __launch_bounds__(kThreads) void stem7x7_pool_kernel(StemArgs a) {
       for (int ks = 0; ks < NKS; ++ks) {
         bf16x8 bh[2], bm[2], bl[2];
 #pragma unroll
-        for (int t = 0; t < 2; ++t) split3(xr[t], bh[t], bm[t], bl[t]);
+        for (int t = 0; t < 2; ++t) split3<P>(xr[t], bh[t], bm[t], bl[t]);
         if (ks + 1 < NKS) gather(ks + 1, xr);
 
-        const unsigned char* panel = smem + kWOff + ks * kPanel;
+        const unsigned char* panel = smem + kWOff + ks * kPanelP;
         auto read_a = [&](bf16x8 (&dst)[3], int rt) {
 #pragma unroll
-          for (int p = 0; p < 3; ++p) dst[p] = *reinterpret_cast<const bf16x8*>(panel + (rt * 3 + p) * kFrag + lane * 16);
+          for (int p = 0; p < P; ++p) dst[p] = *reinterpret_cast<const bf16x8*>(panel + (rt * P + p) * kFrag + lane * 16);
         };
         // the six products of one (row tile, column tile), the small terms first, summed from zero and added to the
         // accumulator once per k-step (conv1x1_split.hip)
         auto six = [&](f32x4 acc_in, const bf16x8 (&av)[3], int cc) {
-          f32x4 c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1], bm[cc], (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[2], bh[cc], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bl[cc], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1], bh[cc], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bm[cc], c, 0, 0, 0);
+          f32x4 c = {0.f, 0.f, 0.f, 0.f};
+          if constexpr (P == 3) {
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1], bm[cc], c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[2], bh[cc], c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bl[cc], c, 0, 0, 0);
+          }
+          if constexpr (P >= 2) {  // P = 2: m.h, h.m, h.h, the order they have in the six-product chain
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1], bh[cc], c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bm[cc], c, 0, 0, 0);
+          }
           return acc_in + __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bh[cc], c, 0, 0, 0);
         };
         bf16x8 av[3];
@@ -387,9 +409,15 @@ int cu_count(int* n_cu) {
 
 using namespace wm2f;
 
-extern "C" int wm2f_stem7x7_pool_fwd(const void* x, const void* w_split, const void* bias, void* out, int B, int Cin, int N,
-                                     int Hi, int Wi, int grid, void* stream) {
-  const char* who = "wm2f_stem7x7_pool_fwd";
+// pieces = P of the kernel (3: wm2f_stem7x7_pool_fwd)
+template <int P>
+static void (*stem_pick(int Cin))(StemArgs) {
+  return Cin == 1 ? stem7x7_pool_kernel<1, P> : Cin == 2 ? stem7x7_pool_kernel<2, P> : stem7x7_pool_kernel<3, P>;
+}
+
+static int stem_launch(const char* who, const void* x, const void* w_split, const void* bias, void* out, int B, int Cin, int N,
+                       int Hi, int Wi, int grid, int pieces, void* stream) {
+  WM2F_REQUIRE(pieces >= 1 && pieces <= 3, "%s: pieces = %d (1, 2 and 3 are built)", who, pieces);
   WM2F_REQUIRE(x && w_split && bias && out, "%s: null pointer", who);
   WM2F_REQUIRE(B > 0 && Hi > 0 && Wi > 0, "%s: non-positive size", who);
   WM2F_REQUIRE(Cin >= 1 && 49 * Cin <= kKPad, "%s: Cin = %d (1, 2 and 3 are built: 49 Cin <= %d)", who, Cin, kKPad);
@@ -424,7 +452,8 @@ extern "C" int wm2f_stem7x7_pool_fwd(const void* x, const void* w_split, const v
   a.nchunk = ceil_div(Hp, rc);
   a.units = B * a.nchunk * S;
   const int wgs = grid > 0 ? grid : min(n_cu, ceil_div(a.units, kWaves));
-  void (*kfn)(StemArgs) = Cin == 1 ? stem7x7_pool_kernel<1> : Cin == 2 ? stem7x7_pool_kernel<2> : stem7x7_pool_kernel<3>;
+  void (*kfn)(StemArgs) = pieces == 3 ? stem_pick<3>(Cin) : (pieces == 2 ? stem_pick<2>(Cin) : stem_pick<1>(Cin));
+  const int kLds = stem_lds(pieces);
   // per call: the attribute belongs to the current device
   hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
   if (e != hipSuccess) {
@@ -434,4 +463,14 @@ extern "C" int wm2f_stem7x7_pool_fwd(const void* x, const void* w_split, const v
   hipLaunchKernelGGL(kfn, dim3(wgs), dim3(kThreads), kLds, (hipStream_t)stream, a);
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;
+}
+
+extern "C" int wm2f_stem7x7_pool_fwd(const void* x, const void* w_split, const void* bias, void* out, int B, int Cin, int N,
+                                     int Hi, int Wi, int grid, void* stream) {
+  return stem_launch("wm2f_stem7x7_pool_fwd", x, w_split, bias, out, B, Cin, N, Hi, Wi, grid, 3, stream);
+}
+
+extern "C" int wm2f_stem7x7_pool_fwd_p(const void* x, const void* w_split, const void* bias, void* out, int B, int Cin, int N,
+                                       int Hi, int Wi, int grid, int pieces, void* stream) {
+  return stem_launch("wm2f_stem7x7_pool_fwd_p", x, w_split, bias, out, B, Cin, N, Hi, Wi, grid, pieces, stream);
 }

@@ -58,16 +58,26 @@ constexpr int kFrag = 1024;   // bytes of one A fragment piece (64 lanes x 8 bf1
 constexpr unsigned kOob = 0x80000000u;
 constexpr float kBf16Max = 3.38953139e38f;  // largest finite bf16, 0x7F7F
 
+// The first P pieces of the three-piece split (P = 3: all of it; the pieces past P are left untouched and never read)
+template <int P = 3>
 __device__ __forceinline__ void split3(const f32x8 x, bf16x8& h, bf16x8& m, bf16x8& l) {
   f32x8 xc;
 #pragma unroll
   for (int i = 0; i < 8; ++i) xc[i] = __builtin_amdgcn_fmed3f(x[i], -kBf16Max, kBf16Max);
+  if constexpr (P == 1) {  // no residual piece carries an inf or a NaN on: x * 0 (0, or NaN) keeps h non-finite with x
+#pragma unroll
+    for (int i = 0; i < 8; ++i) xc[i] = __builtin_fmaf(x[i], 0.f, xc[i]);
+  }
   // vector conversions: v_cvt_pk_bf16_f32 (RNE, a NaN stays a NaN); bf16 -> f32 is exact
   h = __builtin_convertvector(xc, bf16x8);
-  const f32x8 r1 = x - __builtin_convertvector(h, f32x8);
-  m = __builtin_convertvector(r1, bf16x8);
-  const f32x8 r2 = r1 - __builtin_convertvector(m, f32x8);
-  l = __builtin_convertvector(r2, bf16x8);
+  if constexpr (P >= 2) {
+    const f32x8 r1 = x - __builtin_convertvector(h, f32x8);
+    m = __builtin_convertvector(r1, bf16x8);
+    if constexpr (P >= 3) {
+      const f32x8 r2 = r1 - __builtin_convertvector(m, f32x8);
+      l = __builtin_convertvector(r2, bf16x8);
+    }
+  }
 }
 
 __global__ __launch_bounds__(256) void split_weight_kernel(const float* __restrict__ w, bf16x8* __restrict__ ws, int N, int K) {
@@ -123,11 +133,14 @@ constexpr int kAblStores = 1, kAblLoads = 2, kAblMfma = 4;
 // NRT = row tiles of one feature slice (16: N = 256 and the 256-wide slices of N = 1024; 18: N = 288).
 // EPI = the epilogue, fixed at compile time (one LayerNorm epilogue inside the k-step loop beside the others spilled):
 // 0 = bias (+ ReLU) row-major, 1 = bias (+ ReLU) feature-group major, 2 = bias + residual + LayerNorm (+ pos)
-template <int NRT, int EPI, bool PIPE = true, int ABL = 0>
+// P = the pieces of each operand that take part: 3 = all six products, 2 = h and m (m.h, h.m, h.h), 1 = h
+// alone (h.h).  The split weight is the three-piece one at every P; the ring holds the first P pieces of each row tile.
+template <int NRT, int EPI, bool PIPE = true, int ABL = 0, int P = 3>
 __global__ __launch_bounds__(kSgThreads) void token_gemm_split_kernel(SgArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [2][NRT][3][64][16 B], then bias | gamma | beta
-  constexpr int kPanelBytes = NRT * 3 * kFrag;
-  constexpr int kPieces = NRT * 3;
+  static_assert(P >= 1 && P <= 3, "one, two or three pieces");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [2][NRT][P][64][16 B], then bias | gamma | beta
+  constexpr int kPanelBytes = NRT * P * kFrag;
+  constexpr int kPieces = NRT * P;
   constexpr int CT = kSgCT;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n_cu = gridDim.x, cu = blockIdx.x;
@@ -163,8 +176,10 @@ __global__ __launch_bounds__(kSgThreads) void token_gemm_split_kernel(SgArgs a) 
     const int it = q / spt, r = q - it * spt, sl = r / n_ks, ks = r - sl * n_ks;
     unsigned char* dst = smem + (q & 1) * kPanelBytes;
     const int src = (ks * nrt_all + sl * NRT) * 3 * kFrag;
-    for (int f = wave; f < kPieces; f += kSgWaves)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rs, (lds_ptr_t)(dst + f * kFrag), 16, lane * 16, src + f * kFrag, 0, 0);
+    for (int f = wave; f < kPieces; f += kSgWaves) {
+      const int fs = P == 3 ? f : (f / P) * 3 + f % P;  // ring piece f = piece f % P of row tile f / P
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rs, (lds_ptr_t)(dst + f * kFrag), 16, lane * 16, src + fs * kFrag, 0, 0);
+    }
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
       const int tile = w0 + CT * it + c;
@@ -192,7 +207,7 @@ __global__ __launch_bounds__(kSgThreads) void token_gemm_split_kernel(SgArgs a) 
     bf16x8 bh[CT], bm[CT], bl[CT];
 #pragma unroll
     for (int c = 0; c < CT; ++c)
-      if (c < n_live) split3(xr[c], bh[c], bm[c], bl[c]);  // wave-uniform; a dead tile's pieces are never read
+      if (c < n_live) split3<P>(xr[c], bh[c], bm[c], bl[c]);  // wave-uniform; a dead tile's pieces are never read
     // the next step's loads fly under this step's MFMAs -- except before a LayerNorm epilogue, where their 16 registers
     // made the epilogue spill: there they are issued after it
     const bool late = EPI == 2 && ks + 1 == n_ks;
@@ -201,7 +216,7 @@ __global__ __launch_bounds__(kSgThreads) void token_gemm_split_kernel(SgArgs a) 
     const unsigned char* panel = smem + (q & 1) * kPanelBytes;
     auto read_a = [&](bf16x8 (&dst)[3], int rt) {
 #pragma unroll
-      for (int p = 0; p < 3; ++p) dst[p] = *reinterpret_cast<const bf16x8*>(panel + (rt * 3 + p) * kFrag + lane * 16);
+      for (int p = 0; p < P; ++p) dst[p] = *reinterpret_cast<const bf16x8*>(panel + (rt * P + p) * kFrag + lane * 16);
     };
     // the six products of one (row tile, column tile); the small terms first
     auto six = [&](f32x4 c, const bf16x8 (&av)[3], int cc) -> f32x4 {
@@ -211,11 +226,15 @@ __global__ __launch_bounds__(kSgThreads) void token_gemm_split_kernel(SgArgs a) 
         c[2] += __builtin_bit_cast(f32x4, av[2])[2] * __builtin_bit_cast(f32x4, bh[cc])[2];
         return c;
       }
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1], bm[cc], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[2], bh[cc], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bl[cc], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1], bh[cc], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bm[cc], c, 0, 0, 0);
+      if constexpr (P == 3) {
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1], bm[cc], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[2], bh[cc], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bl[cc], c, 0, 0, 0);
+      }
+      if constexpr (P >= 2) {
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1], bh[cc], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bm[cc], c, 0, 0, 0);
+      }
       return __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bh[cc], c, 0, 0, 0);
     };
     // a turn with one live column tile skips the second tile's split and its six-MFMA chains by a wave-uniform branch
@@ -394,11 +413,11 @@ __global__ __launch_bounds__(kSgThreads) void token_gemm_split_kernel(SgArgs a) 
 
 using sg_kernel_t = void (*)(SgArgs);
 
-// the instance of (N == 288, epilogue); PIPE applies to the LayerNorm epilogue alone
-template <bool PIPE, int ABL>
+// the instance of (N == 288, epilogue) with P pieces; PIPE applies to the LayerNorm epilogue alone
+template <bool PIPE, int ABL, int P = 3>
 sg_kernel_t sg_pick(bool n288, int epi) {
-  if (n288) return epi == 2 ? token_gemm_split_kernel<18, 2, PIPE, ABL> : (epi == 1 ? token_gemm_split_kernel<18, 1, true, ABL> : token_gemm_split_kernel<18, 0, true, ABL>);
-  return epi == 2 ? token_gemm_split_kernel<16, 2, PIPE, ABL> : (epi == 1 ? token_gemm_split_kernel<16, 1, true, ABL> : token_gemm_split_kernel<16, 0, true, ABL>);
+  if (n288) return epi == 2 ? token_gemm_split_kernel<18, 2, PIPE, ABL, P> : (epi == 1 ? token_gemm_split_kernel<18, 1, true, ABL, P> : token_gemm_split_kernel<18, 0, true, ABL, P>);
+  return epi == 2 ? token_gemm_split_kernel<16, 2, PIPE, ABL, P> : (epi == 1 ? token_gemm_split_kernel<16, 1, true, ABL, P> : token_gemm_split_kernel<16, 0, true, ABL, P>);
 }
 
 int device_cu_count(int* n_cu) {
@@ -430,11 +449,12 @@ extern "C" int wm2f_token_linear_split_weight(const void* w, void* w_split, int 
   return WM2F_OK;
 }
 
-extern "C" int wm2f_token_linear_split_fwd(const void* x, const void* w_split, const void* bias, const void* residual,
-                                           const void* ln_gamma, const void* ln_beta, const void* pos, void* out,
-                                           void* out_plus_pos, int64_t M, int K, int N, int relu, int64_t pos_rows, float eps,
-                                           int out_group, void* stream) {
-  const char* who = "wm2f_token_linear_split_fwd";
+// pieces = P of the kernel (3: wm2f_token_linear_split_fwd)
+static int token_split_launch(const char* who, const void* x, const void* w_split, const void* bias, const void* residual,
+                              const void* ln_gamma, const void* ln_beta, const void* pos, void* out, void* out_plus_pos,
+                              int64_t M, int K, int N, int relu, int64_t pos_rows, float eps, int out_group, int pieces,
+                              void* stream) {
+  WM2F_REQUIRE(pieces >= 1 && pieces <= 3, "%s: pieces = %d (1, 2 and 3 are built)", who, pieces);
   WM2F_REQUIRE(x && w_split && bias && out, "%s: null pointer", who);
   WM2F_REQUIRE(M > 0 && K > 0 && N > 0, "%s: non-positive size", who);
   WM2F_REQUIRE(N == 256 || N == 288 || N == 512 || N == 768 || N == 1024,
@@ -475,9 +495,10 @@ extern "C" int wm2f_token_linear_split_fwd(const void* x, const void* w_split, c
   int grid = n_cu;
   if (grid > a.tiles_total) grid = a.tiles_total;
   const int nrt = N == 288 ? 18 : 16;
-  const size_t lds = (size_t)2 * nrt * 3 * kFrag + (size_t)3 * N * sizeof(float);
+  const size_t lds = (size_t)2 * nrt * pieces * kFrag + (size_t)3 * N * sizeof(float);
   const int epi = ln_gamma ? 2 : (out_group > 0 ? 1 : 0);
-  sg_kernel_t kfn = sg_pick<true, 0>(N == 288, epi);
+  sg_kernel_t kfn = pieces == 3 ? sg_pick<true, 0>(N == 288, epi)
+                                : (pieces == 2 ? sg_pick<true, 0, 2>(N == 288, epi) : sg_pick<true, 0, 1>(N == 288, epi));
 #ifdef WM2F_PROFILING
   {  // WM2F_TGS_OPT = 0: the LayerNorm epilogue with its loads one batch at a time, as before §13.2 (valid outputs, the
      // same bits); WM2F_TGS_ABL = 1 / 2 / 4: the shipped kernel without epilogue stores / epilogue loads / MFMAs
@@ -485,6 +506,7 @@ extern "C" int wm2f_token_linear_split_fwd(const void* x, const void* w_split, c
     const char* eo = getenv("WM2F_TGS_OPT");
     const char* ea = getenv("WM2F_TGS_ABL");
     const int abl = ea ? atoi(ea) : 0;
+    WM2F_REQUIRE(pieces == 3 || (!eo && abl == 0), "%s: WM2F_TGS_OPT / WM2F_TGS_ABL are built for three pieces", who);
     if (abl != 0) {
       WM2F_REQUIRE(abl == 1 || abl == 2 || abl == 4, "%s: WM2F_TGS_ABL = %d is not built (1, 2, 4 are)", who, abl);
       WM2F_REQUIRE(!eo, "%s: WM2F_TGS_ABL ablates the shipped kernel only (unset WM2F_TGS_OPT)", who);
@@ -504,4 +526,20 @@ extern "C" int wm2f_token_linear_split_fwd(const void* x, const void* w_split, c
   hipLaunchKernelGGL(kfn, dim3(grid), dim3(kSgThreads), lds, (hipStream_t)stream, a);
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;
+}
+
+extern "C" int wm2f_token_linear_split_fwd(const void* x, const void* w_split, const void* bias, const void* residual,
+                                           const void* ln_gamma, const void* ln_beta, const void* pos, void* out,
+                                           void* out_plus_pos, int64_t M, int K, int N, int relu, int64_t pos_rows, float eps,
+                                           int out_group, void* stream) {
+  return token_split_launch("wm2f_token_linear_split_fwd", x, w_split, bias, residual, ln_gamma, ln_beta, pos, out, out_plus_pos,
+                            M, K, N, relu, pos_rows, eps, out_group, 3, stream);
+}
+
+extern "C" int wm2f_token_linear_split_fwd_p(const void* x, const void* w_split, const void* bias, const void* residual,
+                                             const void* ln_gamma, const void* ln_beta, const void* pos, void* out,
+                                             void* out_plus_pos, int64_t M, int K, int N, int relu, int64_t pos_rows, float eps,
+                                             int out_group, int pieces, void* stream) {
+  return token_split_launch("wm2f_token_linear_split_fwd_p", x, w_split, bias, residual, ln_gamma, ln_beta, pos, out,
+                            out_plus_pos, M, K, N, relu, pos_rows, eps, out_group, pieces, stream);
 }

@@ -8,7 +8,9 @@ evaluation shape (config 1: 256 x 256, batch 2, `models/metrics.py:56`) the eage
     out = fwd(pixel_values)                                # same fields as model(pixel_values=...)
 
 The output tensors are the graph's static buffers: they are overwritten by the next call (clone what must survive).
-Shapes and dtype are fixed at capture; a different shape re-captures.
+Shapes and dtype are fixed at capture; a different shape re-captures.  So is the inference precision (`ops.SPLIT_PRECISION`,
+`set_inference_precision`): the graph replays the kernels of the level that was current at capture, whatever the level is
+at replay; build another GraphedForward to run another level.
 """
 from __future__ import annotations
 
@@ -16,6 +18,9 @@ import torch
 
 
 class GraphedForward:
+    """The label-free forward of `model` captured into one HIP graph at the shape, dtype and inference precision
+    (`ops.SPLIT_PRECISION`) that are current at capture; replays run that level whatever the flag says by then."""
+
     def __init__(self, model, example: torch.Tensor, warmup: int = 3):
         if not example.is_cuda:
             from ._lib import Wm2fError

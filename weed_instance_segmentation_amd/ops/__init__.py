@@ -7,6 +7,8 @@ package re-exports them all and owns the switches below: callers assign and read
 """
 from __future__ import annotations
 
+import os as _os
+
 # K1 backward flavour: None = follow torch.are_deterministic_algorithms_enabled(); True / False force it.
 K1_BWD_DETERMINISTIC: bool | None = None
 
@@ -24,6 +26,15 @@ CONV3X3_SPLIT = True
 # group statistics come out of the convolution epilogues (conv1x1_gn, conv3x3_stats) and mask_projection normalises
 # layer_1's raw output in its operand load.  False keeps the separate statistics and apply passes (the reference of the tests).
 CONV_GN_FUSED = True
+
+# The precision of the split-bf16 GEMMs and convolutions (token_linear, conv1x1, conv1x1_gn, conv3x3, conv3x3_stats,
+# stem_conv_pool on their split kernels), read at every call: "highest" (or None) = three bf16 pieces per operand
+# and six products, fp32 accuracy; "high" = two pieces, three products (error floor 2^-14 of sum |x w|); "medium" = one
+# piece, one product (both operands rounded to bf16, fp32 accumulation: floor 2^-6).  Any other value raises ValueError at
+# the first call that reads it.  The environment variable WM2F_SPLIT_PRECISION, when set, gives the initial value.
+# split=False, training and autocast never reach these kernels and are unaffected.  The package's
+# set_inference_precision / get_inference_precision / inference_precision assign and read this flag.
+SPLIT_PRECISION: str | None = _os.environ.get("WM2F_SPLIT_PRECISION") or "highest"
 
 # The flags come first: k1 reads K1_BWD_DETERMINISTIC off this package.
 from .._lib import check

@@ -5,9 +5,23 @@ import weakref
 
 import torch
 
+from .. import ops as _flags  # the package itself: SPLIT_PRECISION is assigned on it and read when a split kernel is called
 from .._lib import load
 from ._core import _launch, _p, _req
 from .fused import bias_act_, bias_relu_maxpool
+
+
+_LEVEL_PIECES = {None: 3, "highest": 3, "high": 2, "medium": 1}
+
+
+def _split_pieces():
+    """(pieces, tag suffix) of the package flag ops.SPLIT_PRECISION as it stands at this call: the `pieces` argument of the
+    wm2f_*_split_*_p entry points and what the launch tags carry below "highest" ("_p2", "_p1")."""
+    level = _flags.SPLIT_PRECISION
+    if not (level is None or isinstance(level, str)) or level not in _LEVEL_PIECES:
+        raise ValueError(f"ops.SPLIT_PRECISION = {level!r}: 'highest', 'high', 'medium' or None")
+    pieces = _LEVEL_PIECES[level]
+    return pieces, ("" if pieces == 3 else f"_p{pieces}")
 
 
 def token_linear_applies(x: torch.Tensor, weight: torch.Tensor) -> bool:
@@ -97,8 +111,10 @@ def token_linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, relu
             w_split = split_weight(weight)
         elif w_split.dtype != torch.uint8 or w_split.numel() != N * K * 6 or w_split.device != x.device:
             raise ValueError("token_linear: w_split is not split_weight(weight)")
-        _launch("wm2f_token_linear_split_fwd", x, _p(x), _p(w_split), _p(bias), _p(residual), _p(gamma), _p(beta), _p(pos),
-                _p(out), _p(out_pos), M, K, N, 1 if relu else 0, pos_rows, eps, int(out_group), tag=tag + "_split")
+        pieces, lvl = _split_pieces()
+        _launch("wm2f_token_linear_split_fwd_p", x, _p(x), _p(w_split), _p(bias), _p(residual), _p(gamma), _p(beta), _p(pos),
+                _p(out), _p(out_pos), M, K, N, 1 if relu else 0, pos_rows, eps, int(out_group), pieces,
+                tag=tag + "_split" + lvl)
     else:
         _launch("wm2f_token_linear_fwd", x, _p(x), _p(weight), _p(bias), _p(residual), _p(gamma), _p(beta), _p(pos), _p(out),
                 _p(out_pos), M, K, N, 1 if relu else 0, pos_rows, eps, int(out_group), tag=tag)
@@ -160,8 +176,9 @@ def conv1x1(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = N
     elif w_split.dtype != torch.uint8 or w_split.numel() != N * K * 6 or w_split.device != x.device:
         raise ValueError("conv1x1: w_split is not split_weight(weight)")
     out = torch.empty(B, N, Ho, Wo, device=x.device, dtype=torch.float32)
-    _launch("wm2f_conv1x1_split_fwd", x, _p(x), _p(w_split), _p(bias), _p(residual), _p(out), B, K, N, H, W, int(stride),
-            1 if relu else 0, int(config), tag=f"conv1x1_K{K}_N{N}_P{Ho * Wo}")
+    pieces, lvl = _split_pieces()
+    _launch("wm2f_conv1x1_split_fwd_p", x, _p(x), _p(w_split), _p(bias), _p(residual), _p(out), B, K, N, H, W, int(stride),
+            1 if relu else 0, int(config), pieces, tag=f"conv1x1_K{K}_N{N}_P{Ho * Wo}{lvl}")
     return out
 
 
@@ -209,9 +226,10 @@ def conv1x1_gn(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None 
     else:
         stats = torch.empty(B, int(stats_groups), 2, device=x.device, dtype=torch.float64)
     out = torch.empty(B, N, Ho, Wo, device=x.device, dtype=torch.float32)
-    _launch("wm2f_conv1x1_split_gn_fwd", x, _p(x), _p(w_split), _p(bias), _p(out), _p(stats), int(stats_groups), _p(nstats),
-            _p(ngamma), _p(nbeta), int(nG), float(neps), 1 if nrelu else 0, B, K, N, H, W, int(stride), int(config),
-            tag=f"conv1x1_K{K}_N{N}_P{Ho * Wo}")
+    pieces, lvl = _split_pieces()
+    _launch("wm2f_conv1x1_split_gn_fwd_p", x, _p(x), _p(w_split), _p(bias), _p(out), _p(stats), int(stats_groups), _p(nstats),
+            _p(ngamma), _p(nbeta), int(nG), float(neps), 1 if nrelu else 0, B, K, N, H, W, int(stride), int(config), pieces,
+            tag=f"conv1x1_K{K}_N{N}_P{Ho * Wo}{lvl}")
     return out if norm is not None else (out, stats)
 
 
@@ -232,8 +250,9 @@ def conv3x3_stats(x: torch.Tensor, weight: torch.Tensor, groups: int, stride: in
         raise ValueError("conv3x3_stats: w_split is not split_weight_3x3(weight)")
     out = torch.empty(B, N, Ho, Wo, device=x.device, dtype=torch.float32)
     stats = torch.empty(B, int(groups), 2, device=x.device, dtype=torch.float64)
-    _launch("wm2f_conv3x3_split_stats_fwd", x, _p(x), _p(w_split), _p(out), _p(stats), int(groups), B, Cin, N, H, W, int(stride),
-            int(config), tag=f"conv3x3_C{Cin}_N{N}_P{Ho * Wo}")
+    pieces, lvl = _split_pieces()
+    _launch("wm2f_conv3x3_split_stats_fwd_p", x, _p(x), _p(w_split), _p(out), _p(stats), int(groups), B, Cin, N, H, W,
+            int(stride), int(config), pieces, tag=f"conv3x3_C{Cin}_N{N}_P{Ho * Wo}{lvl}")
     return out, stats
 
 
@@ -282,8 +301,9 @@ def conv3x3(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = N
     elif w_split.dtype != torch.uint8 or w_split.numel() != N * 9 * Cin * 6 or w_split.device != x.device:
         raise ValueError("conv3x3: w_split is not split_weight_3x3(weight)")
     out = torch.empty(B, N, Ho, Wo, device=x.device, dtype=torch.float32)
-    _launch("wm2f_conv3x3_split_fwd", x, _p(x), _p(w_split), _p(bias), _p(out), B, Cin, N, H, W, int(stride), 1 if relu else 0,
-            int(config), tag=f"conv3x3_C{Cin}_N{N}_P{Ho * Wo}")
+    pieces, lvl = _split_pieces()
+    _launch("wm2f_conv3x3_split_fwd_p", x, _p(x), _p(w_split), _p(bias), _p(out), B, Cin, N, H, W, int(stride),
+            1 if relu else 0, int(config), pieces, tag=f"conv3x3_C{Cin}_N{N}_P{Ho * Wo}{lvl}")
     return out
 
 
@@ -356,7 +376,9 @@ def stem_conv_pool(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, w_
     elif w_split.dtype != torch.uint8 or w_split.numel() != N * STEM_K * 6 or w_split.device != x.device:
         raise ValueError("stem_conv_pool: w_split is not split_weight_stem(weight)")
     out = torch.empty(B, N, ((H - 1) // 2) // 2 + 1, ((W - 1) // 2) // 2 + 1, device=x.device, dtype=torch.float32)
-    _launch("wm2f_stem7x7_pool_fwd", x, _p(x), _p(w_split), _p(bias), _p(out), B, Cin, N, H, W, int(grid), tag="stem7x7_pool")
+    pieces, lvl = _split_pieces()
+    _launch("wm2f_stem7x7_pool_fwd_p", x, _p(x), _p(w_split), _p(bias), _p(out), B, Cin, N, H, W, int(grid), pieces,
+            tag="stem7x7_pool" + lvl)
     return out
 
 
