@@ -792,6 +792,62 @@ int64_t wm2f_labelmap_boundary_workspace(int B, int H, int W);
 int wm2f_labelmap_boundary(const void* map, int dtype, int32_t* out, void* workspace, int B, int H, int W, int d,
                            void* stream);
 
+/* ---- interior distance maps and aim points of id maps on device ---------------------------
+ * Where inside an instance to aim: the pixel farthest from everything that is not the instance, i.e. the maximum of the
+ * instance's interior Euclidean distance transform, and that maximum (the clearance) as its size measure.
+ * wm2f_labelmap_distance:  map (B, H, W) is WM2F_F32, WM2F_I32 or WM2F_U8.  Which value is which id follows
+ *                         wm2f_labelmap_instance_stats (a float that is negative, fractional, not finite or >= 2^24 is
+ *                         no id; +-0 is id 0); a negative int32 is no id either.
+ *                         d2 (B, H, W) int32, overwritten, every element: for a pixel with id k the squared Euclidean
+ *                         distance between pixel centres to the nearest position that does not carry id k; 0 for a
+ *                         pixel without an id.  border_outside != 0: the positions just beyond the image (x = -1, x = W,
+ *                         y = -1, y = H) count as not carrying k, the convention of the boundary bands.
+ *                         border_outside == 0: only real pixels count, and a pixel whose id fills its whole image gets
+ *                         INT32_MAX.  d2 <= 2 * 16384^2 fits int32.
+ *                         workspace: wm2f_labelmap_distance_workspace(B, H, W) bytes, 16-byte aligned: two bytes per
+ *                         pixel (g, below) rounded up to 16, then 16 bytes per column and chunk of rows.  It needs no
+ *                         clearing and holds nothing afterwards.
+ *                         H, W <= 16384, B <= 32, else WM2F_EUNSUPPORTED; sizes below 1 are WM2F_EINVAL (both are
+ *                         decided before a pointer is looked at).
+ *                         Three launches whatever B and the number of instances; the map is read four times in all.
+ *                         summary -- a lane per column marching down a chunk of rows (at least 32 of them): the id
+ *                         and length of the run of equal ids at the chunk's top and bottom.
+ *                         columns -- the same grid; a lane takes the run that ends just above its chunk from the
+ *                         summaries, marches down, takes the run below and marches back up:
+ *                         g(x, y) = vertical distance to the nearest position of column x that does not carry the
+ *                         pixel's id, uint16, 0 without an id, 0xffff where there is none (border-inside mode only).
+ *                         rows -- a workgroup stages whole rows in LDS (ids, g and h: 8 bytes per pixel, 128 KiB for
+ *                         a row of 16384; rows shorter than 1024 share a workgroup).  A wave per row finds every
+ *                         pixel's run of equal ids (ballot and bit scan with a carry) and from it h, the horizontal
+ *                         distance to the nearest position off the pixel's id.  A pixel starts from min(g, h)^2 and
+ *                         walks outwards while step^2 is below its best, offering step^2 + min(g(x - step),
+ *                         g(x + step))^2.  Exact: beyond a pixel of another id nothing is nearer than that pixel, and
+ *                         the walk ends before it leaves the run.  Rows are staged four pixels per lane when
+ *                         W % 4 == 0 and the map is 16-byte (uint8: 4-byte) aligned, pixel by pixel otherwise, with the
+ *                         same results.  All integer, bit-identical from run to run.
+ * wm2f_labelmap_aim_points: map and d2 as above (d2 is that kernel's output for this map), ids / n_ids as in
+ *                         wm2f_labelmap_instance_stats (NULL: row r is id r of [0, N); else (B, N) ascending raw ids,
+ *                         n_ids (B) of them valid), stats that kernel's (B, N, 8) int64 output for the same map and
+ *                         rows, or NULL.
+ *                         points (B, N, 4) int32, 16-byte aligned, overwritten: [x, y, d2max, 0] for an instance with
+ *                         pixels, [-1, -1, 0, 0] for an id without one.  (x, y) is a pixel of the instance with the
+ *                         largest d2; among equals the one nearest the rounded centroid cx = (2 sum_x + area) /
+ *                         (2 area), cy likewise (int64 division), by (x - cx)^2 + (y - cy)^2 as integers; among those
+ *                         the smallest y * W + x.  stats == NULL: the centroid term is 0 and the raster rule decides.
+ *                         workspace: wm2f_labelmap_aim_points_workspace(B, N) = 20 * B * N bytes, 8-byte aligned.
+ *                         H, W <= 16384, B <= 32, N <= 4096, else WM2F_EUNSUPPORTED; sizes below 1 are WM2F_EINVAL.
+ *                         Four launches, nothing read back: init, an atomicMax of d2 per instance, an unsigned 64-bit
+ *                         atomicMin of (centroid distance^2 << 32 | y * W + x) over the pixels that attain it (<= 2^29
+ *                         and < 2^28), and the rows.  Accumulators live in LDS while N <= 1024.  Integer atomics only:
+ *                         the result does not depend on their order. */
+int64_t wm2f_labelmap_distance_workspace(int B, int H, int W);
+int wm2f_labelmap_distance(const void* map, int dtype, int32_t* d2, void* workspace, int B, int H, int W,
+                           int border_outside, void* stream);
+int64_t wm2f_labelmap_aim_points_workspace(int B, int N);
+int wm2f_labelmap_aim_points(const void* map, int dtype, const int32_t* d2, const int32_t* ids, const int32_t* n_ids,
+                             const int64_t* stats, int32_t* points, void* workspace, int B, int H, int W, int N,
+                             void* stream);
+
 /* ---- panoptic quality and semantic mIoU on device ---------------------------------------
  * What scores the maps of post_process_panoptic_segmentation and post_process_semantic_segmentation: the segment
  * matching of panopticapi's pq_compute (which torchmetrics' PanopticQuality follows) and the confusion matrix mIoU is

@@ -1,4 +1,5 @@
-"""Per-instance area, bounding box and centroid of id maps on the GPU.
+"""Per-instance area, bounding box, centroid, distance maps and aim points of id maps on the GPU (DESIGN sections 21, 25,
+32, 36).
 
     from weed_instance_segmentation_amd import instance_statistics
     area, bbox, centroid = instance_statistics(prediction["segmentation"], n=len(prediction["segments_info"]))
@@ -19,6 +20,14 @@ number of instances and the width of the band.
 `clean_label_maps` repairs an id map -- specks dropped, one connected piece per instance, pinholes
 filled -- in a fixed chain of launches of csrc/clean.hip whatever the number of instances.  The post-processor, the
 tiled route and `test_with_metrics` take the same `CleanOptions` as `clean=`.
+
+    from weed_instance_segmentation_amd import aim_points, distance_maps
+    point, clearance = aim_points(prediction["segmentation"], n=len(prediction["segments_info"]))
+    d2 = distance_maps(prediction["segmentation"])             # squared distance to the nearest pixel off the instance
+
+`distance_maps` and `aim_points`: the exact interior Euclidean distance transform of every instance
+at once, and per instance the pixel where it is largest -- where to aim inside a plant whose centroid may lie on soil --
+in seven launches of csrc/distance.hip whatever the number of instances.
 """
 from __future__ import annotations
 
@@ -114,6 +123,110 @@ def boundary_maps(maps, dilation_ratio: float = 0.02, dilation: int | None = Non
     stack = seg.to(dev)
     out = ops.labelmap_boundary(stack.unsqueeze(0) if seg.dim() == 2 else stack, d)
     return out[0] if seg.dim() == 2 else out
+
+
+def _border_outside(border, who: str) -> bool:
+    if border not in ("outside", "inside"):
+        raise ValueError(f"{who}: border must be 'outside' or 'inside', got {border!r}")
+    return border == "outside"
+
+
+def _id_maps(maps, who: str) -> torch.Tensor:
+    """One (H, W) map or a (B, H, W) stack, host or device, as a tensor of an accepted dtype (not yet moved)."""
+    seg = torch.from_numpy(np.ascontiguousarray(maps)) if isinstance(maps, np.ndarray) else torch.as_tensor(maps)
+    if seg.dim() not in (2, 3):
+        raise ValueError(f"{who}: expected (H, W) or (B, H, W), got {tuple(seg.shape)}")
+    if seg.dtype not in (torch.float32, torch.int32, torch.uint8):
+        raise TypeError(f"{who}: maps fp32 / int32 / uint8, got {seg.dtype}")
+    return seg
+
+
+def distance_maps(maps, border: str = "outside", squared: bool = True) -> torch.Tensor:
+    """The interior Euclidean distance transform of every instance of one (H, W) id map or a (B, H, W) stack -- fp32
+    with -1 background, int32 or uint8, on the device or the host (a host map is moved to the current GPU).
+
+    Every pixel with an id gets its distance, between pixel centres, to the nearest position that does not carry that
+    id; a pixel without an id gets 0.  border="outside": the positions just beyond the image count as not carrying the
+    id, as for the boundary bands; border="inside": only real pixels count, and a pixel whose id fills its whole image
+    gets INT32_MAX.  Returns a device tensor of the input's shape: int32 squared distances (exact), or with
+    squared=False float32 distances, the root taken in float64.  Three launches of csrc/distance.hip whatever the
+    number of instances."""
+    seg = _id_maps(maps, "distance_maps")
+    outside = _border_outside(border, "distance_maps")
+    if not torch.cuda.is_available():
+        raise _lib.Wm2fError("distance_maps runs on a GPU only (no CPU fallback): no device is visible")
+    dev = seg.device if seg.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    stack = seg.to(dev)
+    d2 = ops.labelmap_distance(stack.unsqueeze(0) if seg.dim() == 2 else stack, outside)
+    d2 = d2[0] if seg.dim() == 2 else d2
+    return d2 if squared else d2.to(torch.float64).sqrt().to(torch.float32)
+
+
+def aim_point_rows(maps: torch.Tensor, N: int, border_outside: bool = True, ids: torch.Tensor | None = None,
+                   n_ids: torch.Tensor | None = None) -> torch.Tensor:
+    """(B, H, W) device id maps -> (B, N, 4) int32 rows [x, y, d2max, 0] of `ops.labelmap_aim_points`, the tie between
+    equal distances broken towards the centroid: statistics, distance map and aim points, nothing copied to the host."""
+    stats = ops.labelmap_instance_stats(maps, ids, n_ids, N=N)
+    d2 = ops.labelmap_distance(maps, border_outside)
+    return ops.labelmap_aim_points(maps, d2, ids, n_ids, N=N, stats=stats)
+
+
+def rows_to_aim_points(rows: torch.Tensor):
+    """(..., N, 4) int32 rows of `ops.labelmap_aim_points` -> point (..., N, 2) int64 (x, y), (-1, -1) for an id without
+    a pixel, and clearance (..., N) float64 = sqrt(d2max), NaN for such an id.  Works on either device."""
+    point = rows[..., :2].to(torch.int64)
+    clearance = rows[..., 2].to(torch.float64).sqrt()
+    return point, torch.where(rows[..., 0] >= 0, clearance, torch.full_like(clearance, float("nan")))
+
+
+def aim_points(segmentation, n: int | None = None, ids=None, border: str = "outside"):
+    """Where to aim inside every instance of one (H, W) id map or a (B, H, W) stack (maps as for
+    `instance_statistics`): the instance's pixel farthest from everything that is not the instance -- the maximum of its
+    interior distance transform (`distance_maps`).  Unlike the centroid it is always a pixel of the instance.  Among
+    pixels at the same distance the one nearest the centroid is taken, then the first in raster order.
+
+    - `n`: the instances are the ids 0 .. n-1, as the post-processor numbers them.
+    - `ids`: a list of raw ids (one list for every map of a stack), any order; the results follow it.
+    Returns device tensors (point (..., N, 2) int64 (x, y), clearance (..., N) float64): the clearance is the distance
+    at the point -- the radius that stays inside the instance; an id without a pixel has point (-1, -1) and a NaN
+    clearance."""
+    if (n is None) == (ids is None):
+        raise ValueError("aim_points: give either n (ids 0 .. n-1) or ids")
+    seg = _id_maps(segmentation, "aim_points")
+    outside = _border_outside(border, "aim_points")
+    back = None
+    if ids is not None:
+        raw = [int(v) for v in ids]
+        order = sorted(set(raw))
+        if len(order) != len(raw):
+            raise ValueError("aim_points: ids must be distinct")
+        back = [order.index(v) for v in raw]
+    if not torch.cuda.is_available():
+        raise _lib.Wm2fError("aim_points runs on a GPU only (no CPU fallback): no device is visible")
+    dev = seg.device if seg.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    maps = seg.to(dev)
+    maps = maps.unsqueeze(0) if seg.dim() == 2 else maps
+    B = maps.shape[0]
+    if ids is None:
+        rows = aim_point_rows(maps, int(n), outside)
+    else:
+        N = max(1, len(order))
+        ids_t = torch.tensor(order + [0] * (N - len(order)), dtype=torch.int32).expand(B, N).contiguous().to(dev)
+        n_ids = torch.full((B,), len(order), dtype=torch.int32).to(dev)
+        rows = aim_point_rows(maps, N, outside, ids_t, n_ids)
+        rows = rows[:, torch.tensor(back, dtype=torch.int64).to(dev)]  # the caller's order
+    if seg.dim() == 2:
+        rows = rows[0]
+    return rows_to_aim_points(rows)
+
+
+def add_aim_points(segments, rows) -> None:
+    """The host half of `return_aim_points=True`: rows (n, 4) host values [x, y, d2max, 0] for the ids 0 .. n-1 ->
+    "aim_point" ((x, y) ints, None for an instance without a pixel) and "clearance" (float, NaN then) on every entry."""
+    for info in segments:
+        x, y, d2max = (int(v) for v in rows[int(info["id"])][:3])
+        info["aim_point"] = (x, y) if x >= 0 else None
+        info["clearance"] = float(np.sqrt(np.float64(d2max))) if x >= 0 else float("nan")
 
 
 @dataclasses.dataclass(frozen=True)

@@ -181,6 +181,71 @@ def labelmap_instance_stats(maps: torch.Tensor, ids: torch.Tensor | None = None,
     return stats
 
 
+def labelmap_distance(maps: torch.Tensor, border_outside: bool = True) -> torch.Tensor:
+    """(B, H, W) id maps (fp32 with -1 background, int32 or uint8) -> (B, H, W) int32 squared Euclidean distance of every
+    pixel to the nearest position that does not carry its id (wm2f_labelmap_distance), 0 for a pixel without an id.
+    `border_outside`: the positions just beyond the image count as not carrying the id; without it only real pixels do,
+    and a pixel whose id fills its whole image gets INT32_MAX."""
+    if not isinstance(maps, torch.Tensor):
+        raise TypeError("labelmap_distance: expected a tensor")
+    maps = _req(maps, "maps", maps.dtype)
+    dt = _dtype_code(maps, (torch.float32, torch.int32, torch.uint8),
+                     f"labelmap_distance: maps fp32 / int32 / uint8, got {maps.dtype}")
+    if maps.dim() != 3:
+        raise ValueError(f"labelmap_distance: maps must be (B, H, W), got {tuple(maps.shape)}")
+    B, H, W = (int(v) for v in maps.shape)
+    if B == 0 or H == 0 or W == 0:
+        raise ValueError(f"labelmap_distance: bad size {tuple(maps.shape)}")
+    d2 = torch.empty(B, H, W, device=maps.device, dtype=torch.int32)
+    nbytes = int(load().wm2f_labelmap_distance_workspace(B, H, W))
+    ws = torch.empty(max(nbytes, 1), device=maps.device, dtype=torch.uint8)  # an unsupported size: the launch reports it
+    _launch("wm2f_labelmap_distance", maps, _p(maps), dt, _p(d2), _p(ws), B, H, W, int(bool(border_outside)),
+            tag="labelmap_distance")
+    return d2
+
+
+def labelmap_aim_points(maps: torch.Tensor, d2: torch.Tensor, ids: torch.Tensor | None = None,
+                        n_ids: torch.Tensor | None = None, N: int | None = None,
+                        stats: torch.Tensor | None = None) -> torch.Tensor:
+    """(B, H, W) id maps and their `labelmap_distance` -> (B, N, 4) int32 [x, y, d2max, 0] per id
+    (wm2f_labelmap_aim_points): a pixel of the instance where d2 is largest -- among equals the one nearest the rounded
+    centroid of `stats` (`labelmap_instance_stats` of the same maps and rows; without it this term is 0), then the first
+    in raster order; [-1, -1, 0, 0] for an id without a pixel.  `ids` / `n_ids` / `N` as in `labelmap_instance_stats`."""
+    if not isinstance(maps, torch.Tensor):
+        raise TypeError("labelmap_aim_points: expected tensors")
+    maps = _req(maps, "maps", maps.dtype)
+    dt = _dtype_code(maps, (torch.float32, torch.int32, torch.uint8),
+                     f"labelmap_aim_points: maps fp32 / int32 / uint8, got {maps.dtype}")
+    d2 = _req(d2, "d2", torch.int32)
+    if maps.dim() != 3 or d2.shape != maps.shape:
+        raise ValueError(f"labelmap_aim_points: maps and d2 must be (B, H, W), got {tuple(maps.shape)} and {tuple(d2.shape)}")
+    B, H, W = (int(v) for v in maps.shape)
+    if (ids is None) != (n_ids is None):
+        raise ValueError("labelmap_aim_points: ids and n_ids go together")
+    if ids is not None:
+        ids, n_ids = _req(ids, "ids", torch.int32), _req(n_ids, "n_ids", torch.int32)
+        if ids.dim() != 2 or ids.shape[0] != B or n_ids.shape != (B,) or (N is not None and int(N) != ids.shape[1]):
+            raise ValueError("labelmap_aim_points: shapes disagree")
+        N = int(ids.shape[1])
+    elif N is None:
+        raise ValueError("labelmap_aim_points: N is needed without an id list")
+    N = int(N)
+    if N < 0 or B == 0 or H == 0 or W == 0:
+        raise ValueError("labelmap_aim_points: bad size")
+    if stats is not None:
+        stats = _req(stats, "stats", torch.int64)
+        if stats.shape != (B, N, 8):
+            raise ValueError(f"labelmap_aim_points: stats must be ({B}, {N}, 8), got {tuple(stats.shape)}")
+    points = torch.empty(B, N, 4, device=maps.device, dtype=torch.int32)
+    if N == 0:
+        return points
+    nbytes = int(load().wm2f_labelmap_aim_points_workspace(B, N))
+    ws = torch.empty(max(nbytes, 8), device=maps.device, dtype=torch.uint8)  # an unsupported size: the launch reports it
+    _launch("wm2f_labelmap_aim_points", maps, _p(maps), dt, _p(d2), _p(ids), _p(n_ids), _p(stats), _p(points), _p(ws),
+            B, H, W, N, tag="labelmap_aim_points")
+    return points
+
+
 def panoptic_match(hist, pred_label, gt_label, n_pred, n_gt, void_as_background: bool = False):
     """PQ's segment matching of B images (wm2f_panoptic_match): hist (B, P+1, G+1), pred_label (B, P), gt_label (B, G),
     n_pred / n_gt (B) int32.  Returns gt_match (B, G) int32 (matched prediction row, -1 false negative, -2 no such GT),

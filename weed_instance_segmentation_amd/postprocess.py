@@ -108,7 +108,7 @@ class Mask2FormerInstancePostProcessor:
                                            overlap_mask_area_threshold: float = 0.8, target_sizes=None,
                                            return_coco_annotation: bool = False, return_binary_maps: bool = False,
                                            return_instance_stats: bool = False, return_polygons: bool = False,
-                                           clean=None):
+                                           clean=None, return_aim_points: bool = False):
         """`clean=CleanOptions(...)` (not an argument of the dependency; `instances.CleanOptions`) repairs every id map on
         the device before anything is taken from it: pieces below `min_area` dropped, with
         keep="largest" one connected piece per instance, with fill_holes=True enclosed background painted.  Entries of
@@ -125,7 +125,12 @@ class Mask2FormerInstancePostProcessor:
         "area" (int), "bbox" ([x, y, w, h] ints, COCO) and "centroid" ((cx, cy) floats, None when the area is 0) of the
         instance's pixels in the returned id map -- after later instances have painted over earlier ones, whatever
         form `segmentation` is returned in -- from one more launch per distinct target size and one more
-        device-to-host copy."""
+        device-to-host copy.
+        `return_aim_points=True` (not an argument of the dependency) adds "aim_point" ((x, y) ints: the instance's pixel
+        farthest from everything that is not the instance, None for an instance without a pixel) and "clearance" (float:
+        the distance there) to every `segments_info` entry, computed on the returned id map -- after painting, after
+        `clean=`, at the target size -- once per distinct target size, with one more device-to-host copy (DESIGN
+        section 36).  Independent of `return_instance_stats`."""
         if return_coco_annotation and return_binary_maps:
             raise ValueError("return_coco_annotation and return_binary_maps can not be both set to True.")
         if clean is not None:
@@ -169,6 +174,7 @@ class Mask2FormerInstancePostProcessor:
         kept_q_all = torch.zeros(B, Q, dtype=torch.int32, device=dev)
         stats_all = torch.zeros(B, Q, 8, dtype=torch.int64, device=dev) if return_instance_stats else None
         new_id_all = torch.full((B, Q), -1, dtype=torch.int64, device=dev) if clean is not None else None
+        aim_all = torch.zeros(B, Q, 4, dtype=torch.int32, device=dev) if return_aim_points else None
         for size in dict.fromkeys(sizes):  # one launch group per distinct target size
             rows = [i for i in range(B) if sizes[i] == size]
             ridx = torch.tensor(rows, device=dev)
@@ -190,6 +196,9 @@ class Mask2FormerInstancePostProcessor:
             kept_q_all[ridx] = kept_q
             if return_instance_stats:
                 stats_all[ridx] = ops.labelmap_instance_stats(seg, N=Q)
+            if return_aim_points:
+                from .instances import aim_point_rows
+                aim_all[ridx] = aim_point_rows(seg, Q)
             if return_coco_annotation:  # one encode per distinct target size, whatever the number of instances
                 from .rle import encode_label_maps
                 for i, rles in zip(rows, encode_label_maps(seg, n=Q, format="hf")):
@@ -206,6 +215,9 @@ class Mask2FormerInstancePostProcessor:
         if return_instance_stats:
             from .instances import stats_to_boxes
             area, bbox, centroid = (t.tolist() for t in stats_to_boxes(stats_all.cpu()))
+        if return_aim_points:
+            from .instances import add_aim_points
+            aim_cpu = aim_all.cpu().numpy()
         results = []
         for i in range(B):
             ks = torch.nonzero(keep_cpu[i]).flatten().tolist()
@@ -218,6 +230,8 @@ class Mask2FormerInstancePostProcessor:
                     seg_info["area"] = area[i][r]
                     seg_info["bbox"] = bbox[i][r]
                     seg_info["centroid"] = tuple(centroid[i][r]) if area[i][r] > 0 else None
+            if return_aim_points:
+                add_aim_points(segments, aim_cpu[i])
             segmentation = seg_out[i]
             if return_coco_annotation:
                 segmentation = rle_out[i]

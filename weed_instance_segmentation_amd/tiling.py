@@ -154,7 +154,7 @@ def _tile_tables(results, T: int):
 
 
 def merge_tile_results(results, grid: TileGrid, merge_threshold=(1, 2), return_instance_stats: bool = False,
-                       clean=None) -> dict:
+                       clean=None, return_aim_points: bool = False) -> dict:
     """Merge the per-tile results of `post_process_instance_segmentation(target_sizes=[(grid.th, grid.tw)] * T)` (tiles in
     `grid` order) into one image's result: {"segmentation": (H, W) int32 on the device with -1 background,
     "segments_info": [...]}, entries as `merged_segments_info` gives them.
@@ -169,7 +169,11 @@ def merge_tile_results(results, grid: TileGrid, merge_threshold=(1, 2), return_i
     `clean=CleanOptions(...)` repairs the composed map as the post-processor's `clean=` does -- a
     plant cut at a cell border can leave slivers that survive as pieces of the merged id: entries whose instance owns
     no pixel afterwards are dropped, the rest renumbered 0 .. n'-1 in order, and the statistics are taken from the
-    cleaned map.  The new ids travel in the same device-to-host copy."""
+    cleaned map.  The new ids travel in the same device-to-host copy.
+
+    `return_aim_points=True` adds "aim_point" and "clearance" of the merged (and cleaned) map's instances, as the
+    post-processor does: the point of the field map a tool would be driven from.  They travel in the
+    same copy too."""
     results = list(results)
     T = grid.n_tiles
     if len(results) != T:
@@ -213,6 +217,9 @@ def merge_tile_results(results, grid: TileGrid, merge_threshold=(1, 2), return_i
         back.append(clean_stats[0, :, 7])
     if return_instance_stats and n_stats:
         back.append(ops.labelmap_instance_stats(out.unsqueeze(0), N=n_stats).reshape(-1))
+    if return_aim_points and n_stats:
+        from .instances import add_aim_points, aim_point_rows
+        back.append(aim_point_rows(out.unsqueeze(0), n_stats).reshape(-1).to(torch.int64))
     host = torch.cat(back).cpu()  # the one device-to-host copy
     segments = merged_segments_info(host[:T * N].view(T, N).numpy(), int(host[T * N]), results)
     rest = host[T * N + 1:]
@@ -221,12 +228,16 @@ def merge_tile_results(results, grid: TileGrid, merge_threshold=(1, 2), return_i
         rest = rest[n_stats:]
     if return_instance_stats and segments:
         from .instances import stats_to_boxes
-        stats = rest.view(-1, 8)[:len(segments)]
+        stats = rest[:n_stats * 8].view(-1, 8)[:len(segments)]
         area, bbox, centroid = (v.tolist() for v in stats_to_boxes(stats))
         for k, info in enumerate(segments):
             info["area"] = area[k]
             info["bbox"] = bbox[k]
             info["centroid"] = tuple(centroid[k]) if area[k] > 0 else None
+    if return_instance_stats and n_stats:
+        rest = rest[n_stats * 8:]
+    if return_aim_points and segments:
+        add_aim_points(segments, rest[:n_stats * 4].view(-1, 4).numpy())
     return {"segmentation": out, "segments_info": segments}
 
 
@@ -244,7 +255,8 @@ def _device_image(image) -> torch.Tensor:
 
 def segment_tiled(image, model, processor, tile: int = 1024, overlap: int = 256, batch_size: int = 4,
                   threshold: float = 0.5, mask_threshold: float = 0.5, overlap_mask_area_threshold: float = 0.8,
-                  merge_threshold=(1, 2), return_instance_stats: bool = False, clean=None) -> dict:
+                  merge_threshold=(1, 2), return_instance_stats: bool = False, clean=None,
+                  return_aim_points: bool = False) -> dict:
     """Instance segmentation of an image of any size at native resolution: overlapping tiles (`tile_windows`), `batch_size`
     of them at a time through `processor(images=...)`, `model(pixel_values=...)` under no_grad and
     `processor.post_process_instance_segmentation(target_sizes=tile size)`, then `merge_tile_results`.  The image (PIL
@@ -252,8 +264,8 @@ def segment_tiled(image, model, processor, tile: int = 1024, overlap: int = 256,
     than one tile takes the same route with one tile.  `processor` is this package's `Mask2FormerImageProcessor` (or
     anything that takes a list of device uint8 (h, w, 3) tensors and post-processes into id maps on the device); it is
     called with `images=` alone, so its own size settings decide how a tile is fed.  `clean=CleanOptions(...)` repairs
-    the merged map (`merge_tile_results`); the tiles themselves are merged as predicted.  Returns `merge_tile_results`'s
-    dictionary."""
+    the merged map (`merge_tile_results`); the tiles themselves are merged as predicted; `return_aim_points=True` adds the
+    merged map's aim points and clearances there.  Returns `merge_tile_results`'s dictionary."""
     batch_size = int(batch_size)
     if batch_size < 1:
         raise ValueError(f"segment_tiled: batch_size must be at least 1, got {batch_size}")
@@ -270,7 +282,7 @@ def segment_tiled(image, model, processor, tile: int = 1024, overlap: int = 256,
                 outputs, threshold=threshold, mask_threshold=mask_threshold,
                 overlap_mask_area_threshold=overlap_mask_area_threshold, target_sizes=[(grid.th, grid.tw)] * len(batch))
     return merge_tile_results(results, grid, merge_threshold=merge_threshold, return_instance_stats=return_instance_stats,
-                              clean=clean)
+                              clean=clean, return_aim_points=return_aim_points)
 
 
 # ---------------------------------------------------------------------------------------------- the semantic route
