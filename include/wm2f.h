@@ -1469,6 +1469,56 @@ int wm2f_labelmap_clean(const void* map, int dtype, void* out, int out_dtype, in
                         void* workspace, int B, int H, int W, int N, int keep, int64_t min_area, int fill_holes,
                         int64_t max_hole_area, int relabel, int phase, void* stream);
 
+/* ---- splitting touching instances: a watershed of the interior distance -----------------------
+ * Every route that makes instances ends in "one connected blob = one plant"; two plants whose leaves touch, or that one
+ * query painted, are one instance.  This call parts them where the blob has a neck, for a whole (B, H, W) stack in a
+ * fixed chain of launches whatever the number of instances, basins and images.  tests/split_reference.py restates the
+ * rule in numpy.
+ * Input: map (B, H, W) WM2F_F32, WM2F_I32 or WM2F_U8, ids by wm2f_labelmap_instance_stats' rule; the instances are the
+ *   ids 0 .. N-1, every other pixel is background (as for wm2f_labelmap_clean).  d2 (B, H, W) int32: the output of
+ *   wm2f_labelmap_distance for the same map (either border mode).
+ * Definitions: lin(p) = y * W + x.  key(p) = (d2[p] << 32) | (0xFFFFFFFF - lin(p)), unsigned 64-bit, unique per pixel:
+ *   the larger distance wins, among equal distances the earlier pixel in raster order.
+ * ASCENT.  up(p) is the pixel of largest key among p and those of its 8 neighbours that carry p's id.  A pixel with
+ *   up(p) = p is a PEAK.  Following up from an instance pixel ends at a peak (keys strictly increase); the pixels that
+ *   end at one peak are a BASIN.
+ * GROUPS.  A group is a set of basins of one id; at the start every basin is its own group.  A group's peak is the peak
+ *   of largest key among its basins; peak_d2(G) and peak_lin(G) are that pixel's distance and position.
+ * ROUNDS.  `rounds` synchronous rounds; every decision of a round reads the state at the round's start.
+ *   1. For every 8-adjacent pair p, q of equal id in different groups the pass height is s = min(d2[p], d2[q]).
+ *   2. A group G takes, over all such pairs it is part of, the largest (s << 32) | (0xFFFFFFFF - peak_lin(other group)):
+ *      its highest pass, among equal passes the neighbour whose peak comes first in raster order: (s*, O).
+ *   3. G is linked under O when key(peak O) > key(peak G) and
+ *      (peak_d2(G) < min_peak_d2  or  s* * den^2 >= num^2 * peak_d2(G), in int64).
+ *   4. After all decisions the groups are the trees of links.  Links go strictly up in peak key: no cycles, and a
+ *      tree's root is its group's peak.
+ *   A part merges into the higher neighbour across its highest pass when the neck is at least num / den of the part's
+ *   own clearance, or when the part's clearance is below sqrt(min_peak_d2).
+ * OUTPUT.  out (B, H, W) int32, -1 on background.  For each id k the group with the largest peak key keeps k; every
+ *   other group gets N, N+1, ... in raster order of its peak pixel, over the whole image.  M is the size of the output
+ *   id space: a group whose id would be >= M is not split off, its pixels keep k.
+ *   info (B, M, 4) int32 per output id: [parent_id, peak_x, peak_y, peak_d2], parent_id = k for k itself and for the
+ *   groups split off k; [-1, -1, -1, 0] for an id without a pixel.
+ *   status (B, 4) int32: [ids wanted (N + extra groups, uncapped), basins at the start, links made in the last of the
+ *   `rounds` rounds, rounds].  A non-zero third entry says that more rounds would have merged more; the result is
+ *   still the defined result of `rounds` rounds.
+ *   Disconnected pieces of one id are never adjacent, so they come out as separate instances.
+ * Limits: H, W <= 16384, B <= 32, N <= M <= 4096, else WM2F_EUNSUPPORTED, reported before a pointer is looked at;
+ *   1 <= rounds <= 32, 0 <= num <= den, 1 <= den <= 1024, min_peak_d2 >= 0, else WM2F_EINVAL.  out must not overlap map
+ *   or d2.  workspace: wm2f_labelmap_split_workspace(B, H, W, M) bytes (-1 for a bad size), 16-byte aligned like info
+ *   and status, no clearing needed: 16 bytes per pixel (id, forest pointer, and 8 bytes that hold a group's best pass
+ *   during the rounds and the new ids after them), 8 per (image, id), 4 per 1024 pixels and 136 per image.
+ * Kernels: init; ascent (decodes the map, up(p), counts the peaks); flatten (every pixel follows its pointer to the fixed
+ *   point: the basins); per round pass (a pixel and its four forward neighbours, a 64-bit atomicMax into both groups'
+ *   slots after a look at the slot), decide (a thread per group peak) and flatten, each returning at once when the
+ *   round before linked nothing; keep (64-bit atomicMax per id), count, scan, assign (the extras in raster order) and
+ *   paint.  8 + 3 * rounds launches.  Integer max and add atomics only: bit-identical from run to run.  No call
+ *   allocates, keeps state or waits for the device. */
+int64_t wm2f_labelmap_split_workspace(int B, int H, int W, int M);
+int wm2f_labelmap_split(const void* map, int dtype, const int32_t* d2, int32_t* out, int32_t* info, int32_t* status,
+                        void* workspace, int B, int H, int W, int N, int M, int num, int den, int min_peak_d2, int rounds,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,8 +12,8 @@ from .modeling import Mask2FormerForUniversalSegmentation, Mask2FormerForUnivers
 __version__ = "0.1.0"
 from .postprocess import Mask2FormerInstancePostProcessor  # noqa: F401
 from .metrics import MeanAveragePrecision  # noqa: F401
-from .instances import (CleanOptions, aim_points, boundary_dilation, boundary_maps, clean_label_maps,  # noqa: F401
-                        distance_maps, instance_statistics)
+from .instances import (CleanOptions, SplitOptions, aim_points, boundary_dilation, boundary_maps,  # noqa: F401
+                        clean_label_maps, distance_maps, instance_statistics, split_label_maps)
 from .rle import (coco_results, decode_rle, encode_label_maps, rle_from_string, rle_to_string,  # noqa: F401
                   save_coco_results)
 from .contours import (instance_polygons, save_via_annotations, trace_label_maps, via_annotations)  # noqa: F401

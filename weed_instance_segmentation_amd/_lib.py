@@ -195,6 +195,8 @@ SIGNATURES = {
     "wm2f_tile_blend": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_labelmap_clean_workspace": (c_int64, [_I, _I, _I, _I]),
     "wm2f_labelmap_clean": (c_int, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, c_int64, _I, c_int64, _I, _I, _P]),
+    "wm2f_labelmap_split_workspace": (c_int64, [_I, _I, _I, _I]),
+    "wm2f_labelmap_split": (c_int, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
 }
 
 # additions of the profiling library (include/wm2f_prof.h)

@@ -102,26 +102,28 @@ def resize_nearest(mask: torch.Tensor, dsize) -> torch.Tensor:
     return ops.resize_nearest_tables(mask, cv2_nearest_table(sh, h), cv2_nearest_table(sw, w))
 
 
-def semantic_to_instance_map(semantic_mask: torch.Tensor, size=None):
+def semantic_to_instance_map(semantic_mask: torch.Tensor, size=None, split=None):
     """PhenoBench's rule (datasets/pheno_bench/dataset.py:85-116) on the device: optional nearest resize to
     size = (w, h) (cv2's dsize order), then one instance per 8-connected component of each nonzero class, classes in
     ascending value order, ids 1, 2, ... with 255 skipped, 255 outside every component.
     `semantic_mask` is (H, W) uint8, uint16 or int32.  Returns (instance_map (h, w) int32 on the device,
-    id_to_semantic {id: class value})."""
+    id_to_semantic {id: class value}).
+    `split=SplitOptions(...)` (not in the reference) parts components that are touching plants: the
+    parts split off continue the numbering after the last id, 255 skipped, and carry their parent's class."""
     m = _require_cuda(semantic_mask, "semantic_mask")
     if m.dim() != 2 or m.dtype not in (torch.uint8, torch.uint16, torch.int32):
         raise TypeError(f"semantic_mask: expected (H, W) uint8 / uint16 / int32, got {tuple(m.shape)} {m.dtype}")
     ty, tx, hw = _tables(m.shape, size)
     out, comp_class, n = ops.label_components(m, _lib.WM2F_CCL_VALUE, hw, ty, tx)
-    return out, _id_dict(comp_class.cpu().numpy(), n, None)
+    return _split_instances(out, _id_dict(comp_class.cpu().numpy(), n, None), n, split)
 
 
-def color_mask_to_instance_map(mask_rgb: torch.Tensor, color_map: dict, size=None):
+def color_mask_to_instance_map(mask_rgb: torch.Tensor, color_map: dict, size=None, split=None):
     """The CropWeed PNG rule (dataset_from_png_annotations.py:80-116) on the device: optional nearest resize to
     size = (w, h), then one instance per 8-connected component of the pixels equal to each colour, colours tried in the
     dict's order, ids 1, 2, ... with 255 skipped.  `mask_rgb` is (H, W, 3) uint8 RGB; `color_map` maps a class name to
     {'color': [r, g, b], 'id': semantic id}.  Returns (instance_map (h, w) int32 on the device,
-    id_to_semantic {id: color_map[...]['id']})."""
+    id_to_semantic {id: color_map[...]['id']}).  `split=SplitOptions(...)`: as for `semantic_to_instance_map`."""
     m = _require_cuda(mask_rgb, "mask_rgb")
     if m.dim() != 3 or m.shape[2] != 3 or m.dtype != torch.uint8:
         raise TypeError(f"mask_rgb: expected (H, W, 3) uint8, got {tuple(m.shape)} {m.dtype}")
@@ -131,7 +133,7 @@ def color_mask_to_instance_map(mask_rgb: torch.Tensor, color_map: dict, size=Non
     colors = [[int(c) for c in info["color"]] for info in infos]
     ty, tx, hw = _tables(m.shape[:2], size)
     out, comp_class, n = ops.label_components(m, _lib.WM2F_CCL_RGB, hw, ty, tx, colors=colors)
-    return out, _id_dict(comp_class.cpu().numpy(), n, [int(info["id"]) for info in infos])
+    return _split_instances(out, _id_dict(comp_class.cpu().numpy(), n, [int(info["id"]) for info in infos]), n, split)
 
 
 def _id_dict(classes: np.ndarray, n: int, semantic_of_colour):
@@ -140,6 +142,33 @@ def _id_dict(classes: np.ndarray, n: int, semantic_of_colour):
     if semantic_of_colour is None:
         return {int(i): int(c) for i, c in zip(ids, classes)}
     return {int(i): semantic_of_colour[int(c) - 1] for i, c in zip(ids, classes)}
+
+
+def _loader_id(k):
+    """The loader's id of the k-th instance, k from 0: 1, 2, ... with 255 skipped (a number or an array)."""
+    return k + 1 + (k >= 254)
+
+
+def _split_instances(out: torch.Tensor, id_to_semantic: dict, n: int, split):
+    """`split=` of the two PNG loaders: the loader's map (ids 1 .. with 255 skipped, 255 background) is renumbered
+    0 .. n-1 with -1 background, split, and numbered back; the dictionary gets the parts split off."""
+    if split is None:
+        return out, id_to_semantic
+    from .instances import SplitOptions, split_rows
+    if not isinstance(split, SplitOptions):
+        raise TypeError(f"split must be a SplitOptions or None, got {type(split).__name__}")
+    if n == 0:
+        return out, id_to_semantic
+    compact = torch.where(out == 255, -1, out - 1 - (out > 255).to(out.dtype))
+    parted, info, status = split_rows(compact.unsqueeze(0), n, split)
+    parted = parted[0]
+    out = torch.where(parted < 0, 255, _loader_id(parted)).to(torch.int32)
+    host = torch.cat([status[0, :1], info[0, :, 0]]).cpu().numpy()
+    n_out, parents = min(int(host[0]), split.id_space(n)), host[1:]
+    ids = dict(id_to_semantic)
+    for j in range(n, n_out):
+        ids[int(_loader_id(j))] = id_to_semantic[int(_loader_id(int(parents[j])))]
+    return out, ids
 
 
 def _read_semantic_png(path: str) -> np.ndarray:
@@ -160,11 +189,14 @@ def _read_semantic_png(path: str) -> np.ndarray:
 
 
 class _AnnotatedPngDataset(torch.utils.data.Dataset):
-    """File pairing and item assembly shared by the two loaders; subclasses give the mask file and the instance map."""
+    """File pairing and item assembly shared by the two loaders; subclasses give the mask file and the instance map.
+    `split_touching=SplitOptions(...)` (not in the reference; default off) parts connected components that are touching
+    plants, see `semantic_to_instance_map`."""
 
     def __init__(self, image_folder_path, annotation_path, processor, label2id: dict, max_input_dim: int = 1024,
-                 max_images=None, device="cuda", augment=None, generator=None, compact: bool = False):
+                 max_images=None, device="cuda", augment=None, generator=None, compact: bool = False, split_touching=None):
         self.image_folder = image_folder_path
+        self.split_touching = split_touching  # a SplitOptions: components that are touching plants are parted (section 37)
         self.annotation_path = annotation_path
         self.processor = processor
         self.label2id = label2id
@@ -252,7 +284,7 @@ class PhenoBenchDataset(_AnnotatedPngDataset):
         return _read_semantic_png(path)
 
     def _instance_map(self, mask, dsize):
-        return semantic_to_instance_map(mask, dsize)
+        return semantic_to_instance_map(mask, dsize, split=self.split_touching)
 
 
 class CropWeedDataset(_AnnotatedPngDataset):
@@ -276,7 +308,7 @@ class CropWeedDataset(_AnnotatedPngDataset):
         }
 
     def _instance_map(self, mask, dsize):
-        return color_mask_to_instance_map(mask, self.color_map(), dsize)
+        return color_mask_to_instance_map(mask, self.color_map(), dsize, split=self.split_touching)
 
 
 # ------------------------------------------------------------------------------------------- polygons

@@ -28,10 +28,20 @@ tiled route and `test_with_metrics` take the same `CleanOptions` as `clean=`.
 `distance_maps` and `aim_points`: the exact interior Euclidean distance transform of every instance
 at once, and per instance the pixel where it is largest -- where to aim inside a plant whose centroid may lie on soil --
 in seven launches of csrc/distance.hip whatever the number of instances.
+
+    from weed_instance_segmentation_amd import SplitOptions, split_label_maps
+    parted = split_label_maps(prediction["segmentation"], n, SplitOptions(min_neck_ratio=0.5))
+
+`split_label_maps` parts touching plants that one instance covers: a watershed of the interior
+distance whose basins are merged again wherever the neck between them is wide, in a fixed chain of launches of
+csrc/split.hip.  The post-processor, the tiled route, `test_with_metrics` and the PNG loaders take the same
+`SplitOptions` as `split=`.
 """
 from __future__ import annotations
 
 import dataclasses
+import math
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -306,3 +316,128 @@ def clean_label_maps(maps, n: int, options: CleanOptions | None = None, *, relab
     if seg.dim() == 2:
         out, stats = out[0], stats[0]
     return (out, stats) if return_stats else out
+
+
+def _exact(v) -> Fraction:
+    """A number as the exact fraction it is (numpy scalars through their Python value)."""
+    return v if isinstance(v, Fraction) else Fraction(v.item() if isinstance(v, np.generic) else v)
+
+
+@dataclasses.dataclass(frozen=True)
+class SplitOptions:
+    """How `split_label_maps` (and `split=` of the post-processor, `merge_tile_results`, `segment_tiled`,
+    `test_with_metrics` and the PNG loaders) parts an instance that covers touching plants.  Every pixel climbs the
+    instance's interior distance map to a peak; the pixels of one peak are a part; a part is merged into the higher
+    neighbour across its highest pass when the neck there is wide.
+
+    - `min_neck_ratio` in [0, 1]: a part stays separate only where the neck's clearance is below this fraction of the
+      part's own clearance (the distance at its peak).  0 merges everything that touches, 1 keeps nearly every peak.  The
+      kernel compares integers: the ratio becomes `Fraction(ratio).limit_denominator(1024)`.  The default of 0.5 is a
+      convention -- split only where the neck is narrower than half the smaller part's clearance -- and not a value
+      measured on field data.
+    - `min_clearance` >= 0 pixels: a part whose clearance is below it is always merged (min_peak_d2 = ceil(c^2)).
+    - `rounds` in [1, 32]: the synchronous merge rounds; ragged maps of hundreds of parts settle in 2 to 4.
+    - `border`: the border mode of the distance map, "outside" or "inside" (`distance_maps`).
+    - `max_instances`: the size of the output id space, at most 4096; parts past it are not split off.  None: twice the
+      map's instances, at least 64 more than them."""
+    min_neck_ratio: float = 0.5
+    min_clearance: float = 0.0
+    rounds: int = 8
+    border: str = "outside"
+    max_instances: int | None = None
+
+    def __post_init__(self):
+        for name in ("min_neck_ratio", "min_clearance"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating, Fraction)) or not math.isfinite(v):
+                raise ValueError(f"SplitOptions: {name} must be a finite number, got {v!r}")
+        if not 0 <= self.min_neck_ratio <= 1:
+            raise ValueError(f"SplitOptions: min_neck_ratio must be in [0, 1], got {self.min_neck_ratio!r}")
+        if not 0 <= self.min_clearance < 32768:
+            raise ValueError(f"SplitOptions: min_clearance must be in [0, 32768), got {self.min_clearance!r}")
+        if isinstance(self.rounds, bool) or not isinstance(self.rounds, (int, np.integer)) or not 1 <= self.rounds <= ops.split.MAX_ROUNDS:
+            raise ValueError(f"SplitOptions: rounds must be an integer in [1, {ops.split.MAX_ROUNDS}], got {self.rounds!r}")
+        _border_outside(self.border, "SplitOptions")
+        m = self.max_instances
+        if m is not None and (isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 0 <= m <= ops.split.MAX_IDS):
+            raise ValueError(f"SplitOptions: max_instances must be None or an integer in [0, {ops.split.MAX_IDS}], got {m!r}")
+
+    def neck_fraction(self) -> Fraction:
+        """min_neck_ratio as the kernel takes it: num / den with den <= 1024."""
+        return _exact(self.min_neck_ratio).limit_denominator(ops.split.MAX_DEN)
+
+    def id_space(self, n: int) -> int:
+        """M for a map of n instances: `max_instances`, or room for every instance to be halved and for 64 parts more."""
+        n = int(n)
+        m = min(ops.split.MAX_IDS, max(2 * n, n + 64)) if self.max_instances is None else int(self.max_instances)
+        if m < int(n):
+            raise ValueError(f"SplitOptions: max_instances = {m} is below the {n} instances of the map")
+        return m
+
+    def kernel_arguments(self) -> dict:
+        """The keywords of `ops.labelmap_split` after N and M."""
+        f = self.neck_fraction()
+        return {"num": f.numerator, "den": f.denominator, "min_peak_d2": math.ceil(_exact(self.min_clearance) ** 2),
+                "rounds": int(self.rounds)}
+
+
+def split_rows(maps: torch.Tensor, N: int, options: SplitOptions):
+    """(B, H, W) device id maps -> (out, info, status) of `ops.labelmap_split`: the distance map, then the split; nothing
+    is copied to the host."""
+    d2 = ops.labelmap_distance(maps, options.border == "outside")
+    return ops.labelmap_split(maps, d2, int(N), options.id_space(N), **options.kernel_arguments())
+
+
+def split_segments_info(segments, info, n_out: int) -> list:
+    """The host half of `split=`: `segments` (entries with ids 0 .. n-1) and the host rows info[j] =
+    [parent_id, x, y, d2] of the output ids -> the entries, followed by one for every id n .. n_out-1 that was split off:
+    a copy of its parent's entry with its own "id" and "split_from": parent_id."""
+    by_id = {int(s["id"]): s for s in segments}
+    out = list(segments)
+    for j in range(len(segments), int(n_out)):
+        parent = int(info[j][0])
+        if parent in by_id:
+            out.append({**by_id[parent], "id": j, "split_from": parent})
+    return out
+
+
+def split_label_maps(maps, n: int, options: SplitOptions | None = None, *, return_info: bool = False, **fields):
+    """Part the touching plants of one (H, W) id map or a (B, H, W) stack -- fp32 with -1 background (the
+    post-processor's map), int32 or uint8, on the device or the host (a host map is moved to the current GPU).  The
+    instances are the ids 0 .. n-1; every other value is background.  `options` (or its fields as keywords:
+    `split_label_maps(m, n, min_neck_ratio=0.75)`) says where a neck is a neck, see `SplitOptions`.
+
+    Per id the part with the highest peak keeps the id; the parts split off get n, n+1, ... in raster order of their
+    peaks.  Disconnected pieces of one id are never adjacent, so they come out as separate instances:
+    `clean_label_maps(..., keep="largest")` comes first when that is not wanted.
+
+    Returns an int32 device tensor of the input's shape with -1 background.  `return_info=True` returns
+    (map, parent, peaks, clearance, n_out), device tensors over the M = `max_instances` output ids: parent (..., M) int64
+    (the input id an output id belongs to, itself for 0 .. n-1, -1 for an id without a pixel), peaks (..., M, 2) int64
+    (x, y) of the part's peak ((-1, -1) then), clearance (..., M) float64, the distance at the peak (NaN then), and n_out
+    (...) int64, the number of output ids, at most M."""
+    if options is None:
+        options = SplitOptions(**fields)
+    elif not isinstance(options, SplitOptions):
+        raise TypeError(f"split_label_maps: options must be a SplitOptions, got {type(options).__name__}")
+    elif fields:
+        options = dataclasses.replace(options, **fields)
+    seg = _id_maps(maps, "split_label_maps")
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"split_label_maps: n must not be negative, got {n}")
+    M = options.id_space(n)
+    if not torch.cuda.is_available():
+        raise _lib.Wm2fError("split_label_maps runs on a GPU only (no CPU fallback): no device is visible")
+    dev = seg.device if seg.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    stack = seg.to(dev)
+    out, info, status = split_rows(stack.unsqueeze(0) if seg.dim() == 2 else stack, n, options)
+    if seg.dim() == 2:
+        out, info, status = out[0], info[0], status[0]
+    if not return_info:
+        return out
+    some = info[..., 1] >= 0
+    clearance = info[..., 3].to(torch.float64).sqrt()
+    clearance = torch.where(some, clearance, torch.full_like(clearance, float("nan")))
+    n_out = status[..., 0].to(torch.int64).clamp(max=M)
+    return out, info[..., 0].to(torch.int64), info[..., 1:3].to(torch.int64), clearance, n_out

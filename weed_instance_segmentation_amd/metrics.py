@@ -427,14 +427,15 @@ class MeanAveragePrecision:
 
 
 # --------------------------------------------------------------------------- drop-ins for models/metrics.py
-def test_with_metrics(model, processor, data_loader, device, iou_type="segm", results_json=None, clean=None) -> dict:
+def test_with_metrics(model, processor, data_loader, device, iou_type="segm", results_json=None, clean=None, split=None) -> dict:
     """models/metrics.py::test_with_metrics with the same arguments and result, through the label-map route.
     `iou_type` (not an argument of the reference) goes to MeanAveragePrecision: "segm", "bbox", "boundary" or a tuple of
     them; the boxes are those of the masks (`boxes_from_masks=True`), as this route has nothing else.
     `results_json` (not an argument of the reference either): a path that receives the evaluated predictions as a COCO
     results file (`rle.save_coco_results`), the images named by the batches' `file_names`, or numbered without them.
     `clean` (not an argument of the reference either): an `instances.CleanOptions` handed to the post-processor, so that
-    AP can be read with and without the repair of the id maps; a processor is only given the keyword when it is set."""
+    AP can be read with and without the repair of the id maps; a processor is only given the keyword when it is set.
+    `split` (not an argument of the reference either): an `instances.SplitOptions`, passed on in the same way."""
     model.eval()
     types = (iou_type,) if isinstance(iou_type, str) else tuple(iou_type) if isinstance(iou_type, (tuple, list)) else ()
     metric = MeanAveragePrecision(iou_type=iou_type, boxes_from_masks="bbox" in types)
@@ -450,7 +451,8 @@ def test_with_metrics(model, processor, data_loader, device, iou_type="segm", re
         predictions = processor.post_process_instance_segmentation(outputs=outputs, target_sizes=batch["target_sizes"],
                                                                    threshold=0.5, mask_threshold=0.5,
                                                                    **({} if results_json is None else {"return_instance_stats": True}),
-                                                                   **({} if clean is None else {"clean": clean}))
+                                                                   **({} if clean is None else {"clean": clean}),
+                                                                   **({} if split is None else {"split": split}))
         metric.update_from_maps([p["segmentation"] for p in predictions], [p["segments_info"] for p in predictions],
                                 batch["original_maps"], batch["id_mappings"])
         if results_json is not None:

@@ -108,7 +108,7 @@ class Mask2FormerInstancePostProcessor:
                                            overlap_mask_area_threshold: float = 0.8, target_sizes=None,
                                            return_coco_annotation: bool = False, return_binary_maps: bool = False,
                                            return_instance_stats: bool = False, return_polygons: bool = False,
-                                           clean=None, return_aim_points: bool = False):
+                                           clean=None, return_aim_points: bool = False, split=None):
         """`clean=CleanOptions(...)` (not an argument of the dependency; `instances.CleanOptions`) repairs every id map on
         the device before anything is taken from it: pieces below `min_area` dropped, with
         keep="largest" one connected piece per instance, with fill_holes=True enclosed background painted.  Entries of
@@ -130,13 +130,24 @@ class Mask2FormerInstancePostProcessor:
         farthest from everything that is not the instance, None for an instance without a pixel) and "clearance" (float:
         the distance there) to every `segments_info` entry, computed on the returned id map -- after painting, after
         `clean=`, at the target size -- once per distinct target size, with one more device-to-host copy (DESIGN
-        section 36).  Independent of `return_instance_stats`."""
+        section 36).  Independent of `return_instance_stats`.
+        `split=SplitOptions(...)` (not an argument of the dependency; `instances.SplitOptions`) parts touching plants that
+        one instance covers, after `clean=` and before everything that is taken from the map: the
+        part with the highest peak of the interior distance keeps the instance's id, every part split off gets the next
+        free id and a new `segments_info` entry after the existing ones -- a copy of its parent's (label, score) with its
+        own "id" and "split_from": the parent's id.  Statistics, aim points, the encoding, polygons and, with
+        `return_binary_maps=True`, the stack (cut from the map, as with `clean=`) describe the split map.  split=None
+        changes nothing."""
         if return_coco_annotation and return_binary_maps:
             raise ValueError("return_coco_annotation and return_binary_maps can not be both set to True.")
         if clean is not None:
             from .instances import CleanOptions, cleaned_segments_info
             if not isinstance(clean, CleanOptions):
                 raise TypeError(f"clean must be a CleanOptions or None, got {type(clean).__name__}")
+        if split is not None:
+            from .instances import SplitOptions, split_rows, split_segments_info
+            if not isinstance(split, SplitOptions):
+                raise TypeError(f"split must be a SplitOptions or None, got {type(split).__name__}")
         cls = outputs.class_queries_logits
         logits = outputs.masks_queries_logits
         if not logits.is_cuda:
@@ -172,9 +183,11 @@ class Mask2FormerInstancePostProcessor:
         rle_out: list = [None] * B
         keep_all = torch.zeros(B, Q, dtype=torch.bool, device=dev)
         kept_q_all = torch.zeros(B, Q, dtype=torch.int32, device=dev)
-        stats_all = torch.zeros(B, Q, 8, dtype=torch.int64, device=dev) if return_instance_stats else None
+        n_ids = Q if split is None else split.id_space(Q)  # the id space of the returned maps
+        stats_all = torch.zeros(B, n_ids, 8, dtype=torch.int64, device=dev) if return_instance_stats else None
         new_id_all = torch.full((B, Q), -1, dtype=torch.int64, device=dev) if clean is not None else None
-        aim_all = torch.zeros(B, Q, 4, dtype=torch.int32, device=dev) if return_aim_points else None
+        aim_all = torch.zeros(B, n_ids, 4, dtype=torch.int32, device=dev) if return_aim_points else None
+        split_all = torch.zeros(B, n_ids + 1, dtype=torch.int64, device=dev) if split is not None else None
         for size in dict.fromkeys(sizes):  # one launch group per distinct target size
             rows = [i for i in range(B) if sizes[i] == size]
             ridx = torch.tensor(rows, device=dev)
@@ -190,18 +203,24 @@ class Mask2FormerInstancePostProcessor:
             n_kept = keep.sum(1).to(torch.int32)
             seg = ops.instance_segmentation(lg, kept_q, n_kept, size)
             if clean is not None:  # in the map's own dtype, ids renumbered: everything below describes the cleaned map
-                seg, clean_stats, _ = ops.labelmap_clean(seg, Q, relabel=True, out_dtype=seg.dtype, **clean.kernel_arguments())
+                seg, clean_stats, n_kept = ops.labelmap_clean(seg, Q, relabel=True, out_dtype=seg.dtype, **clean.kernel_arguments())
                 new_id_all[ridx] = clean_stats[:, :, 7]
+            if split is not None:  # the kernel numbers the parts split off from Q; they continue each image's own ids
+                parted, info, status = split_rows(seg, Q, split)
+                shift = (Q - n_kept).view(-1, 1, 1)
+                seg = torch.where(parted >= Q, parted - shift, parted).to(seg.dtype)
+                split_all[ridx, :n_ids] = info[:, :, 0].to(torch.int64)
+                split_all[ridx, n_ids] = status[:, 0].clamp(max=n_ids).to(torch.int64)
             keep_all[ridx] = keep
             kept_q_all[ridx] = kept_q
             if return_instance_stats:
-                stats_all[ridx] = ops.labelmap_instance_stats(seg, N=Q)
+                stats_all[ridx] = ops.labelmap_instance_stats(seg, N=n_ids)
             if return_aim_points:
                 from .instances import aim_point_rows
-                aim_all[ridx] = aim_point_rows(seg, Q)
+                aim_all[ridx] = aim_point_rows(seg, n_ids)
             if return_coco_annotation:  # one encode per distinct target size, whatever the number of instances
                 from .rle import encode_label_maps
-                for i, rles in zip(rows, encode_label_maps(seg, n=Q, format="hf")):
+                for i, rles in zip(rows, encode_label_maps(seg, n=n_ids, format="hf")):
                     rle_out[i] = list(rles.values())  # ascending ids, -1 first, only ids that still own a pixel
             for j, i in enumerate(rows):
                 seg_out[i] = seg[j]
@@ -212,6 +231,8 @@ class Mask2FormerInstancePostProcessor:
         else:  # the new ids travel with the flags
             flags = torch.cat([keep_all.to(torch.int64), new_id_all], 1).cpu()
             keep_cpu, new_id_cpu, score_cpu = flags[:, :Q].bool(), flags[:, Q:].numpy(), pred_scores.cpu()
+        if split is not None:
+            split_cpu = split_all.cpu().numpy()
         if return_instance_stats:
             from .instances import stats_to_boxes
             area, bbox, centroid = (t.tolist() for t in stats_to_boxes(stats_all.cpu()))
@@ -225,6 +246,11 @@ class Mask2FormerInstancePostProcessor:
                         for r, j in enumerate(ks)]
             if clean is not None:  # the survivors are numbered 0 .. n'-1 in this order
                 segments = cleaned_segments_info(segments, new_id_cpu[i])
+            if split is not None:  # kernel ids Q, Q + 1, ... are the map's ids n, n + 1, ...
+                n = len(segments)
+                extras = int(split_cpu[i, n_ids]) - Q
+                segments = split_segments_info(segments, [[p] for p in split_cpu[i, :n]] + [[p] for p in split_cpu[i, Q:Q + extras]],
+                                               n + extras)
             if return_instance_stats:
                 for r, seg_info in enumerate(segments):
                     seg_info["area"] = area[i][r]
@@ -235,7 +261,7 @@ class Mask2FormerInstancePostProcessor:
             segmentation = seg_out[i]
             if return_coco_annotation:
                 segmentation = rle_out[i]
-            if return_binary_maps and ks and clean is None:
+            if return_binary_maps and ks and clean is None and split is None:
                 segmentation = ops.instance_maps(logits[i], kept_q_all[i], len(ks), sizes[i])
             elif return_binary_maps and segments:
                 ids = torch.arange(len(segments), device=dev, dtype=seg_out[i].dtype).view(-1, 1, 1)

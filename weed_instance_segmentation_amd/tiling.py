@@ -154,7 +154,7 @@ def _tile_tables(results, T: int):
 
 
 def merge_tile_results(results, grid: TileGrid, merge_threshold=(1, 2), return_instance_stats: bool = False,
-                       clean=None, return_aim_points: bool = False) -> dict:
+                       clean=None, return_aim_points: bool = False, split=None) -> dict:
     """Merge the per-tile results of `post_process_instance_segmentation(target_sizes=[(grid.th, grid.tw)] * T)` (tiles in
     `grid` order) into one image's result: {"segmentation": (H, W) int32 on the device with -1 background,
     "segments_info": [...]}, entries as `merged_segments_info` gives them.
@@ -173,7 +173,12 @@ def merge_tile_results(results, grid: TileGrid, merge_threshold=(1, 2), return_i
 
     `return_aim_points=True` adds "aim_point" and "clearance" of the merged (and cleaned) map's instances, as the
     post-processor does: the point of the field map a tool would be driven from.  They travel in the
-    same copy too."""
+    same copy too.
+
+    `split=SplitOptions(...)` parts touching plants of the merged (and cleaned) field map as the post-processor's
+    `split=` does -- the tile merge can only join instances, this parts them: a part split off gets
+    the next free id and an entry after the merged ones, a copy of its parent's with its own "id" and "split_from";
+    statistics and aim points describe the split map."""
     results = list(results)
     T = grid.n_tiles
     if len(results) != T:
@@ -192,6 +197,10 @@ def merge_tile_results(results, grid: TileGrid, merge_threshold=(1, 2), return_i
         from .instances import CleanOptions, cleaned_segments_info
         if not isinstance(clean, CleanOptions):
             raise TypeError(f"merge_tile_results: clean must be a CleanOptions or None, got {type(clean).__name__}")
+    if split is not None:
+        from .instances import SplitOptions, split_rows, split_segments_info
+        if not isinstance(split, SplitOptions):
+            raise TypeError(f"merge_tile_results: split must be a SplitOptions or None, got {type(split).__name__}")
     n_ids_h, labels_h = _tile_tables(results, T)
     N = int(labels_h.shape[1])
     tiles = torch.stack(maps)
@@ -212,32 +221,44 @@ def merge_tile_results(results, grid: TileGrid, merge_threshold=(1, 2), return_i
     n_stats = min(int(n_ids_h.sum()), MAX_MERGED_IDS)  # an upper bound of n_merged known without a copy
     cleaning = clean is not None and n_stats > 0
     if cleaning:  # merged ids beyond n_stats (then merged_segments_info raises below) would count as background
-        cleaned, clean_stats, _ = ops.labelmap_clean(out.unsqueeze(0), n_stats, relabel=True, **clean.kernel_arguments())
+        cleaned, clean_stats, n_merged = ops.labelmap_clean(out.unsqueeze(0), n_stats, relabel=True, **clean.kernel_arguments())
         out = cleaned[0]
         back.append(clean_stats[0, :, 7])
+    splitting = split is not None and n_stats > 0
+    n_rows = split.id_space(n_stats) if splitting else n_stats  # the id space of the returned map
+    if splitting:  # the kernel numbers the parts split off from n_stats; they continue the map's own ids
+        parted, info, status = split_rows(out.unsqueeze(0), n_stats, split)
+        out = torch.where(parted[0] >= n_stats, parted[0] - (n_stats - n_merged.view(())).to(torch.int32), parted[0])
+        back += [info[0, :, 0].to(torch.int64), status[0, :1].clamp(max=n_rows).to(torch.int64)]
     if return_instance_stats and n_stats:
-        back.append(ops.labelmap_instance_stats(out.unsqueeze(0), N=n_stats).reshape(-1))
+        back.append(ops.labelmap_instance_stats(out.unsqueeze(0), N=n_rows).reshape(-1))
     if return_aim_points and n_stats:
         from .instances import add_aim_points, aim_point_rows
-        back.append(aim_point_rows(out.unsqueeze(0), n_stats).reshape(-1).to(torch.int64))
+        back.append(aim_point_rows(out.unsqueeze(0), n_rows).reshape(-1).to(torch.int64))
     host = torch.cat(back).cpu()  # the one device-to-host copy
     segments = merged_segments_info(host[:T * N].view(T, N).numpy(), int(host[T * N]), results)
     rest = host[T * N + 1:]
     if cleaning:
         segments = cleaned_segments_info(segments, rest[:n_stats].numpy())
         rest = rest[n_stats:]
+    if splitting:
+        parents, extras = rest[:n_rows].numpy(), int(rest[n_rows]) - n_stats
+        n = len(segments)
+        segments = split_segments_info(segments, [[p] for p in parents[:n]] + [[p] for p in parents[n_stats:n_stats + extras]],
+                                       n + extras)
+        rest = rest[n_rows + 1:]
     if return_instance_stats and segments:
         from .instances import stats_to_boxes
-        stats = rest[:n_stats * 8].view(-1, 8)[:len(segments)]
+        stats = rest[:n_rows * 8].view(-1, 8)[:len(segments)]
         area, bbox, centroid = (v.tolist() for v in stats_to_boxes(stats))
         for k, info in enumerate(segments):
             info["area"] = area[k]
             info["bbox"] = bbox[k]
             info["centroid"] = tuple(centroid[k]) if area[k] > 0 else None
     if return_instance_stats and n_stats:
-        rest = rest[n_stats * 8:]
+        rest = rest[n_rows * 8:]
     if return_aim_points and segments:
-        add_aim_points(segments, rest[:n_stats * 4].view(-1, 4).numpy())
+        add_aim_points(segments, rest[:n_rows * 4].view(-1, 4).numpy())
     return {"segmentation": out, "segments_info": segments}
 
 
@@ -256,7 +277,7 @@ def _device_image(image) -> torch.Tensor:
 def segment_tiled(image, model, processor, tile: int = 1024, overlap: int = 256, batch_size: int = 4,
                   threshold: float = 0.5, mask_threshold: float = 0.5, overlap_mask_area_threshold: float = 0.8,
                   merge_threshold=(1, 2), return_instance_stats: bool = False, clean=None,
-                  return_aim_points: bool = False) -> dict:
+                  return_aim_points: bool = False, split=None) -> dict:
     """Instance segmentation of an image of any size at native resolution: overlapping tiles (`tile_windows`), `batch_size`
     of them at a time through `processor(images=...)`, `model(pixel_values=...)` under no_grad and
     `processor.post_process_instance_segmentation(target_sizes=tile size)`, then `merge_tile_results`.  The image (PIL
@@ -265,7 +286,8 @@ def segment_tiled(image, model, processor, tile: int = 1024, overlap: int = 256,
     anything that takes a list of device uint8 (h, w, 3) tensors and post-processes into id maps on the device); it is
     called with `images=` alone, so its own size settings decide how a tile is fed.  `clean=CleanOptions(...)` repairs
     the merged map (`merge_tile_results`); the tiles themselves are merged as predicted; `return_aim_points=True` adds the
-    merged map's aim points and clearances there.  Returns `merge_tile_results`'s dictionary."""
+    merged map's aim points and clearances there; `split=SplitOptions(...)` parts touching plants of the merged map
+    there.  Returns `merge_tile_results`'s dictionary."""
     batch_size = int(batch_size)
     if batch_size < 1:
         raise ValueError(f"segment_tiled: batch_size must be at least 1, got {batch_size}")
@@ -282,7 +304,7 @@ def segment_tiled(image, model, processor, tile: int = 1024, overlap: int = 256,
                 outputs, threshold=threshold, mask_threshold=mask_threshold,
                 overlap_mask_area_threshold=overlap_mask_area_threshold, target_sizes=[(grid.th, grid.tw)] * len(batch))
     return merge_tile_results(results, grid, merge_threshold=merge_threshold, return_instance_stats=return_instance_stats,
-                              clean=clean, return_aim_points=return_aim_points)
+                              clean=clean, return_aim_points=return_aim_points, split=split)
 
 
 # ---------------------------------------------------------------------------------------------- the semantic route
