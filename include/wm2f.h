@@ -438,6 +438,38 @@ int wm2f_token_linear_split_fwd(const void* x, const void* w_split, const void* 
                                 const void* ln_beta, const void* pos, void* out, void* out_plus_pos, int64_t M, int K, int N,
                                 int relu, int64_t pos_rows, float eps, int out_group, void* stream);
 
+/* wm2f_token_ffn_split_fwd: the feed-forward pair of a pixel-decoder encoder layer (HF:1080-1088) in one kernel, at the
+ *                        accuracy and with the arithmetic of wm2f_token_linear_split_fwd:
+ *                        out (M, N) = LayerNorm(relu(x (M, K) . W1 (F, K)^T + b1[F]) . W2 (N, F)^T + b2[N] + residual (M, N))
+ *                        with ln_gamma / ln_beta / eps, and, with pos (pos_rows, N) and out_plus_pos, also
+ *                        out_plus_pos = out + pos[row % pos_rows] as one fp32 add.  The (M, F) intermediate is never written.
+ *                        out and out_plus_pos are, bit for bit, what wm2f_token_linear_split_fwd (relu = 1) followed by
+ *                        wm2f_token_linear_split_fwd (residual, LayerNorm, pos) store.
+ *                        w1_split = wm2f_token_linear_split_weight_rows(W1, F, K, WM2F_ROWS_FFN);
+ *                        w2_split = wm2f_token_linear_split_weight(W2, N, F), the plain split.
+ *                        K = N = 256; F = 256, 512, 768 or 1024; residual, ln_gamma and ln_beta are required; pos and
+ *                        out_plus_pos are optional and come together, with any pos_rows >= 1; M * 256 * 4 < 2 GiB.  Anything
+ *                        else returns WM2F_EINVAL with nothing launched and the outputs untouched.  Deterministic, no atomics;
+ *                        a token's output does not depend on M, on the other tokens or on how rows are cut into calls.
+ *                        Non-finite inputs: a token of x that holds an inf or a NaN makes that token's rows of both outputs
+ *                        non-finite and touches no other token.  (Here the two launches differ: their ReLU is a
+ *                        v_max_f32, which answers 0 for a NaN; this kernel puts the NaN back behind the max.)
+ * wm2f_token_linear_split_weight_rows: wm2f_token_linear_split_weight with the rows of W (N, K) in another order.  row_order =
+ *                        WM2F_ROWS_NATURAL: the same bytes.  WM2F_ROWS_FFN (N % 32 == 0): row position n of the split holds row
+ *                        wm2f_token_ffn_row(n) of W -- inside every block of 32 rows, position 16 h + 4 g + e (h < 2, g < 4,
+ *                        e < 4) holds row 8 g + 4 h + e, so that the fp32 C tiles of two neighbouring row tiles are, register
+ *                        for register, the B fragment of the next product's 32-deep k-step in natural k order.
+ * wm2f_token_ffn_row:    that map on the host (-1 for n < 0). */
+#define WM2F_ROWS_NATURAL 0
+#define WM2F_ROWS_FFN 1
+int wm2f_token_linear_split_weight_rows(const void* w, void* w_split, int N, int K, int row_order, void* stream);
+int wm2f_token_ffn_row(int n);
+int wm2f_token_ffn_split_fwd(const void* x, const void* w1_split, const void* b1, const void* w2_split, const void* b2,
+                             const void* residual, const void* ln_gamma, const void* ln_beta, const void* pos, void* out,
+                             void* out_plus_pos, int64_t M, int K, int F, int N, int64_t pos_rows, float eps, void* stream);
+/* (wm2f_token_ffn_split_fwd_p, with a trailing `pieces`, is declared with the other *_p entry points below: at every
+ * level it gives the bits of the two wm2f_token_linear_split_fwd_p launches at that level.) */
+
 /* wm2f_conv1x1_split_fwd: 1x1 convolution without padding, NCHW fp32, at fp32 accuracy on the bf16 matrix cores (the split
  *                        arithmetic of wm2f_token_linear_split_fwd):  out (B, N, Ho, Wo) = epilogue(W (N, K) .
  *                        x (B, K, Hi, Wi) sampled at (stride ho, stride wo)), Ho = (Hi - 1) / stride + 1, likewise Wo.  w_split =
@@ -533,6 +565,10 @@ int wm2f_token_linear_split_fwd_p(const void* x, const void* w_split, const void
                                   const void* ln_gamma, const void* ln_beta, const void* pos, void* out, void* out_plus_pos,
                                   int64_t M, int K, int N, int relu, int64_t pos_rows, float eps, int out_group, int pieces,
                                   void* stream);
+int wm2f_token_ffn_split_fwd_p(const void* x, const void* w1_split, const void* b1, const void* w2_split, const void* b2,
+                               const void* residual, const void* ln_gamma, const void* ln_beta, const void* pos, void* out,
+                               void* out_plus_pos, int64_t M, int K, int F, int N, int64_t pos_rows, float eps, int pieces,
+                               void* stream);
 int wm2f_conv1x1_split_fwd_p(const void* x, const void* w_split, const void* bias, const void* residual, void* out, int B, int K,
                              int N, int Hi, int Wi, int stride, int relu, int config, int pieces, void* stream);
 int wm2f_conv1x1_split_gn_fwd_p(const void* x, const void* w_split, const void* bias, void* out, void* stats_out, int G_out,

@@ -25,6 +25,8 @@
  *                     epilogue loads (residual and pos read as zero), 4 no MFMAs; any other value is refused
  *       WM2F_TGS_OPT  0: the LayerNorm epilogue with its residual / pos loads one batch at a time, as before section 13.2
  *                     (valid outputs, the same bits as the shipped kernel); 1 or unset: the shipped kernel
+ *   - wm2f_token_ffn_split_fwd reads on every launch   (tools/kbench.py --prof --only ffn)
+ *       WM2F_FFN_ABL  timing ablations whose OUTPUTS ARE NOT VALID: 1 no epilogue stores, 4 no MFMAs; any other value is refused
  *   - the stamp buffer below: a __device__ global, i.e. the global mutable state the production library forbids.
  */
 #ifndef WM2F_PROF_H

@@ -233,6 +233,36 @@ def main():
                 ts = sorted(rounds[v])
                 res[f"tgs_{name}_{v}"] = dict(M=M_, K=K, N=N, med_us=ts[len(ts) // 2], min_us=ts[0], spread_us=ts[-1] - ts[0],
                                               rounds_us=[round(t, 2) for t in rounds[v]])
+    if "ffn" in only:  # the encoder's feed-forward pair at M = B * S tokens: the fused kernel against the
+        # two launches it replaces, interleaved rounds in one process.  With --prof also the fused kernel's timing
+        # ablations (WM2F_FFN_ABL, read by libwm2f_prof.so on every launch; OUTPUTS NOT VALID).
+        Mtok, F_ = B * S, 1024
+        x = torch.randn(Mtok, 256, device=dev)
+        w1, w2 = torch.randn(F_, 256, device=dev) * 0.05, torch.randn(256, F_, device=dev) * 0.03
+        b1, b2 = torch.randn(F_, device=dev), torch.randn(256, device=dev)
+        ln = (torch.randn(256, device=dev), torch.randn(256, device=dev), 1e-5)
+        pe = torch.randn(S, 256, device=dev)
+        w1f, w1p, w2s = ops.split_weight_rows(w1, ops.ROWS_FFN), ops.split_weight(w1), ops.split_weight(w2)
+        fused = lambda: ops.token_ffn(x, w1, b1, w2, b2, x, ln, pos=pe, w1_split=w1f, w2_split=w2s)  # noqa: E731
+        two = lambda: ops.token_linear(ops.token_linear(x, w1, b1, relu=True, w_split=w1p), w2, b2, residual=x, ln=ln,  # noqa: E731
+                                       pos=pe, w_split=w2s)
+        a_, b_ = fused(), two()
+        assert torch.equal(a_[0], b_[0]) and torch.equal(a_[1], b_[1])
+        del a_, b_
+        todo = [("two_launches", two, {}), ("fused", fused, {})]
+        if a.prof:
+            todo += [("fused_no_epilogue_stores_INVALID", fused, {"WM2F_FFN_ABL": "1"}), ("fused_no_mfma_INVALID", fused, {"WM2F_FFN_ABL": "4"})]
+        rounds = {v: [] for v, _, _ in todo}
+        for _ in range(5):
+            for v, fn, env in todo:
+                os.environ.pop("WM2F_FFN_ABL", None)
+                os.environ.update(env)
+                rounds[v].append(timeit(fn, a.iters)["med_us"])
+        os.environ.pop("WM2F_FFN_ABL", None)
+        for v, _, _ in todo:
+            ts = sorted(rounds[v])
+            res[f"ffn_{v}"] = dict(M=Mtok, F=F_, med_us=ts[len(ts) // 2], min_us=ts[0], spread_us=ts[-1] - ts[0],
+                                   rounds_us=[round(t, 2) for t in rounds[v]])
     if "k3m" in only:  # K3 with the fused attention-mask epilogue at the three level resolutions (the inference route)
         emb = torch.randn(B, Q, 256, device=dev)
         for hw in shapes:

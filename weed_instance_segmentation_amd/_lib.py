@@ -110,6 +110,9 @@ SIGNATURES = {
     "wm2f_token_linear_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _I, _I, _I, c_int64, c_float, _I, _P]),
     "wm2f_token_linear_split_weight": (c_int, [_P, _P, _I, _I, _P]),
     "wm2f_token_linear_split_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _I, _I, _I, c_int64, c_float, _I, _P]),
+    "wm2f_token_linear_split_weight_rows": (c_int, [_P, _P, _I, _I, _I, _P]),
+    "wm2f_token_ffn_row": (c_int, [_I]),
+    "wm2f_token_ffn_split_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _I, _I, _I, c_int64, c_float, _P]),
     "wm2f_conv1x1_split_config": (c_int, [_I, _I, _I, _I]),
     "wm2f_conv1x1_split_fwd": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_conv3x3_split_config": (c_int, [_I, _I, _I, _I]),
@@ -121,6 +124,7 @@ SIGNATURES = {
     "wm2f_stem7x7_pool_fwd":(c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     # the same entry points with a trailing `pieces` before the stream
     "wm2f_token_linear_split_fwd_p": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _I, _I, _I, c_int64, c_float, _I, _I, _P]),
+    "wm2f_token_ffn_split_fwd_p": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _I, _I, _I, c_int64, c_float, _I, _P]),
     "wm2f_conv1x1_split_fwd_p": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_conv1x1_split_gn_fwd_p": (c_int, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, c_float, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_conv3x3_split_fwd_p": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

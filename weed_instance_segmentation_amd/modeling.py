@@ -212,14 +212,21 @@ class PixelDecoderEncoderLayer(nn.Module):
             B_, S_, C_ = hidden.shape
             ln1, ln2 = self.self_attn_layer_norm, self.final_layer_norm
             op = self.self_attn.output_proj
+            fused = ops.TOKEN_FFN_FUSED and ops.token_ffn_applies(hidden, self.fc1.weight, self.fc2.weight)
+            # (the bound on the fc1 output belongs to the two launches: the fused kernel has no intermediate)
             if (ops.token_linear_applies(hidden, op.weight) and ops.token_linear_applies(hidden, self.fc1.weight)
-                    and B_ * S_ * self.fc1.out_features * 4 < (1 << 31)):
+                    and (fused or B_ * S_ * self.fc1.out_features * 4 < (1 << 31))):
                 # all four Linears on the split-bf16 token GEMM (fp32 accuracy): output_proj with the residual +
                 # LayerNorm in its epilogue, fc1 with bias + ReLU, fc2 with the residual + LayerNorm and the next layer's
-                # hidden + pos
+                # hidden + pos -- the last two as one kernel (§13.3) when it applies
                 a = self.self_attn(hidden, pos, ref, level_hw, hp, project=False)
                 hidden = ops.token_linear(a, op.weight, op.bias, residual=hidden, ln=(ln1.weight, ln1.bias, ln1.eps),
                                           w_split=ops.split_weight_cached(self, "output_proj", op.weight))
+                if fused:
+                    return ops.token_ffn(hidden, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, hidden,
+                                         (ln2.weight, ln2.bias, ln2.eps), pos=pos,
+                                         w1_split=ops.split_weight_rows_cached(self, "fc1_ffn", self.fc1.weight),
+                                         w2_split=ops.split_weight_cached(self, "fc2", self.fc2.weight))
                 f = ops.token_linear(hidden, self.fc1.weight, self.fc1.bias, relu=True,
                                      w_split=ops.split_weight_cached(self, "fc1", self.fc1.weight))
                 return ops.token_linear(f, self.fc2.weight, self.fc2.bias, residual=hidden, ln=(ln2.weight, ln2.bias, ln2.eps),

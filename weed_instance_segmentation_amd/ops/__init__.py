@@ -27,6 +27,11 @@ CONV3X3_SPLIT = True
 # layer_1's raw output in its operand load.  False keeps the separate statistics and apply passes (the reference of the tests).
 CONV_GN_FUSED = True
 
+# The inference forward of a pixel-decoder encoder layer runs fc1 + ReLU and fc2 + LayerNorm (+ pos) as ONE kernel while this
+# is True and token_ffn_applies: the (tokens, 1024) intermediate never reaches memory.  False keeps the two
+# token_linear launches (the reference of the tests: the fused kernel gives their bits).
+TOKEN_FFN_FUSED = True
+
 # The precision of the split-bf16 GEMMs and convolutions (token_linear, conv1x1, conv1x1_gn, conv3x3, conv3x3_stats,
 # stem_conv_pool on their split kernels), read at every call: "highest" (or None) = three bf16 pieces per operand
 # and six products, fp32 accuracy; "high" = two pieces, three products (error floor 2^-14 of sum |x w|); "medium" = one
@@ -45,9 +50,10 @@ from .copy_paste import copy_paste
 from .fused import (add_broadcast, bias_act_, bias_relu_maxpool, group_norm_act_, group_norm_act_from_stats_, group_norm_tokens_,
                     group_norm_tokens_from_stats_, resize_bilinear, resize_pyramid, tokens_to_nchw)
 from .gemm import (conv1x1, conv1x1_applies, conv1x1_gn, conv3x3, conv3x3_applies, conv3x3_stats, conv_group_stats_applies,
-                   linear_tokens, split_weight, split_weight_3x3,
-                   split_weight_cached, split_weight_stem, stem_conv_pool, stem_conv_pool_applies, stem_weight_columns,
-                   stem_weight_matrix, token_linear, token_linear_applies, token_wgrad, token_wgrad_applies)
+                   ROWS_FFN, ROWS_NATURAL, ffn_row_order, linear_tokens, split_weight, split_weight_3x3,
+                   split_weight_cached, split_weight_rows, split_weight_rows_cached, split_weight_stem, stem_conv_pool,
+                   stem_conv_pool_applies, stem_weight_columns, stem_weight_matrix, token_ffn, token_ffn_applies,
+                   token_linear, token_linear_applies, token_wgrad, token_wgrad_applies)
 from .k1 import (k1_bwd_deterministic, k1_lane_order, k1_lane_rows, k1_lanes_applies, k1_rows_applies, ms_deform_attn,
                  ms_deform_attn_bwd, ms_deform_attn_fused, ms_deform_attn_fused_lanes, ms_deform_attn_fused_packed,
                  ms_deform_attn_rows, ms_deform_attn_variant)

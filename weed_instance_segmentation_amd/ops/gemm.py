@@ -44,24 +44,57 @@ def split_weight(weight: torch.Tensor) -> torch.Tensor:
     return ws
 
 
+ROWS_NATURAL, ROWS_FFN = 0, 1  # WM2F_ROWS_* of include/wm2f.h
+
+
+def ffn_row_order(n_rows: int) -> torch.Tensor:
+    """The row map of ROWS_FFN for a weight of n_rows rows (a multiple of 32), from the library: entry n is the weight row
+    that split_weight_rows(weight, ROWS_FFN) puts at row position n (include/wm2f.h, wm2f_token_ffn_row)."""
+    lib = load()
+    return torch.tensor([lib.wm2f_token_ffn_row(n) for n in range(n_rows)], dtype=torch.long)
+
+
+def split_weight_rows(weight: torch.Tensor, row_order: int = ROWS_FFN) -> torch.Tensor:
+    """split_weight with the rows of the weight (N, K) in another order, done by the kernel on the original weight
+    (wm2f_token_linear_split_weight_rows): ROWS_NATURAL gives split_weight's bytes, ROWS_FFN (N % 32 == 0) the order
+    token_ffn reads fc1's weight in, the bytes of split_weight(weight[ffn_row_order(N)])."""
+    weight = _req(weight, "weight")
+    N, K = weight.shape
+    ws = torch.empty(N * K * 6, device=weight.device, dtype=torch.uint8)
+    _launch("wm2f_token_linear_split_weight_rows", weight, _p(weight), _p(ws), N, K, int(row_order))
+    return ws
+
+
+def _split_cached(owner, name: str, weight: torch.Tensor, ident: torch.Tensor, make) -> torch.Tensor:
+    """make(weight), kept in owner.__dict__ under `name` and redone when `ident` (held by weak reference) is another
+    tensor or has another version, or the weight another storage, device or shape."""
+    c = owner.__dict__.setdefault("_wm2f_split", {})
+    key = (ident._version, weight.data_ptr(), weight.device, tuple(weight.shape))
+    hit = c.get(name)
+    if hit is None or hit[0]() is not ident or hit[1] != key:
+        hit = (weakref.ref(ident), key, make(weight))
+        c[name] = hit
+    return hit[2]
+
+
 def split_weight_cached(owner, name: str, weight: torch.Tensor, base: torch.Tensor | None = None,
                         tap_major: bool = False) -> torch.Tensor:
     """split_weight(weight), kept in owner.__dict__ under `name` and redone when the weight changes: another tensor (held by
     weak reference: `base` when weight is a fresh view of it each call), another version, storage or device.
     tap_major=True: weight is a convolution kernel, split in the K order its kernel reads: (N, Cin, 3, 3) as conv3x3 does
     (split_weight_3x3), (64, Cin, 7, 7) as stem_conv_pool does (split_weight_stem)."""
-    ident = weight if base is None else base
-    c = owner.__dict__.setdefault("_wm2f_split", {})
-    key = (ident._version, weight.data_ptr(), weight.device, tuple(weight.shape))
-    hit = c.get(name)
-    if hit is None or hit[0]() is not ident or hit[1] != key:
-        if not tap_major:
-            ws = split_weight(weight)
-        else:
-            ws = split_weight_stem(weight) if tuple(weight.shape[2:]) == (7, 7) else split_weight_3x3(weight)
-        hit = (weakref.ref(ident), key, ws)
-        c[name] = hit
-    return hit[2]
+    if not tap_major:
+        make = split_weight
+    else:
+        make = split_weight_stem if tuple(weight.shape[2:]) == (7, 7) else split_weight_3x3
+    return _split_cached(owner, name, weight, weight if base is None else base, make)
+
+
+def split_weight_rows_cached(owner, name: str, weight: torch.Tensor, row_order: int = ROWS_FFN) -> torch.Tensor:
+    """split_weight_rows(weight, row_order), cached as split_weight_cached caches split_weight: keyed on the parameter
+    itself (version, storage, device) under `name`, which must be a name of its own (the plain split of the same weight
+    lives under another)."""
+    return _split_cached(owner, name, weight, weight, lambda w: split_weight_rows(w, row_order))
 
 
 def split_weight_3x3(weight: torch.Tensor) -> torch.Tensor:
@@ -118,6 +151,62 @@ def token_linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, relu
     else:
         _launch("wm2f_token_linear_fwd", x, _p(x), _p(weight), _p(bias), _p(residual), _p(gamma), _p(beta), _p(pos), _p(out),
                 _p(out_pos), M, K, N, 1 if relu else 0, pos_rows, eps, int(out_group), tag=tag)
+    return (out, out_pos) if pos is not None else out
+
+
+def token_ffn_applies(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor) -> bool:
+    """Shapes token_ffn is built for: fp32 on a GPU, w1 (F, 256) and w2 (256, F) with F in {256, 512, 768, 1024},
+    x (..., 256) below 2 GiB."""
+    if w1.dim() != 2 or w2.dim() != 2:
+        return False
+    F_, K = w1.shape
+    N = w2.shape[0]
+    M = x.numel() // max(K, 1)
+    return (x.is_cuda and x.dtype == torch.float32 and w1.dtype == torch.float32 and w2.dtype == torch.float32
+            and K == 256 and N == 256 and w2.shape[1] == F_ and F_ in (256, 512, 768, 1024) and x.shape[-1] == K
+            and M * 256 * 4 < (1 << 31))
+
+
+def token_ffn(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, residual: torch.Tensor,
+              ln: tuple, pos: torch.Tensor | None = None, w1_split: torch.Tensor | None = None,
+              w2_split: torch.Tensor | None = None):
+    """The feed-forward pair of an encoder layer in one kernel (inference, no autograd; wm2f_token_ffn_split_fwd, DESIGN
+    §13.3): LayerNorm(relu(x @ w1^T + b1) @ w2^T + b2 + residual) with ln = (gamma, beta, eps), and with `pos`
+    (rows_per_image, 256) additionally out + pos broadcast over the batch.  Returns out, or (out, out + pos) -- the bits of
+        token_linear(token_linear(x, w1, b1, relu=True), w2, b2, residual=residual, ln=ln, pos=pos)
+    without the (M, F) intermediate, at every ops.SPLIT_PRECISION.  w1_split = split_weight_rows(w1, ROWS_FFN) and
+    w2_split = split_weight(w2) if the caller keeps them.  The shapes of token_ffn_applies."""
+    x, w1, b1, w2, b2 = _req(x, "x"), _req(w1, "w1"), _req(b1, "b1"), _req(w2, "w2"), _req(b2, "b2")
+    F_, K = w1.shape
+    N = w2.shape[0]
+    if x.shape[-1] != K or b1.shape != (F_,) or w2.shape != (N, F_) or b2.shape != (N,):
+        raise ValueError(f"token_ffn: x {tuple(x.shape)} w1 {tuple(w1.shape)} b1 {tuple(b1.shape)} w2 {tuple(w2.shape)} "
+                         f"b2 {tuple(b2.shape)}")
+    if residual is None or ln is None:
+        raise ValueError("token_ffn: the residual and the LayerNorm are part of the kernel")
+    M = x.numel() // K
+    residual = _req(residual, "residual")
+    if residual.numel() != M * N:
+        raise ValueError("token_ffn: residual shape")
+    gamma, beta, eps = _req(ln[0], "gamma"), _req(ln[1], "beta"), float(ln[2])
+    out = torch.empty(*x.shape[:-1], N, device=x.device, dtype=torch.float32)
+    out_pos, pos_rows = None, 0
+    if pos is not None:
+        pos = _req(pos, "pos")
+        pos_rows = pos.numel() // N
+        if M % pos_rows:
+            raise ValueError("token_ffn: pos rows do not divide the token count")
+        out_pos = torch.empty_like(out)
+    for ws, what in ((w1_split, "w1_split is not split_weight_rows(w1, ROWS_FFN)"), (w2_split, "w2_split is not split_weight(w2)")):
+        if ws is not None and (ws.dtype != torch.uint8 or ws.numel() != F_ * K * 6 or ws.device != x.device):
+            raise ValueError("token_ffn: " + what)
+    if w1_split is None:
+        w1_split = split_weight_rows(w1, ROWS_FFN)
+    if w2_split is None:
+        w2_split = split_weight(w2)
+    pieces, lvl = _split_pieces()
+    _launch("wm2f_token_ffn_split_fwd_p", x, _p(x), _p(w1_split), _p(b1), _p(w2_split), _p(b2), _p(residual), _p(gamma), _p(beta),
+            _p(pos), _p(out), _p(out_pos), M, K, F_, N, pos_rows, eps, pieces, tag=f"token_ffn_K{K}_F{F_}_split" + lvl)
     return (out, out_pos) if pos is not None else out
 
 
