@@ -884,6 +884,69 @@ int wm2f_labelmap_aim_points(const void* map, int dtype, const int32_t* d2, cons
                              const int64_t* stats, int32_t* points, void* workspace, int B, int H, int W, int N,
                              void* stream);
 
+/* ---- nearest-instance maps and per-cell pixel counts of id maps on device ------------------
+ * The exterior counterpart of wm2f_labelmap_distance: for every pixel the nearest instance and how far away it is, up
+ * to a cap -- growing ids by a margin (skimage's expand_labels), a protection distance round crop plants, bare pixels
+ * assigned to the plant that owns them -- and the pixel counts of the cells of a sprayer's grid.
+ * wm2f_labelmap_nearest:   map (B, H, W) is WM2F_F32, WM2F_I32 or WM2F_U8.  The instances are the ids 0 .. N-1, by the
+ *                         rule of wm2f_labelmap_instance_stats for floats; every other value is free (the convention
+ *                         of wm2f_labelmap_clean).  source (B, N) uint8 or NULL: instance id of image b is a source when
+ *                         source is NULL or source[b, id] != 0.
+ *                         nearest, d2 (B, H, W) int32, overwritten, every element.  For a pixel p take the source
+ *                         pixels q with |p - q|^2 <= max_d2, distances between pixel centres; the image border is not
+ *                         a source.  None: nearest = -1, d2 = INT32_MAX.  Otherwise d2 is the smallest such distance
+ *                         and nearest the smallest id among the sources that attain it; a source pixel so gets its
+ *                         own id and d2 = 0.
+ *                         flags: WM2F_NEAREST_BLOCKED -- a pixel of an instance that is not a source is written as
+ *                         its own id with d2 = 0 (growth: other plants keep their pixels); without it such a pixel is
+ *                         a query like a free pixel (protection: a weed pixel's distance to the crop).  Growth is
+ *                         Euclidean, as in skimage: it may jump across a blocking plant; geodesic growth is out of
+ *                         scope.  WM2F_NEAREST_WALK_ALL -- every pixel walks its row even where the prefix count
+ *                         (below) says nothing is in range; same results, for measuring what the count saves.
+ *                         0 <= max_d2 <= 1024^2 (the margin r = floor(sqrt(max_d2)) <= 1024), H, W <= 16384, B <= 32,
+ *                         N <= 4096, else WM2F_EUNSUPPORTED; sizes below 1, a negative max_d2 and unknown flags are
+ *                         WM2F_EINVAL (both are decided before a pointer is looked at).  The uncapped (Voronoi) map is
+ *                         out of scope: its walk has no bound.
+ *                         workspace: wm2f_labelmap_nearest_workspace(B, H, W) bytes, 16-byte aligned: six bytes per
+ *                         pixel (g uint16 rounded up to 16 bytes, then the column's id int32).  It needs no clearing.
+ *                         Two launches whatever B and N.  Exact in integers and separable: with g(x', y) the vertical
+ *                         distance to the nearest source pixel of column x', the answer is the minimum over x' of
+ *                         ((x - x')^2 + g(x', y)^2, id).
+ *                         columns -- a lane per column over chunks of at least 32 rows; a chunk starts its march r
+ *                         rows above itself and its march back r rows below, so it needs no summary of other chunks.
+ *                         It writes g (r + 1: none within r) and the id of that source pixel, the smaller id where
+ *                         the one above and the one below are equally far (within a column the smaller |dy| wins and
+ *                         an equal |dy| occurs at most twice).
+ *                         rows -- a workgroup stages whole rows of g and id in LDS (rows shorter than 1024 share
+ *                         one; a row longer than 4096 gets 1024 threads), builds per row the prefix count of pixels
+ *                         with g <= r, and a pixel whose window [x - r, x + r] counts none writes "none" after one
+ *                         subtraction.  Every other pixel walks s = 0, 1, ... <= r while s^2 <= its best (not <: a
+ *                         candidate at equal distance with a smaller id still has to be seen), four steps' reads in
+ *                         flight.  All integer, bit-identical from run to run.
+ * wm2f_labelmap_cell_counts: map as above.  Pixel (x, y) lies in cell ((y + off_y) / cell_h, (x + off_x) / cell_w),
+ *                         0 <= off < cell; GH = ceil((H + off_y) / cell_h), GW = ceil((W + off_x) / cell_w).
+ *                         group (B, N) uint8: group[b, id] in 0 .. G-1 names the column an instance's pixels are
+ *                         counted in; 255 (any value >= G): not counted.  Free pixels are not counted.
+ *                         veto_d2 (B, H, W) int32 or NULL (wm2f_labelmap_nearest's d2 towards the protected
+ *                         instances): counts[b, cy, cx, g] gets the pixel when veto_d2 is NULL or veto_d2[p] > veto_max,
+ *                         counts[b, cy, cx, G + g] otherwise -- what the protection zone took away.
+ *                         counts (B, GH, GW, 2G) int32, written in full by the call (no memset contract).  1 <= G <= 8.
+ *                         H, W, cell_h, cell_w <= 16384, B <= 32, N <= 4096, else WM2F_EUNSUPPORTED; sizes below 1, an
+ *                         offset outside [0, cell), G outside [1, 8] and a negative veto_max are WM2F_EINVAL (decided
+ *                         before a pointer is looked at).
+ *                         One launch, one read of the map: a workgroup owns a tile of cells, counts its pixels into
+ *                         integer LDS accumulators and stores the tile.  Bit-identical from run to run. */
+#define WM2F_NEAREST_BLOCKED 1
+#define WM2F_NEAREST_WALK_ALL 2
+#define WM2F_NEAREST_MAX_D2 (1024 * 1024)
+#define WM2F_CELL_MAX_GROUPS 8
+int64_t wm2f_labelmap_nearest_workspace(int B, int H, int W);
+int wm2f_labelmap_nearest(const void* map, int dtype, const uint8_t* source, int32_t* nearest, int32_t* d2,
+                          void* workspace, int B, int H, int W, int N, int max_d2, int flags, void* stream);
+int wm2f_labelmap_cell_counts(const void* map, int dtype, const uint8_t* group, const int32_t* veto_d2, int veto_max,
+                              int32_t* counts, int B, int H, int W, int N, int G, int cell_h, int cell_w, int off_y,
+                              int off_x, void* stream);
+
 /* ---- panoptic quality and semantic mIoU on device ---------------------------------------
  * What scores the maps of post_process_panoptic_segmentation and post_process_semantic_segmentation: the segment
  * matching of panopticapi's pq_compute (which torchmetrics' PanopticQuality follows) and the confusion matrix mIoU is

@@ -153,6 +153,9 @@ SIGNATURES = {
     "wm2f_labelmap_distance": (c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _P]),
     "wm2f_labelmap_aim_points_workspace": (c_int64, [_I, _I]),
     "wm2f_labelmap_aim_points": (c_int, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "wm2f_labelmap_nearest_workspace": (c_int64, [_I, _I, _I]),
+    "wm2f_labelmap_nearest": (c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "wm2f_labelmap_cell_counts": (c_int, [_P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_panoptic_match": (c_int, [_P] * 8 + [_I, _I, _I, _I, _P]),
     "wm2f_semantic_confusion": (c_int, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, c_int64, _I, _I, _I, _I, _P]),
     "wm2f_labelmap_overlay": (c_int, [_P, _P, _I, _P, _P, _P, _P, ctypes.c_uint32, _I, _I, _P, _I, _I, _I, _I, _P]),

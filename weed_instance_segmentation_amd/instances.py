@@ -36,6 +36,14 @@ in seven launches of csrc/distance.hip whatever the number of instances.
 distance whose basins are merged again wherever the neck between them is wide, in a fixed chain of launches of
 csrc/split.hip.  The post-processor, the tiled route, `test_with_metrics` and the PNG loaders take the same
 `SplitOptions` as `split=`.
+
+    from weed_instance_segmentation_amd import grow_label_maps, nearest_instance_maps
+    grown = grow_label_maps(prediction["segmentation"], n, margin=8)          # skimage's expand_labels
+    nearest, d2 = nearest_instance_maps(prediction["segmentation"], n, 12, sources=crop_ids)
+
+`nearest_instance_maps` and `grow_label_maps` look outward from the plants: every pixel's nearest
+source instance within a cap and the exact squared distance to it, the smallest id among equally near ones, in two
+launches of csrc/nearest.hip whatever the number of instances.  `treatment.py` builds the sprayer's cell grid on them.
 """
 from __future__ import annotations
 
@@ -170,6 +178,105 @@ def distance_maps(maps, border: str = "outside", squared: bool = True) -> torch.
     d2 = ops.labelmap_distance(stack.unsqueeze(0) if seg.dim() == 2 else stack, outside)
     d2 = d2[0] if seg.dim() == 2 else d2
     return d2 if squared else d2.to(torch.float64).sqrt().to(torch.float32)
+
+
+def _exact(v) -> Fraction:
+    """A number as the exact fraction it is (numpy scalars through their Python value)."""
+    return v if isinstance(v, Fraction) else Fraction(v.item() if isinstance(v, np.generic) else v)
+
+
+def squared_cap(distance, who: str) -> int:
+    """floor(distance^2) in exact arithmetic, for a distance in [0, 1024] pixels: the cap of `ops.labelmap_nearest`."""
+    if isinstance(distance, bool) or not isinstance(distance, (int, float, np.integer, np.floating, Fraction)) or not math.isfinite(distance):
+        raise ValueError(f"{who}: the distance must be a finite number, got {distance!r}")
+    if not 0 <= distance <= 1024:
+        raise ValueError(f"{who}: the distance must be in [0, 1024] pixels, got {distance!r}")
+    return math.floor(_exact(distance) ** 2)
+
+
+def source_flags(sources, n: int, who: str):
+    """`sources` -- None (every instance), an iterable of ids of [0, n) or a bool array of length n -- as a host bool array
+    (n,), or None."""
+    if sources is None:
+        return None
+    a = sources.cpu().numpy() if isinstance(sources, torch.Tensor) else np.asarray(list(sources) if not isinstance(sources, np.ndarray) else sources)
+    if a.dtype == np.bool_:
+        if a.shape != (n,):
+            raise ValueError(f"{who}: a bool array of sources must have length {n}, got shape {a.shape}")
+        return a.copy()
+    if a.size and a.dtype.kind not in "iu":
+        raise TypeError(f"{who}: sources must be ids or a bool array, got {a.dtype}")
+    ids = a.astype(np.int64).reshape(-1)
+    if ((ids < 0) | (ids >= n)).any():
+        raise ValueError(f"{who}: source ids must lie in [0, {n}), got {ids.tolist()}")
+    flags = np.zeros(n, np.bool_)
+    flags[ids] = True
+    return flags
+
+
+def nearest_rows(maps: torch.Tensor, n: int, max_d2: int, flags, blocked: bool):
+    """(B, H, W) device id maps and host source flags (n,) or None -> (nearest, d2) of `ops.labelmap_nearest`."""
+    B = maps.shape[0]
+    N = max(1, int(n))
+    source = None
+    if flags is not None or n == 0:  # no instance at all: one id that is no source
+        row = np.zeros(N, np.uint8)
+        if flags is not None:
+            row[:n] = flags
+        source = torch.from_numpy(row).to(maps.device).expand(B, N).contiguous()
+    return ops.labelmap_nearest(maps, N, max_d2, source, blocked)
+
+
+def nearest_instance_maps(maps, n: int, max_distance, sources=None, blocked: bool = False, squared: bool = True):
+    """For every pixel of one (H, W) id map or a (B, H, W) stack -- fp32 with -1 background, int32 or uint8, host or
+    device; the instances are the ids 0 .. n-1, every other value is free -- the nearest source instance within
+    `max_distance` pixels (at most 1024, between pixel centres; the image border is no source) and the distance to it.
+
+    - `sources`: an iterable of ids or a bool array of length n; None: every instance.
+    - `blocked`: a pixel of an instance that is no source keeps its own id at distance 0 (the form growth uses);
+      otherwise it is a query like a free pixel (the form a protection distance uses).
+    Returns device tensors of the input's shape (nearest int32, distance): nearest is -1 where no source is in range;
+    among equally near sources the smallest id wins.  The distance is squared and exact (int32, INT32_MAX for none), or
+    with squared=False float32, the root taken in float64, inf for none.  Two launches of csrc/nearest.hip whatever the
+    number of instances."""
+    seg = _id_maps(maps, "nearest_instance_maps")
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"nearest_instance_maps: n must not be negative, got {n}")
+    max_d2 = squared_cap(max_distance, "nearest_instance_maps")
+    flags = source_flags(sources, n, "nearest_instance_maps")
+    if not torch.cuda.is_available():
+        raise _lib.Wm2fError("nearest_instance_maps runs on a GPU only (no CPU fallback): no device is visible")
+    dev = seg.device if seg.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    stack = seg.to(dev)
+    nearest, d2 = nearest_rows(stack.unsqueeze(0) if seg.dim() == 2 else stack, n, max_d2, flags, bool(blocked))
+    if seg.dim() == 2:
+        nearest, d2 = nearest[0], d2[0]
+    if squared:
+        return nearest, d2
+    dist = d2.to(torch.float64).sqrt().to(torch.float32)
+    return nearest, torch.where(nearest >= 0, dist, torch.full_like(dist, float("inf")))
+
+
+def grow_label_maps(maps, n: int, margin, sources=None) -> torch.Tensor:
+    """Grow the instances of one (H, W) id map or a (B, H, W) stack (maps as for `nearest_instance_maps`) by `margin`
+    pixels: every free pixel within `margin` of a source instance takes the id of the nearest one (the smallest id among
+    equally near ones), so two instances never grow into each other -- skimage's `expand_labels`.  Instance pixels are
+    unchanged, those of instances that are no `sources` included.  Growth is Euclidean: it may reach across a narrow
+    plant that lies between, as in skimage.  max_d2 = floor(margin^2) is computed exactly.  Returns an int32 device
+    tensor of the input's shape with -1 background."""
+    seg = _id_maps(maps, "grow_label_maps")
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"grow_label_maps: n must not be negative, got {n}")
+    max_d2 = squared_cap(margin, "grow_label_maps")
+    flags = source_flags(sources, n, "grow_label_maps")
+    if not torch.cuda.is_available():
+        raise _lib.Wm2fError("grow_label_maps runs on a GPU only (no CPU fallback): no device is visible")
+    dev = seg.device if seg.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    stack = seg.to(dev)
+    nearest, _ = nearest_rows(stack.unsqueeze(0) if seg.dim() == 2 else stack, n, max_d2, flags, True)
+    return nearest[0] if seg.dim() == 2 else nearest
 
 
 def aim_point_rows(maps: torch.Tensor, N: int, border_outside: bool = True, ids: torch.Tensor | None = None,
@@ -316,11 +423,6 @@ def clean_label_maps(maps, n: int, options: CleanOptions | None = None, *, relab
     if seg.dim() == 2:
         out, stats = out[0], stats[0]
     return (out, stats) if return_stats else out
-
-
-def _exact(v) -> Fraction:
-    """A number as the exact fraction it is (numpy scalars through their Python value)."""
-    return v if isinstance(v, Fraction) else Fraction(v.item() if isinstance(v, np.generic) else v)
 
 
 @dataclasses.dataclass(frozen=True)

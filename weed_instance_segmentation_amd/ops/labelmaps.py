@@ -246,6 +246,88 @@ def labelmap_aim_points(maps: torch.Tensor, d2: torch.Tensor, ids: torch.Tensor 
     return points
 
 
+# wm2f_labelmap_nearest's bounds and launch shape (include/wm2f.h), for callers and tests
+NEAREST_MAX_D2 = 1024 * 1024
+NEAREST_MIN_CHUNK_ROWS = 32   # columns pass: rows of a chunk, at least (exactly, for a small map taller than this)
+NEAREST_ROW_PIXELS = 1024     # rows pass: shorter rows share a workgroup
+NEAREST_WIDE_ROW = 4096       # rows pass: a longer row gets 1024 threads
+CELL_MAX_GROUPS = 8
+INT32_MAX = 2 ** 31 - 1
+
+
+def labelmap_nearest(maps: torch.Tensor, N: int, max_d2: int, source: torch.Tensor | None = None, blocked: bool = True,
+                     walk_all: bool = False):
+    """(B, H, W) id maps (fp32 with -1 background, int32 or uint8) whose instances are the ids 0 .. N-1 -> (nearest, d2),
+    both (B, H, W) int32 (wm2f_labelmap_nearest): per pixel the nearest source instance within squared distance `max_d2`
+    (the smallest id among equally near ones) and that squared distance; -1 and INT32_MAX where there is none.  `source`
+    (B, N) uint8 / bool: which instances are sources (None: all).  `blocked`: a pixel of an instance that is no source is
+    written as its own id with d2 = 0; otherwise it is a query like a free pixel.  `walk_all` switches the rows pass's
+    early "none" off (same results; for measurements)."""
+    if not isinstance(maps, torch.Tensor):
+        raise TypeError("labelmap_nearest: expected a tensor")
+    maps = _req(maps, "maps", maps.dtype)
+    dt = _dtype_code(maps, (torch.float32, torch.int32, torch.uint8),
+                     f"labelmap_nearest: maps fp32 / int32 / uint8, got {maps.dtype}")
+    if maps.dim() != 3:
+        raise ValueError(f"labelmap_nearest: maps must be (B, H, W), got {tuple(maps.shape)}")
+    B, H, W = (int(v) for v in maps.shape)
+    N, max_d2 = int(N), int(max_d2)
+    if B == 0 or H == 0 or W == 0 or N < 1 or max_d2 < 0:
+        raise ValueError(f"labelmap_nearest: bad size {tuple(maps.shape)}, N = {N}, max_d2 = {max_d2}")
+    if source is not None:
+        source = _req(source, "source", source.dtype if source.dtype in (torch.bool, torch.uint8) else torch.uint8)
+        if source.shape != (B, N):
+            raise ValueError(f"labelmap_nearest: source must be ({B}, {N}), got {tuple(source.shape)}")
+        source = source.view(torch.uint8)
+    nearest = torch.empty(B, H, W, device=maps.device, dtype=torch.int32)
+    d2 = torch.empty(B, H, W, device=maps.device, dtype=torch.int32)
+    nbytes = int(load().wm2f_labelmap_nearest_workspace(B, H, W))
+    ws = torch.empty(max(nbytes, 1), device=maps.device, dtype=torch.uint8)  # an unsupported size: the launch reports it
+    flags = (1 if blocked else 0) | (2 if walk_all else 0)
+    _launch("wm2f_labelmap_nearest", maps, _p(maps), dt, _p(source), _p(nearest), _p(d2), _p(ws), B, H, W, N, max_d2, flags,
+            tag="labelmap_nearest")
+    return nearest, d2
+
+
+def cell_grid_shape(H: int, W: int, cell, offset=(0, 0)):
+    """(GH, GW) of the grid whose cell (cy, cx) holds the pixels with (y + off_y) // cell_h == cy, (x + off_x) // cell_w == cx."""
+    return -(-(int(H) + int(offset[0])) // int(cell[0])), -(-(int(W) + int(offset[1])) // int(cell[1]))
+
+
+def labelmap_cell_counts(maps: torch.Tensor, group: torch.Tensor, G: int, cell, offset=(0, 0),
+                         veto_d2: torch.Tensor | None = None, veto_max: int = 0) -> torch.Tensor:
+    """(B, H, W) id maps and group (B, N) uint8 -> counts (B, GH, GW, 2G) int32 (wm2f_labelmap_cell_counts): per cell of
+    `cell` = (h, w) pixels, shifted by `offset` = (off_y, off_x) with 0 <= off < cell, the pixels of the instances of
+    every group 0 .. G-1 (group value 255: not counted).  Column g counts the pixels with veto_d2 > veto_max (all of them
+    without `veto_d2`), column G + g the others."""
+    if not isinstance(maps, torch.Tensor):
+        raise TypeError("labelmap_cell_counts: expected a tensor")
+    maps = _req(maps, "maps", maps.dtype)
+    dt = _dtype_code(maps, (torch.float32, torch.int32, torch.uint8),
+                     f"labelmap_cell_counts: maps fp32 / int32 / uint8, got {maps.dtype}")
+    if maps.dim() != 3:
+        raise ValueError(f"labelmap_cell_counts: maps must be (B, H, W), got {tuple(maps.shape)}")
+    B, H, W = (int(v) for v in maps.shape)
+    group = _req(group, "group", torch.uint8)
+    if group.dim() != 2 or group.shape[0] != B or group.shape[1] < 1:
+        raise ValueError(f"labelmap_cell_counts: group must be ({B}, N), got {tuple(group.shape)}")
+    N, G = int(group.shape[1]), int(G)
+    (ch, cw), (oy, ox) = (int(v) for v in cell), (int(v) for v in offset)
+    if B == 0 or H == 0 or W == 0 or ch < 1 or cw < 1 or not (0 <= oy < ch and 0 <= ox < cw) or not 1 <= G <= CELL_MAX_GROUPS:
+        raise ValueError(f"labelmap_cell_counts: bad size {tuple(maps.shape)}, cell {ch} x {cw}, offset ({oy}, {ox}), G = {G}")
+    if veto_d2 is not None:
+        veto_d2 = _req(veto_d2, "veto_d2", torch.int32)
+        if veto_d2.shape != maps.shape:
+            raise ValueError(f"labelmap_cell_counts: veto_d2 must be {tuple(maps.shape)}, got {tuple(veto_d2.shape)}")
+    if int(veto_max) < 0:
+        raise ValueError(f"labelmap_cell_counts: veto_max must not be negative, got {veto_max}")
+    GH, GW = cell_grid_shape(H, W, (ch, cw), (oy, ox))
+    counts = torch.empty(B, GH, GW, 2 * G, device=maps.device, dtype=torch.int32)
+    _launch("wm2f_labelmap_cell_counts", maps, _p(maps), dt, _p(group), _p(veto_d2), int(veto_max), _p(counts), B, H, W, N, G,
+            ch, cw, oy, ox, tag="labelmap_cell_counts")
+    return counts
+
+
 def panoptic_match(hist, pred_label, gt_label, n_pred, n_gt, void_as_background: bool = False):
     """PQ's segment matching of B images (wm2f_panoptic_match): hist (B, P+1, G+1), pred_label (B, P), gt_label (B, G),
     n_pred / n_gt (B) int32.  Returns gt_match (B, G) int32 (matched prediction row, -1 false negative, -2 no such GT),
