@@ -16,38 +16,22 @@
 //                   one does), writes every owned pixel's id when it passes it and -1 over it d rows later if it turns
 //                   out interior -- the same lane, the same address, in program order.
 // Everything is integer and no result depends on an order of accumulation.
-#include <type_traits>
-
-#include "common.h"
+#include "labelmap.h"
 
 namespace wm2f {
 namespace {
 
 constexpr int kBdThreads = 256;
 constexpr int kBdWaves = kBdThreads / 64;
-constexpr int kBdMaxSide = 16384;
-constexpr int kBdMaxBatch = 32;
 constexpr int kBdMinChunkRows = 64;   // vertical pass: a chunk owns at least this many rows (and at least 2d)
-constexpr int kBdTargetWaves = 2048;  // about this many waves in the vertical pass's grid
 constexpr int kBdUnroll = 16;         // rows of one column per register set; two sets in flight
-
-// the id of a raw map value, -1 for none (wm2f_labelmap_instance_stats's rule for floats; a negative int32 is no id)
-template <int DT>
-__device__ __forceinline__ int key_of(uint32_t raw) {
-  if (DT == WM2F_F32) {
-    int v;
-    return f32_bits_to_int(raw, v) ? v : -1;
-  }
-  const int v = (int)raw;  // a uint8 arrives zero-extended
-  return v < 0 ? -1 : v;
-}
 
 // grid ceil(B * H / 4), 256 threads: wave w of block k owns row 4k + w of the (B * H, W) stack.
 template <int DT, int PIX>
 __global__ __launch_bounds__(kBdThreads) void boundary_rows_kernel(const void* __restrict__ map,
                                                                   uint8_t* __restrict__ plane, int64_t rows, int W,
                                                                   int d) {
-  using E = typename std::conditional<DT == WM2F_U8, uint8_t, uint32_t>::type;
+  using E = typename MapElem<DT>::type;
   constexpr int kStep = 64 * PIX;
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * kBdWaves + (threadIdx.x >> 6);
@@ -61,19 +45,7 @@ __global__ __launch_bounds__(kBdThreads) void boundary_rows_kernel(const void* _
 #pragma unroll
     for (int j = 0; j < PIX; ++j) v[j] = 0u;
     if constexpr (PIX == 4) {  // W % 4 == 0 and an aligned map: the four pixels are inside the row together
-      if (x < W) {
-        if constexpr (DT == WM2F_U8) {
-          const uint32_t w4 = *reinterpret_cast<const uint32_t*>(src + x);
-#pragma unroll
-          for (int j = 0; j < PIX; ++j) v[j] = (w4 >> (8 * j)) & 0xffu;
-        } else {
-          const uint4 q = *reinterpret_cast<const uint4*>(src + x);
-          v[0] = q.x;
-          v[1] = q.y;
-          v[2] = q.z;
-          v[3] = q.w;
-        }
-      }
+      if (x < W) load_map4<DT>(src + x, v);
     } else {
       if (x < W) v[0] = (uint32_t)src[x];
     }
@@ -87,7 +59,7 @@ __global__ __launch_bounds__(kBdThreads) void boundary_rows_kernel(const void* _
     const int x0 = xs + lane * PIX;
     int key[PIX];
 #pragma unroll
-    for (int j = 0; j < PIX; ++j) key[j] = key_of<DT>(cur[j]);
+    for (int j = 0; j < PIX; ++j) key[j] = map_id<DT>(cur[j]);
     int prev = __shfl_up(key[PIX - 1], 1, 64);
     if (lane == 0) prev = carry_key;
     int lc[PIX];  // last change at or before the pixel inside this lane, -1 for none
@@ -131,7 +103,7 @@ __global__ __launch_bounds__(kBdThreads) void boundary_cols_kernel(const void* _
                                                                   const uint8_t* __restrict__ plane,
                                                                   int32_t* __restrict__ out, int H, int W, int d,
                                                                   int chunk_rows) {
-  using E = typename std::conditional<DT == WM2F_U8, uint8_t, uint32_t>::type;
+  using E = typename MapElem<DT>::type;
   const int x = blockIdx.x * kBdThreads + threadIdx.x;
   if (x >= W) return;
   const int y0 = blockIdx.y * chunk_rows;
@@ -158,7 +130,7 @@ __global__ __launch_bounds__(kBdThreads) void boundary_cols_kernel(const void* _
     for (int u = 0; u < kBdUnroll; ++u) {
       const int r = r0 + u;
       if (r >= re) break;
-      const int k = key_of<DT>(v[u]);
+      const int k = map_id<DT>(v[u]);
       cnt = h[u] ? ((k == prev && r > rs) ? cnt + 1 : 1) : 0;
       prev = k;
       if (r >= y0 && r < y1) dst[(int64_t)r * W] = k;
@@ -179,13 +151,15 @@ __global__ __launch_bounds__(kBdThreads) void boundary_cols_kernel(const void* _
   }
 }
 
+static_assert(kBdThreads == kMapColumnThreads, "column_chunk_rows sizes the grid of the vertical pass");
+
 }  // namespace
 }  // namespace wm2f
 
 using namespace wm2f;
 
 extern "C" int64_t wm2f_labelmap_boundary_workspace(int B, int H, int W) {
-  if (B <= 0 || H <= 0 || W <= 0 || H > kBdMaxSide || W > kBdMaxSide || B > kBdMaxBatch) return -1;
+  if (B <= 0 || H <= 0 || W <= 0 || H > kMapMaxSide || W > kMapMaxSide || B > kMapMaxBatch) return -1;
   return (int64_t)B * H * W;
 }
 
@@ -194,43 +168,31 @@ extern "C" int wm2f_labelmap_boundary(const void* map, int dtype, int32_t* out, 
   const char* who = "wm2f_labelmap_boundary";
   WM2F_REQUIRE(map && out && workspace, "%s: null pointer", who);
   WM2F_REQUIRE(B > 0 && H > 0 && W > 0 && d >= 1, "%s: bad size", who);
-  WM2F_REQUIRE(dtype == WM2F_F32 || dtype == WM2F_I32 || dtype == WM2F_U8, "%s: map must be fp32, int32 or uint8", who);
-  if (H > kBdMaxSide || W > kBdMaxSide || B > kBdMaxBatch || d > kBdMaxSide) {
-    set_error("%s: sides <= %d, B <= %d, d <= %d (got %d x %d, %d, %d)", who, kBdMaxSide, kBdMaxBatch, kBdMaxSide, H, W, B,
+  WM2F_REQUIRE_MAP_DTYPE(dtype, who);
+  if (H > kMapMaxSide || W > kMapMaxSide || B > kMapMaxBatch || d > kMapMaxSide) {
+    set_error("%s: sides <= %d, B <= %d, d <= %d (got %d x %d, %d, %d)", who, kMapMaxSide, kMapMaxBatch, kMapMaxSide, H, W, B,
               d);
     return WM2F_EUNSUPPORTED;
   }
   hipStream_t s = (hipStream_t)stream;
   uint8_t* plane = reinterpret_cast<uint8_t*>(workspace);
-  const size_t esz = dtype == WM2F_U8 ? 1 : 4;
-  const bool vec = W % 4 == 0 && reinterpret_cast<uintptr_t>(map) % (esz * 4) == 0 && reinterpret_cast<uintptr_t>(plane) % 4 == 0;
+  const bool vec = map_vec4_ok(map, dtype, W) && reinterpret_cast<uintptr_t>(plane) % 4 == 0;
   const int64_t rows = (int64_t)B * H;
   const dim3 rgrid((unsigned)ceil_div64(rows, kBdWaves));
-#define WM2F_BD_ROWS(DT)                                                                                              \
-  do {                                                                                                                \
-    if (vec) hipLaunchKernelGGL((boundary_rows_kernel<DT, 4>), rgrid, dim3(kBdThreads), 0, s, map, plane, rows, W, d); \
-    else hipLaunchKernelGGL((boundary_rows_kernel<DT, 1>), rgrid, dim3(kBdThreads), 0, s, map, plane, rows, W, d);     \
-  } while (0)
-  if (dtype == WM2F_F32) WM2F_BD_ROWS(WM2F_F32);
-  else if (dtype == WM2F_I32) WM2F_BD_ROWS(WM2F_I32);
-  else WM2F_BD_ROWS(WM2F_U8);
-#undef WM2F_BD_ROWS
+  for_map_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    if (vec) hipLaunchKernelGGL((boundary_rows_kernel<DT, 4>), rgrid, dim3(kBdThreads), 0, s, map, plane, rows, W, d);
+    else hipLaunchKernelGGL((boundary_rows_kernel<DT, 1>), rgrid, dim3(kBdThreads), 0, s, map, plane, rows, W, d);
+  });
   WM2F_CHECK_LAUNCH(who);
-  // row chunks: about kBdTargetWaves waves in all, each chunk at least kBdMinChunkRows and 2d rows (its 2d rows of
+  // row chunks: about kMapColumnWaves waves in all, each chunk at least kBdMinChunkRows and 2d rows (its 2d rows of
   // warm-up then cost at most what it owns; neighbouring chunks read them at about the same time)
-  const int col_blocks = ceil_div(W, kBdThreads);
-  const int want = ceil_div(kBdTargetWaves, B * col_blocks * kBdWaves);
-  int chunk_rows = ceil_div(H, want);
-  const int min_rows = 2 * d > kBdMinChunkRows ? (2 * d < H ? 2 * d : H) : kBdMinChunkRows;
-  chunk_rows = chunk_rows < min_rows ? min_rows : chunk_rows;
-  chunk_rows = chunk_rows > H ? H : chunk_rows;
-  const dim3 cgrid(col_blocks, ceil_div(H, chunk_rows), B);
-  if (dtype == WM2F_F32)
-    hipLaunchKernelGGL((boundary_cols_kernel<WM2F_F32>), cgrid, dim3(kBdThreads), 0, s, map, plane, out, H, W, d, chunk_rows);
-  else if (dtype == WM2F_I32)
-    hipLaunchKernelGGL((boundary_cols_kernel<WM2F_I32>), cgrid, dim3(kBdThreads), 0, s, map, plane, out, H, W, d, chunk_rows);
-  else
-    hipLaunchKernelGGL((boundary_cols_kernel<WM2F_U8>), cgrid, dim3(kBdThreads), 0, s, map, plane, out, H, W, d, chunk_rows);
+  const int chunk_rows = column_chunk_rows(B, H, W, 2 * d > kBdMinChunkRows ? 2 * d : kBdMinChunkRows);
+  const dim3 cgrid(ceil_div(W, kBdThreads), ceil_div(H, chunk_rows), B);
+  for_map_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(boundary_cols_kernel<decltype(dt)::value>, cgrid, dim3(kBdThreads), 0, s, map, plane, out, H, W, d,
+                       chunk_rows);
+  });
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;
 }

@@ -28,16 +28,13 @@
 // No loop depends on a map value: a value is decoded to an id in [0, N) or to "free" before anything indexes with it.
 #include <type_traits>
 
-#include "common.h"
 #include "labelling.h"
+#include "labelmap.h"
 
 namespace wm2f {
 namespace {
 
 constexpr int kClThreads = 256;
-constexpr int kClMaxSide = 16384;
-constexpr int kClMaxBatch = 32;
-constexpr int kClMaxIds = 4096;
 constexpr int kClBestPx = 16;                                 // pixels per thread of clean_best
 constexpr int kClBestLdsIds = 1024;                           // 20 B of LDS per id: 20 KiB at the cap
 constexpr uint32_t kClBorder = 0x80000000u;                   // a free component touches the image border (areas < 2^29)
@@ -77,18 +74,6 @@ __host__ inline ClWs carve(void* ws, int64_t n_ids, int64_t n_px) {
   return w;
 }
 
-// the id of a raw map value in [0, N), -1 (free) for everything else
-template <int DT>
-__device__ __forceinline__ int id_of(uint32_t raw, int N) {
-  int v;
-  if (DT == WM2F_F32) {
-    if (!f32_bits_to_int(raw, v)) return -1;
-  } else {
-    v = (int)raw;  // int32 as it is; a uint8 arrives zero-extended
-  }
-  return (v >= 0 && v < N) ? v : -1;
-}
-
 template <int kMode>
 __device__ __forceinline__ bool is_active(int key) {
   return kMode == kPieces ? key >= 0 : key == -1;
@@ -119,7 +104,7 @@ __global__ __launch_bounds__(kClThreads) void clean_init_kernel(long long* __res
 template <int kMode, int DT>
 __global__ __launch_bounds__(kLabelThreads) void clean_local_kernel(const void* __restrict__ map, ClWs ws, int H, int W,
                                                                  int N) {
-  using E = typename std::conditional<DT == WM2F_U8, uint8_t, uint32_t>::type;
+  using E = typename MapElem<DT>::type;
   constexpr int kAux = kMode == kFree ? kLabelTilePx : 1;
   __shared__ int32_t s_parent[kLabelTilePx];
   __shared__ int32_t s_key[kLabelTilePx];
@@ -137,7 +122,7 @@ __global__ __launch_bounds__(kLabelThreads) void clean_local_kernel(const void* 
     if (y < H && x < W) {
       const int64_t p = (int64_t)y * W + x;
       if (kMode == kPieces) {
-        c = id_of<DT>((uint32_t)reinterpret_cast<const E*>(map)[img + p], N);
+        c = map_id_below<DT>((uint32_t)reinterpret_cast<const E*>(map)[img + p], N);
         key[p] = c;
       } else {
         c = key[p];
@@ -451,7 +436,7 @@ int64_t workspace_bytes(int B, int H, int W, int N) {
 using namespace wm2f;
 
 extern "C" int64_t wm2f_labelmap_clean_workspace(int B, int H, int W, int N) {
-  if (B <= 0 || H <= 0 || W <= 0 || N < 0 || H > kClMaxSide || W > kClMaxSide || B > kClMaxBatch || N > kClMaxIds) return -1;
+  if (B <= 0 || H <= 0 || W <= 0 || N < 0 || H > kMapMaxSide || W > kMapMaxSide || B > kMapMaxBatch || N > kMapMaxIds) return -1;
   return workspace_bytes(B, H, W, N);
 }
 
@@ -462,20 +447,20 @@ extern "C" int wm2f_labelmap_clean(const void* map, int dtype, void* out, int ou
   WM2F_REQUIRE(phase >= WM2F_CLEAN_ALL && phase <= WM2F_CLEAN_PAINT, "%s: unknown phase %d", who, phase);
   WM2F_REQUIRE(map && out && n_out && workspace && (stats || N == 0), "%s: null pointer", who);
   WM2F_REQUIRE(B > 0 && H > 0 && W > 0 && N >= 0, "%s: bad size", who);
-  WM2F_REQUIRE(dtype == WM2F_F32 || dtype == WM2F_I32 || dtype == WM2F_U8, "%s: map must be fp32, int32 or uint8", who);
+  WM2F_REQUIRE_MAP_DTYPE(dtype, who);
   WM2F_REQUIRE(out_dtype == WM2F_F32 || out_dtype == WM2F_I32, "%s: out must be fp32 or int32", who);
   WM2F_REQUIRE(keep == WM2F_CLEAN_KEEP_ALL || keep == WM2F_CLEAN_KEEP_LARGEST, "%s: unknown keep mode %d", who, keep);
   WM2F_REQUIRE((fill_holes == 0 || fill_holes == 1) && (relabel == 0 || relabel == 1), "%s: fill_holes and relabel are 0 or 1",
                who);
   WM2F_REQUIRE(min_area >= 0, "%s: min_area must not be negative", who);
   WM2F_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, "%s: the workspace must be 8-byte aligned", who);
-  if (H > kClMaxSide || W > kClMaxSide || B > kClMaxBatch || N > kClMaxIds) {
-    set_error("%s: sides <= %d, B <= %d, N <= %d (got %d x %d, %d, %d)", who, kClMaxSide, kClMaxBatch, kClMaxIds, H, W, B,
+  if (H > kMapMaxSide || W > kMapMaxSide || B > kMapMaxBatch || N > kMapMaxIds) {
+    set_error("%s: sides <= %d, B <= %d, N <= %d (got %d x %d, %d, %d)", who, kMapMaxSide, kMapMaxBatch, kMapMaxIds, H, W, B,
               N);
     return WM2F_EUNSUPPORTED;
   }
   const int64_t all_px = (int64_t)B * H * W;
-  const uintptr_t m0 = reinterpret_cast<uintptr_t>(map), m1 = m0 + (uintptr_t)all_px * (dtype == WM2F_U8 ? 1 : 4);
+  const uintptr_t m0 = reinterpret_cast<uintptr_t>(map), m1 = m0 + (uintptr_t)all_px * map_elem_bytes(dtype);
   const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + (uintptr_t)all_px * 4;
   WM2F_REQUIRE(o1 <= m0 || m1 <= o0, "%s: out overlaps map", who);
   const uintptr_t w0 = reinterpret_cast<uintptr_t>(workspace), w1 = w0 + (uintptr_t)workspace_bytes(B, H, W, N);
@@ -490,9 +475,7 @@ extern "C" int wm2f_labelmap_clean(const void* map, int dtype, void* out, int ou
   if (runs(WM2F_CLEAN_PIECES)) {
     if (B * N > 0)
       hipLaunchKernelGGL(clean_init_kernel, dim3(ceil_div(B * N, kClThreads)), dim3(kClThreads), 0, s, st, ws.best, B * N);
-    if (dtype == WM2F_F32) launch_labelling<kPieces, WM2F_F32>(map, ws, B, H, W, N, s);
-    else if (dtype == WM2F_I32) launch_labelling<kPieces, WM2F_I32>(map, ws, B, H, W, N, s);
-    else launch_labelling<kPieces, WM2F_U8>(map, ws, B, H, W, N, s);
+    for_map_dtype(dtype, [&](auto dt) { launch_labelling<kPieces, decltype(dt)::value>(map, ws, B, H, W, N, s); });
     WM2F_CHECK_LAUNCH(who);
   }
   if (runs(WM2F_CLEAN_CHOOSE)) {
@@ -511,16 +494,15 @@ extern "C" int wm2f_labelmap_clean(const void* map, int dtype, void* out, int ou
   hipLaunchKernelGGL(clean_relabel_kernel, dim3((unsigned)B), dim3(kClThreads), 0, s, ws, st, n_out, N, relabel);
   const bool vec = W % 4 == 0 && o0 % 16 == 0 && reinterpret_cast<uintptr_t>(ws.key) % 16 == 0;
   const dim3 vgrid((unsigned)ceil_div(n_px, kClThreads * 4), (unsigned)B);
-#define WM2F_CL_PAINT(O)                                                                                              \
-  do {                                                                                                                \
-    if (vec) hipLaunchKernelGGL((clean_paint_kernel<O, 4>), vgrid, dim3(kClThreads), 0, s, ws, (O*)out, n_px, N,      \
-                                fill_holes, (long long)max_hole_area);                                                \
-    else hipLaunchKernelGGL((clean_paint_kernel<O, 1>), px_grid, dim3(kClThreads), 0, s, ws, (O*)out, n_px, N,        \
-                            fill_holes, (long long)max_hole_area);                                                    \
-  } while (0)
-  if (out_dtype == WM2F_F32) WM2F_CL_PAINT(float);
-  else WM2F_CL_PAINT(int32_t);
-#undef WM2F_CL_PAINT
+  const auto paint = [&](auto* o) {  // o: out as the type it is painted in
+    using O = std::remove_pointer_t<decltype(o)>;
+    if (vec) hipLaunchKernelGGL((clean_paint_kernel<O, 4>), vgrid, dim3(kClThreads), 0, s, ws, o, n_px, N, fill_holes,
+                                (long long)max_hole_area);
+    else hipLaunchKernelGGL((clean_paint_kernel<O, 1>), px_grid, dim3(kClThreads), 0, s, ws, o, n_px, N, fill_holes,
+                            (long long)max_hole_area);
+  };
+  if (out_dtype == WM2F_F32) paint((float*)out);
+  else paint((int32_t*)out);
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;
 }

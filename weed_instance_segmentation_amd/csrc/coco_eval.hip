@@ -10,7 +10,7 @@
 //   coco_match     : the greedy COCO matching, one 64-lane workgroup per image, a lane per (area range, IoU threshold).
 //                    coco_match_min is the same walk with a second (inter, area, area) triple: the IoU of a pair is the
 //                    smaller of the two quotients (Boundary AP: mask IoU and boundary IoU).
-#include "common.h"
+#include "labelmap.h"
 
 namespace wm2f {
 namespace {
@@ -24,19 +24,13 @@ constexpr int kMatchMaxD = 1024;      // detections per image in LDS (see wm2f.h
 constexpr int kMatchMaxLanes = 64;    // area ranges x thresholds
 
 __device__ __forceinline__ int pred_row(float v, int P) {
-  // the post-processor writes ids as exact small floats; anything else is "no prediction"
+  // the post-processor writes ids as exact small floats; anything else is "no prediction".  A rule of its own, on the
+  // float and not on its bits (labelmap.h's map_id_below): the prediction arrives typed, and P may exceed 2^24
   return (v >= 0.f && v < (float)P && v == floorf(v)) ? (int)v + 1 : 0;
 }
 __device__ __forceinline__ int pred_row(int32_t v, int P) { return (v >= 0 && v < P) ? v + 1 : 0; }
 
-__device__ __forceinline__ int gt_col(int32_t v, const int32_t* ids, int n) {
-  int lo = 0, hi = n;  // lower_bound in the sorted ids
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (ids[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  return (lo < n && ids[lo] == v) ? lo + 1 : 0;
-}
+__device__ __forceinline__ int gt_col(int32_t v, const int32_t* ids, int n) { return list_row(v, ids, n) + 1; }
 
 // grid (chunks, B), 256 threads.  hist (B, P+1, G+1) cleared by the host side.  The (0, 0) bin -- background on both
 // maps, most of an image -- is never counted per pixel: each block adds the number of pixels it skipped once.
@@ -409,23 +403,20 @@ extern "C" int wm2f_labelmap_pair_counts(const void* pred_map, int pred_dtype, c
   const dim3 grid((unsigned)ceil_div64(n_pixels, chunk), B);
   const bool lds = nb <= kPcLdsBins;
   const size_t shm = (size_t)(G + (lds ? nb : 0)) * sizeof(int32_t);
-#define WM2F_PAIRS_LAUNCH(PT, GT_)                                                                                    \
-  if (lds)                                                                                                            \
-    hipLaunchKernelGGL((labelmap_pairs_kernel<PT, GT_, true>), grid, dim3(kPcThreads), shm, s, (const PT*)pred_map,   \
-                       (const GT_*)gt_map, gt_ids, n_ids, hist, n_pixels, P, G, chunk);                               \
-  else                                                                                                                \
-    hipLaunchKernelGGL((labelmap_pairs_kernel<PT, GT_, false>), grid, dim3(kPcThreads), shm, s, (const PT*)pred_map,  \
-                       (const GT_*)gt_map, gt_ids, n_ids, hist, n_pixels, P, G, chunk);
-  if (pred_dtype == WM2F_F32 && gt_dtype == WM2F_U8) {
-    WM2F_PAIRS_LAUNCH(float, uint8_t)
-  } else if (pred_dtype == WM2F_F32) {
-    WM2F_PAIRS_LAUNCH(float, int32_t)
-  } else if (gt_dtype == WM2F_U8) {
-    WM2F_PAIRS_LAUNCH(int32_t, uint8_t)
-  } else {
-    WM2F_PAIRS_LAUNCH(int32_t, int32_t)
-  }
-#undef WM2F_PAIRS_LAUNCH
+  const auto launch = [&](auto* pred, auto* gt) {  // the two maps as the types they hold
+    using PT = std::remove_const_t<std::remove_pointer_t<decltype(pred)>>;
+    using GT = std::remove_const_t<std::remove_pointer_t<decltype(gt)>>;
+    if (lds)
+      hipLaunchKernelGGL((labelmap_pairs_kernel<PT, GT, true>), grid, dim3(kPcThreads), shm, s, pred, gt, gt_ids, n_ids, hist,
+                         n_pixels, P, G, chunk);
+    else
+      hipLaunchKernelGGL((labelmap_pairs_kernel<PT, GT, false>), grid, dim3(kPcThreads), shm, s, pred, gt, gt_ids, n_ids, hist,
+                         n_pixels, P, G, chunk);
+  };
+  if (pred_dtype == WM2F_F32 && gt_dtype == WM2F_U8) launch((const float*)pred_map, (const uint8_t*)gt_map);
+  else if (pred_dtype == WM2F_F32) launch((const float*)pred_map, (const int32_t*)gt_map);
+  else if (gt_dtype == WM2F_U8) launch((const int32_t*)pred_map, (const uint8_t*)gt_map);
+  else launch((const int32_t*)pred_map, (const int32_t*)gt_map);
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;
 }

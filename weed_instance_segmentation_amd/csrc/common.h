@@ -47,22 +47,4 @@ __device__ __forceinline__ int xcd_contiguous_id(int bid, int per_xcd) {
 __host__ __device__ __forceinline__ int ceil_div(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ __forceinline__ int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-
-// the id a float map value stands for (wm2f_labelmap_instance_stats, wm2f_labelmap_overlay), from its bits: +-0 and exact
-// integers in [1, 2^24); anything else is no id
-__device__ __forceinline__ bool f32_bits_to_int(uint32_t u, int& out) {
-  if ((u << 1) == 0u) {
-    out = 0;
-    return true;
-  }
-  if (u >> 31) return false;
-  const int e = (int)(u >> 23) - 127;
-  if (e < 0 || e > 23) return false;
-  const uint32_t m = (u & 0x7fffffu) | 0x800000u;
-  const int sh = 23 - e;
-  if (m & ((1u << sh) - 1u)) return false;
-  out = (int)(m >> sh);
-  return true;
-}
-
 }  // namespace wm2f

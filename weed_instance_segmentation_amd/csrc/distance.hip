@@ -22,20 +22,13 @@
 // aim points: init (rounded centroids from the stats rows), an atomicMax of d2 per instance, an unsigned 64-bit atomicMin
 // of (centroid distance^2 << 32 | y * W + x) over the pixels that attain it, and a pass that writes the rows.
 // Everything is integer and no result depends on an order of accumulation.
-#include <type_traits>
-
-#include "common.h"
+#include "labelmap.h"
 
 namespace wm2f {
 namespace {
 
 constexpr int kDtThreads = 256;
-constexpr int kDtWaves = kDtThreads / 64;
-constexpr int kDtMaxSide = 16384;
-constexpr int kDtMaxBatch = 32;
-constexpr int kDtMaxIds = 4096;
 constexpr int kDtMinChunkRows = 32;   // columns pass: a chunk owns at least this many rows
-constexpr int kDtTargetWaves = 2048;  // about this many waves in the columns pass's grid
 constexpr int kDtUnroll = 8;          // rows of one column in flight
 constexpr int kDtRowPixels = 1024;    // rows pass: short rows share a workgroup up to this many pixels (8 KiB of LDS)
 constexpr int kDtWideRow = 4096;      // rows pass: a longer row gets a workgroup of kDtRowThreadsWide threads
@@ -45,27 +38,11 @@ constexpr int kDtLdsMaxIds = 1024;    // aim points: per-instance accumulators i
 constexpr int kDtNone = 0xffff;       // g: no position of the column is off the pixel's id
 constexpr int kDtNoKey = -2;          // equals no pixel's key, not even "no id" (-1)
 
-// the id of a raw map value, -1 for none (wm2f_labelmap_instance_stats's rule for floats; a negative int32 is no id)
-template <int DT>
-__device__ __forceinline__ int key_of(uint32_t raw) {
-  if (DT == WM2F_F32) {
-    int v;
-    return f32_bits_to_int(raw, v) ? v : -1;
-  }
-  const int v = (int)raw;  // a uint8 arrives zero-extended
-  return v < 0 ? -1 : v;
-}
-
 // result row of a key, -1 for none: the key itself when in [0, N), or its position in the image's ascending list
 __device__ __forceinline__ int row_of_key(int v, const int32_t* ids, int n, int N) {
   if (v < 0) return -1;
   if (ids == nullptr) return v < N ? v : -1;
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (ids[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  return (lo < n && ids[lo] == v) ? lo : -1;
+  return list_row(v, ids, n);
 }
 
 // grid (ceil(W / 256), chunks, B), 256 threads: a lane per column, the chunk's rows top to bottom.
@@ -73,7 +50,7 @@ __device__ __forceinline__ int row_of_key(int v, const int32_t* ids, int n, int 
 template <int DT>
 __global__ __launch_bounds__(kDtThreads) void distance_summary_kernel(const void* __restrict__ map, int4* __restrict__ sum,
                                                                      int H, int W, int chunk_rows) {
-  using E = typename std::conditional<DT == WM2F_U8, uint8_t, uint32_t>::type;
+  using E = typename MapElem<DT>::type;
   const int x = blockIdx.x * kDtThreads + threadIdx.x;
   if (x >= W) return;
   const int y0 = blockIdx.y * chunk_rows;
@@ -89,7 +66,7 @@ __global__ __launch_bounds__(kDtThreads) void distance_summary_kernel(const void
     for (int u = 0; u < kDtUnroll; ++u) {
       const int r = r0 + u;
       if (r >= y1) break;
-      const int k = key_of<DT>(v[u]);
+      const int k = map_id<DT>(v[u]);
       if (k == cur) {
         ++run;
       } else {
@@ -113,7 +90,7 @@ template <int DT>
 __global__ __launch_bounds__(kDtThreads) void distance_cols_kernel(const void* __restrict__ map, const int4* __restrict__ sum,
                                                                   uint16_t* __restrict__ g, int H, int W, int chunk_rows,
                                                                   int border_outside) {
-  using E = typename std::conditional<DT == WM2F_U8, uint8_t, uint32_t>::type;
+  using E = typename MapElem<DT>::type;
   const int x = blockIdx.x * kDtThreads + threadIdx.x;
   if (x >= W) return;
   const int c = blockIdx.y, chunks = gridDim.y;
@@ -146,7 +123,7 @@ __global__ __launch_bounds__(kDtThreads) void distance_cols_kernel(const void* _
     for (int u = 0; u < kDtUnroll; ++u) {
       const int r = r0 + u;
       if (r >= y1) break;
-      const int k = key_of<DT>(v[u]);
+      const int k = map_id<DT>(v[u]);
       const bool same = k == prev;
       cnt = same ? cnt + 1 : 1;
       open = same ? open : r == 0;
@@ -183,7 +160,7 @@ __global__ __launch_bounds__(kDtThreads) void distance_cols_kernel(const void* _
     for (int u = 0; u < kDtUnroll; ++u) {
       const int r = r0 - u;
       if (r < y0) break;
-      const int k = key_of<DT>(v[u]);
+      const int k = map_id<DT>(v[u]);
       const bool same = k == prev;
       cnt = same ? cnt + 1 : 1;
       open = same ? open : r == H - 1;
@@ -201,7 +178,7 @@ __global__ __launch_bounds__(kDtRowThreadsWide) void distance_rows_kernel(const 
                                                                          const uint16_t* __restrict__ g,
                                                                          int32_t* __restrict__ d2, int64_t rows, int W,
                                                                          int rpb, int border_outside) {
-  using E = typename std::conditional<DT == WM2F_U8, uint8_t, uint32_t>::type;
+  using E = typename MapElem<DT>::type;
   extern __shared__ __align__(16) unsigned char dtmem[];
   int* skey = reinterpret_cast<int*>(dtmem);
   uint16_t* sg = reinterpret_cast<uint16_t*>(dtmem + (size_t)rpb * W * sizeof(int));
@@ -216,25 +193,15 @@ __global__ __launch_bounds__(kDtRowThreadsWide) void distance_rows_kernel(const 
   if (kVec) {
     for (int i = tid * 4; i < n; i += nt * 4) {  // n % 4 == 0
       uint32_t v[4];
-      if (DT == WM2F_U8) {
-        const uint32_t w4 = *reinterpret_cast<const uint32_t*>(src + i);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = (w4 >> (8 * j)) & 0xffu;
-      } else {
-        const uint4 q = *reinterpret_cast<const uint4*>(src + i);
-        v[0] = q.x;
-        v[1] = q.y;
-        v[2] = q.z;
-        v[3] = q.w;
-      }
+      load_map4<DT>(src + i, v);
       const uint2 gq = *reinterpret_cast<const uint2*>(gs + i);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) skey[i + j] = key_of<DT>(v[j]);
+      for (int j = 0; j < 4; ++j) skey[i + j] = map_id<DT>(v[j]);
       *reinterpret_cast<uint2*>(sg + i) = gq;  // rpb * W * 4 and i * 2 are multiples of 8
     }
   } else {
     for (int i = tid; i < n; i += nt) {
-      skey[i] = key_of<DT>((uint32_t)src[i]);
+      skey[i] = map_id<DT>((uint32_t)src[i]);
       sg[i] = gs[i];
     }
   }
@@ -377,23 +344,13 @@ __global__ __launch_bounds__(kDtThreads) void aim_init_kernel(const long long* _
 // f(p, raw, d) for every pixel p of [p0, p1) of one image; kVec: four pixels per lane and load
 template <int DT, bool kVec, class F>
 __device__ __forceinline__ void aim_pixels(const void* map, const int32_t* d2, int64_t img, int p0, int p1, F&& f) {
-  using E = typename std::conditional<DT == WM2F_U8, uint8_t, uint32_t>::type;
+  using E = typename MapElem<DT>::type;
   const E* src = reinterpret_cast<const E*>(map) + img;
   const int32_t* dd = d2 + img;
   if (kVec) {
     for (int p = p0 + (int)threadIdx.x * 4; p < p1; p += kDtThreads * 4) {
       uint32_t v[4];
-      if (DT == WM2F_U8) {
-        const uint32_t w4 = *reinterpret_cast<const uint32_t*>(src + p);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = (w4 >> (8 * j)) & 0xffu;
-      } else {
-        const uint4 q = *reinterpret_cast<const uint4*>(src + p);
-        v[0] = q.x;
-        v[1] = q.y;
-        v[2] = q.z;
-        v[3] = q.w;
-      }
+      load_map4<DT>(src + p, v);
       const int4 d = *reinterpret_cast<const int4*>(dd + p);
       f(p, v[0], d.x);
       f(p + 1, v[1], d.y);
@@ -441,7 +398,7 @@ __global__ __launch_bounds__(kDtThreads) void aim_scan_kernel(const void* __rest
   unsigned long long* abest = kLds ? lbest : gbest;
   // a maximum only grows and a minimum only shrinks, so a stale read can at worst ask for an atomic that changes nothing
   aim_pixels<DT, kVec>(map, d2, (int64_t)b * HW, p0, p1, [&](int p, uint32_t raw, int d) {
-    const int r = row_of_key(key_of<DT>(raw), idl, n, N);
+    const int r = row_of_key(map_id<DT>(raw), idl, n, N);
     if (r < 0) return;
     if (!kArg) {
       if (d > amax[r]) atomicMax(amax + r, d);
@@ -479,16 +436,22 @@ __global__ __launch_bounds__(kDtThreads) void aim_write_kernel(AimWs w, int32_t*
   reinterpret_cast<int4*>(points)[i] = row;
 }
 
-int distance_chunk_rows(int B, int H, int W) {
-  const int col_blocks = ceil_div(W, kDtThreads);
-  const int want = ceil_div(kDtTargetWaves, B * col_blocks * kDtWaves);
-  int chunk_rows = ceil_div(H, want);
-  chunk_rows = chunk_rows < kDtMinChunkRows ? kDtMinChunkRows : chunk_rows;
-  return chunk_rows > H ? H : chunk_rows;
-}
+static_assert(kDtThreads == kMapColumnThreads, "column_chunk_rows sizes the grid of the columns pass");
 
-// g first (8-byte aligned for the four-pixel path), the summaries after it at a 16-byte boundary
-int64_t distance_g_bytes(int B, int H, int W) { return ((int64_t)B * H * W * 2 + 15) / 16 * 16; }
+// the rows launch for one dtype and alignment
+template <int DT, bool kVec>
+int launch_rows(const char* who, const void* map, const uint16_t* g, int32_t* d2, int64_t rows, int W, int rpb,
+                int threads, size_t lds, int border_outside, hipStream_t s) {
+  auto kfn = distance_rows_kernel<DT, kVec>;
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    set_error("%s: cannot reserve %zu bytes of LDS", who, lds);
+    return WM2F_ELAUNCH;
+  }
+  hipLaunchKernelGGL(kfn, dim3((unsigned)ceil_div64(rows, rpb)), dim3(threads), lds, s, map, g, d2, rows, W, rpb,
+                     border_outside);
+  return WM2F_OK;
+}
 
 }  // namespace
 }  // namespace wm2f
@@ -496,37 +459,33 @@ int64_t distance_g_bytes(int B, int H, int W) { return ((int64_t)B * H * W * 2 +
 using namespace wm2f;
 
 extern "C" int64_t wm2f_labelmap_distance_workspace(int B, int H, int W) {
-  if (B <= 0 || H <= 0 || W <= 0 || H > kDtMaxSide || W > kDtMaxSide || B > kDtMaxBatch) return -1;
-  const int chunks = ceil_div(H, distance_chunk_rows(B, H, W));
-  return distance_g_bytes(B, H, W) + (int64_t)B * chunks * W * (int64_t)sizeof(int4);
+  if (B <= 0 || H <= 0 || W <= 0 || H > kMapMaxSide || W > kMapMaxSide || B > kMapMaxBatch) return -1;
+  const int chunks = ceil_div(H, column_chunk_rows(B, H, W, kDtMinChunkRows));
+  return map_g_bytes(B, H, W) + (int64_t)B * chunks * W * (int64_t)sizeof(int4);
 }
 
 extern "C" int wm2f_labelmap_distance(const void* map, int dtype, int32_t* d2, void* workspace, int B, int H, int W,
                                       int border_outside, void* stream) {
   const char* who = "wm2f_labelmap_distance";
   WM2F_REQUIRE(B > 0 && H > 0 && W > 0, "%s: bad size", who);
-  if (H > kDtMaxSide || W > kDtMaxSide || B > kDtMaxBatch) {
-    set_error("%s: sides <= %d, B <= %d (got %d x %d, %d)", who, kDtMaxSide, kDtMaxBatch, H, W, B);
+  if (H > kMapMaxSide || W > kMapMaxSide || B > kMapMaxBatch) {
+    set_error("%s: sides <= %d, B <= %d (got %d x %d, %d)", who, kMapMaxSide, kMapMaxBatch, H, W, B);
     return WM2F_EUNSUPPORTED;
   }
   WM2F_REQUIRE(map && d2 && workspace, "%s: null pointer", who);
-  WM2F_REQUIRE(dtype == WM2F_F32 || dtype == WM2F_I32 || dtype == WM2F_U8, "%s: map must be fp32, int32 or uint8", who);
+  WM2F_REQUIRE_MAP_DTYPE(dtype, who);
   WM2F_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "%s: the workspace must be 16-byte aligned", who);
   hipStream_t s = (hipStream_t)stream;
   uint16_t* g = reinterpret_cast<uint16_t*>(workspace);
-  int4* sum = reinterpret_cast<int4*>(reinterpret_cast<unsigned char*>(workspace) + distance_g_bytes(B, H, W));
-  const int chunk_rows = distance_chunk_rows(B, H, W);
+  int4* sum = reinterpret_cast<int4*>(reinterpret_cast<unsigned char*>(workspace) + map_g_bytes(B, H, W));
+  const int chunk_rows = column_chunk_rows(B, H, W, kDtMinChunkRows);
   const dim3 cgrid(ceil_div(W, kDtThreads), ceil_div(H, chunk_rows), B);
-#define WM2F_DT_COLS(DT)                                                                                             \
-  do {                                                                                                               \
-    hipLaunchKernelGGL((distance_summary_kernel<DT>), cgrid, dim3(kDtThreads), 0, s, map, sum, H, W, chunk_rows);     \
-    hipLaunchKernelGGL((distance_cols_kernel<DT>), cgrid, dim3(kDtThreads), 0, s, map, sum, g, H, W, chunk_rows,      \
-                       border_outside);                                                                              \
-  } while (0)
-  if (dtype == WM2F_F32) WM2F_DT_COLS(WM2F_F32);
-  else if (dtype == WM2F_I32) WM2F_DT_COLS(WM2F_I32);
-  else WM2F_DT_COLS(WM2F_U8);
-#undef WM2F_DT_COLS
+  for_map_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    hipLaunchKernelGGL(distance_summary_kernel<DT>, cgrid, dim3(kDtThreads), 0, s, map, sum, H, W, chunk_rows);
+    hipLaunchKernelGGL(distance_cols_kernel<DT>, cgrid, dim3(kDtThreads), 0, s, map, sum, g, H, W, chunk_rows,
+                       border_outside);
+  });
   WM2F_CHECK_LAUNCH(who);
 
   const int64_t rows = (int64_t)B * H;
@@ -534,35 +493,19 @@ extern "C" int wm2f_labelmap_distance(const void* map, int dtype, int32_t* d2, v
   rpb = rpb > rows ? (int)rows : rpb;
   const int threads = W > kDtWideRow ? kDtRowThreadsWide : kDtThreads;
   const size_t lds = (size_t)rpb * W * (sizeof(int) + 2 * sizeof(uint16_t)) + (size_t)rpb * ceil_div(W, 64) * 2 * sizeof(int);
-  const size_t esz = dtype == WM2F_U8 ? 1 : 4;
-  const bool vec = W % 4 == 0 && reinterpret_cast<uintptr_t>(map) % (esz * 4) == 0;  // g is 16-byte aligned
-  const dim3 rgrid((unsigned)ceil_div64(rows, rpb));
-#define WM2F_DT_ROWS(DT, VEC)                                                                                        \
-  do {                                                                                                               \
-    auto kfn = distance_rows_kernel<DT, VEC>;                                                                        \
-    if (lds > 64 * 1024 &&                                                                                           \
-        hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { \
-      set_error("%s: cannot reserve %zu bytes of LDS", who, lds);                                                    \
-      return WM2F_ELAUNCH;                                                                                           \
-    }                                                                                                                \
-    hipLaunchKernelGGL(kfn, rgrid, dim3(threads), lds, s, map, g, d2, rows, W, rpb, border_outside);                  \
-  } while (0)
-#define WM2F_DT_DTYPE(DT)           \
-  do {                              \
-    if (vec) WM2F_DT_ROWS(DT, true); \
-    else WM2F_DT_ROWS(DT, false);    \
-  } while (0)
-  if (dtype == WM2F_F32) WM2F_DT_DTYPE(WM2F_F32);
-  else if (dtype == WM2F_I32) WM2F_DT_DTYPE(WM2F_I32);
-  else WM2F_DT_DTYPE(WM2F_U8);
-#undef WM2F_DT_DTYPE
-#undef WM2F_DT_ROWS
+  const bool vec = map_vec4_ok(map, dtype, W);  // g is 16-byte aligned
+  const int rc = for_map_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    return vec ? launch_rows<DT, true>(who, map, g, d2, rows, W, rpb, threads, lds, border_outside, s)
+               : launch_rows<DT, false>(who, map, g, d2, rows, W, rpb, threads, lds, border_outside, s);
+  });
+  if (rc != WM2F_OK) return rc;
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;
 }
 
 extern "C" int64_t wm2f_labelmap_aim_points_workspace(int B, int N) {
-  if (B <= 0 || N <= 0 || B > kDtMaxBatch || N > kDtMaxIds) return -1;
+  if (B <= 0 || N <= 0 || B > kMapMaxBatch || N > kMapMaxIds) return -1;
   return (int64_t)B * N * 20;
 }
 
@@ -571,14 +514,14 @@ extern "C" int wm2f_labelmap_aim_points(const void* map, int dtype, const int32_
                                         int B, int H, int W, int N, void* stream) {
   const char* who = "wm2f_labelmap_aim_points";
   WM2F_REQUIRE(B > 0 && H > 0 && W > 0 && N > 0, "%s: bad size", who);
-  if (H > kDtMaxSide || W > kDtMaxSide || B > kDtMaxBatch || N > kDtMaxIds) {
-    set_error("%s: sides <= %d, B <= %d, N <= %d (got %d x %d, %d, %d)", who, kDtMaxSide, kDtMaxBatch, kDtMaxIds, H, W,
+  if (H > kMapMaxSide || W > kMapMaxSide || B > kMapMaxBatch || N > kMapMaxIds) {
+    set_error("%s: sides <= %d, B <= %d, N <= %d (got %d x %d, %d, %d)", who, kMapMaxSide, kMapMaxBatch, kMapMaxIds, H, W,
               B, N);
     return WM2F_EUNSUPPORTED;
   }
   WM2F_REQUIRE(map && d2 && points && workspace, "%s: null pointer", who);
   WM2F_REQUIRE((ids == nullptr) == (n_ids == nullptr), "%s: ids and n_ids go together", who);
-  WM2F_REQUIRE(dtype == WM2F_F32 || dtype == WM2F_I32 || dtype == WM2F_U8, "%s: map must be fp32, int32 or uint8", who);
+  WM2F_REQUIRE_MAP_DTYPE(dtype, who);
   WM2F_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 8 == 0 && reinterpret_cast<uintptr_t>(points) % 16 == 0,
                "%s: the workspace must be 8-byte and points 16-byte aligned", who);
   hipStream_t s = (hipStream_t)stream;
@@ -592,31 +535,24 @@ extern "C" int wm2f_labelmap_aim_points(const void* map, int dtype, const int32_
   span = span < 4096 ? 4096 : ceil_div(span, 1024) * 1024;
   const dim3 grid(ceil_div(HW, span), B);
   const bool lds = N <= kDtLdsMaxIds;
-  const size_t esz = dtype == WM2F_U8 ? 1 : 4;
-  const bool vec = W % 4 == 0 && reinterpret_cast<uintptr_t>(map) % (esz * 4) == 0 && reinterpret_cast<uintptr_t>(d2) % 16 == 0;
+  const bool vec = map_vec4_ok(map, dtype, W) && reinterpret_cast<uintptr_t>(d2) % 16 == 0;
   const int centred = stats != nullptr;
-#define WM2F_AIM_LAUNCH(DT, VEC, LDS, ARG)                                                                             \
-  hipLaunchKernelGGL((aim_scan_kernel<DT, VEC, LDS, ARG>), grid, dim3(kDtThreads),                                     \
-                     (LDS ? (size_t)N * (ARG ? 12 : 4) : 0) + (ids ? (size_t)N * 4 : 0), s, map, d2, ids, n_ids, w, HW, \
-                     W, N, span, centred)
-#define WM2F_AIM_DTYPE(DT, ARG)                              \
-  do {                                                       \
-    if (vec && lds) WM2F_AIM_LAUNCH(DT, true, true, ARG);    \
-    else if (vec) WM2F_AIM_LAUNCH(DT, true, false, ARG);     \
-    else if (lds) WM2F_AIM_LAUNCH(DT, false, true, ARG);     \
-    else WM2F_AIM_LAUNCH(DT, false, false, ARG);             \
-  } while (0)
-#define WM2F_AIM_PASS(ARG)                                   \
-  do {                                                       \
-    if (dtype == WM2F_F32) WM2F_AIM_DTYPE(WM2F_F32, ARG);    \
-    else if (dtype == WM2F_I32) WM2F_AIM_DTYPE(WM2F_I32, ARG); \
-    else WM2F_AIM_DTYPE(WM2F_U8, ARG);                       \
-  } while (0)
-  WM2F_AIM_PASS(false);
-  WM2F_AIM_PASS(true);
-#undef WM2F_AIM_PASS
-#undef WM2F_AIM_DTYPE
-#undef WM2F_AIM_LAUNCH
+  for_map_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    const auto pass = [&](auto arg) {  // kArg false: the maxima; true: the pixels that attain them
+      constexpr bool kArg = decltype(arg)::value;
+      const auto scan = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(kDtThreads), (lds ? (size_t)N * (kArg ? 12 : 4) : 0) + (ids ? (size_t)N * 4 : 0),
+                           s, map, d2, ids, n_ids, w, HW, W, N, span, centred);
+      };
+      if (vec && lds) scan(aim_scan_kernel<DT, true, true, kArg>);
+      else if (vec) scan(aim_scan_kernel<DT, true, false, kArg>);
+      else if (lds) scan(aim_scan_kernel<DT, false, true, kArg>);
+      else scan(aim_scan_kernel<DT, false, false, kArg>);
+    };
+    pass(std::false_type{});
+    pass(std::true_type{});
+  });
   hipLaunchKernelGGL(aim_write_kernel, igrid, dim3(kDtThreads), 0, s, w, points, total, W);
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;

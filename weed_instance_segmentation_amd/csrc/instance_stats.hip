@@ -17,23 +17,18 @@
 //                    accumulates straight into the result.
 // Everything is integer -- a float map's ids are decoded from the bits -- so the result does not depend on the order of
 // accumulation.
-#include <type_traits>
-
-#include "common.h"
+#include "labelmap.h"
 
 namespace wm2f {
 namespace {
 
 constexpr int kIsThreads = 256;
 constexpr int kIsWaves = kIsThreads / 64;
-constexpr int kIsPix = 4;               // pixels per lane per load
+constexpr int kIsPix = 4;               // pixels per lane per load (load_map4)
 constexpr int kIsSeg = 64 * kIsPix;     // pixels of one row per wave-instruction
 constexpr int kIsUnroll = 4;
 constexpr int kIsLdsMaxIds = 1024;      // 32 B of accumulators + 4 B of id list each: 36 KiB, four workgroups per CU
 constexpr int kIsMaxStripRows = 256;    // keeps a strip's relative sum_y (< 2^29 at W = 16384) in the packed word's half
-constexpr int kIsMaxSide = 16384;
-constexpr int kIsMaxBatch = 32;
-constexpr int kIsMaxIds = 4096;
 
 struct IsAcc {
   unsigned long long pk;  // count | strip-relative sum_y << 32
@@ -47,18 +42,9 @@ static_assert(sizeof(IsAcc) == 32, "IsAcc layout");
 template <int DT>
 __device__ __forceinline__ int row_of(uint32_t raw, const int32_t* ids, int n, int N) {
   int v;
-  if (DT == WM2F_F32) {
-    if (!f32_bits_to_int(raw, v)) return -1;
-  } else {
-    v = (int)raw;  // int32 as it is; a uint8 arrives zero-extended
-  }
+  if (!map_int<DT>(raw, v)) return -1;
   if (ids == nullptr) return (v >= 0 && v < N) ? v : -1;
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (ids[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  return (lo < n && ids[lo] == v) ? lo : -1;
+  return list_row(v, ids, n);
 }
 
 // a run of len pixels x0 .. x1 of row y with result row r.  The bounds only ever move one way, so a stale read can at
@@ -107,7 +93,7 @@ __global__ __launch_bounds__(kIsThreads) void instance_stats_kernel(const void* 
                                                                     const int32_t* __restrict__ n_ids,
                                                                     long long* __restrict__ stats, int H, int W, int N,
                                                                     int strip_rows) {
-  using E = typename std::conditional<DT == WM2F_U8, uint8_t, uint32_t>::type;
+  using E = typename MapElem<DT>::type;
   extern __shared__ __align__(8) unsigned char ismem[];
   IsAcc* acc = reinterpret_cast<IsAcc*>(ismem);
   int32_t* sids = reinterpret_cast<int32_t*>(ismem + (kLds ? (size_t)N * sizeof(IsAcc) : 0));
@@ -155,19 +141,7 @@ __global__ __launch_bounds__(kIsThreads) void instance_stats_kernel(const void* 
       if (iy[u] < y1) {
         const E* p = base + (int64_t)iy[u] * W + x;
         if (kVec) {
-          if (x < W) {
-            if (DT == WM2F_U8) {
-              const uint32_t w4 = *reinterpret_cast<const uint32_t*>(p);
-#pragma unroll
-              for (int j = 0; j < kIsPix; ++j) v[u][j] = (w4 >> (8 * j)) & 0xffu;
-            } else {
-              const uint4 q = *reinterpret_cast<const uint4*>(p);
-              v[u][0] = q.x;
-              v[u][1] = q.y;
-              v[u][2] = q.z;
-              v[u][3] = q.w;
-            }
-          }
+          if (x < W) load_map4<DT>(p, v[u]);
         } else {
 #pragma unroll
           for (int j = 0; j < kIsPix; ++j)
@@ -232,9 +206,9 @@ extern "C" int wm2f_labelmap_instance_stats(const void* map, int dtype, const in
   WM2F_REQUIRE(map && stats, "%s: null pointer", who);
   WM2F_REQUIRE((ids == nullptr) == (n_ids == nullptr), "%s: ids and n_ids go together", who);
   WM2F_REQUIRE(B > 0 && H > 0 && W > 0 && N > 0, "%s: bad size", who);
-  WM2F_REQUIRE(dtype == WM2F_F32 || dtype == WM2F_I32 || dtype == WM2F_U8, "%s: map must be fp32, int32 or uint8", who);
-  if (H > kIsMaxSide || W > kIsMaxSide || B > kIsMaxBatch || N > kIsMaxIds) {
-    set_error("%s: sides <= %d, B <= %d, N <= %d (got %d x %d, %d, %d)", who, kIsMaxSide, kIsMaxBatch, kIsMaxIds, H, W,
+  WM2F_REQUIRE_MAP_DTYPE(dtype, who);
+  if (H > kMapMaxSide || W > kMapMaxSide || B > kMapMaxBatch || N > kMapMaxIds) {
+    set_error("%s: sides <= %d, B <= %d, N <= %d (got %d x %d, %d, %d)", who, kMapMaxSide, kMapMaxBatch, kMapMaxIds, H, W,
               B, N);
     return WM2F_EUNSUPPORTED;
   }
@@ -249,24 +223,18 @@ extern "C" int wm2f_labelmap_instance_stats(const void* map, int dtype, const in
   rows = rows > H ? H : rows;
   const dim3 grid(ceil_div(H, rows), B);
   const bool lds = N <= kIsLdsMaxIds;
-  const size_t esz = dtype == WM2F_U8 ? 1 : 4;
-  const bool vec = W % kIsPix == 0 && reinterpret_cast<uintptr_t>(map) % (esz * kIsPix) == 0;
+  const bool vec = map_vec4_ok(map, dtype, W);
   const size_t shm = (lds ? (size_t)N * sizeof(IsAcc) : 0) + (ids ? (size_t)N * sizeof(int32_t) : 0);
-#define WM2F_IS_LAUNCH(DT, VEC, LDS)                                                                                  \
-  hipLaunchKernelGGL((instance_stats_kernel<DT, VEC, LDS>), grid, dim3(kIsThreads), shm, s, map, ids, n_ids, out, H, W, \
-                     N, rows)
-#define WM2F_IS_DTYPE(DT)                         \
-  do {                                            \
-    if (vec && lds) WM2F_IS_LAUNCH(DT, true, true);        \
-    else if (vec) WM2F_IS_LAUNCH(DT, true, false);         \
-    else if (lds) WM2F_IS_LAUNCH(DT, false, true);         \
-    else WM2F_IS_LAUNCH(DT, false, false);                 \
-  } while (0)
-  if (dtype == WM2F_F32) WM2F_IS_DTYPE(WM2F_F32);
-  else if (dtype == WM2F_I32) WM2F_IS_DTYPE(WM2F_I32);
-  else WM2F_IS_DTYPE(WM2F_U8);
-#undef WM2F_IS_DTYPE
-#undef WM2F_IS_LAUNCH
+  for_map_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    const auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, dim3(kIsThreads), shm, s, map, ids, n_ids, out, H, W, N, rows);
+    };
+    if (vec && lds) launch(instance_stats_kernel<DT, true, true>);
+    else if (vec) launch(instance_stats_kernel<DT, true, false>);
+    else if (lds) launch(instance_stats_kernel<DT, false, true>);
+    else launch(instance_stats_kernel<DT, false, false>);
+  });
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;
 }

@@ -16,20 +16,13 @@
 //                  to be seen.  kNrWalk steps' reads are in flight together.
 //   cell_counts  : a workgroup owns a tile of cells, counts its pixels into integer LDS accumulators and stores the tile:
 //                  no atomics on memory, nothing to clear.
-#include <type_traits>
-
-#include "common.h"
+#include "labelmap.h"
 
 namespace wm2f {
 namespace {
 
 constexpr int kNrThreads = 256;
-constexpr int kNrWaves = kNrThreads / 64;
-constexpr int kNrMaxSide = 16384;
-constexpr int kNrMaxBatch = 32;
-constexpr int kNrMaxIds = 4096;
 constexpr int kNrMinChunkRows = 32;   // columns pass: a chunk owns at least this many rows
-constexpr int kNrTargetWaves = 2048;  // about this many waves in the columns pass's grid
 constexpr int kNrUnroll = 8;          // rows of one column in flight
 constexpr int kNrRowPixels = 1024;    // rows pass: short rows share a workgroup up to this many pixels
 constexpr int kNrWideRow = 4096;      // rows pass: a longer row gets a workgroup of kNrRowThreadsWide threads
@@ -39,25 +32,14 @@ constexpr int kCellPixelsX = 256;     // cell counts: a tile is about this many 
 constexpr int kCellPixelsY = 16;      //              about this many tall,
 constexpr int kCellTileCells = 512;   //              and at most this many cells (32 KiB of accumulators at G = 8)
 
-// the id of a raw map value, -1 for none (wm2f_labelmap_instance_stats's rule for floats; a negative int32 is no id)
-template <int DT>
-__device__ __forceinline__ int key_of(uint32_t raw) {
-  if (DT == WM2F_F32) {
-    int v;
-    return f32_bits_to_int(raw, v) ? v : -1;
-  }
-  const int v = (int)raw;  // a uint8 arrives zero-extended
-  return v < 0 ? -1 : v;
-}
-
 // grid (ceil(W / 256), chunks, B), 256 threads: a lane per column.  g (B, H, W) uint16, gid (B, H, W) int32.
 template <int DT>
 __global__ __launch_bounds__(kNrThreads) void nearest_cols_kernel(const void* __restrict__ map,
                                                                  const uint8_t* __restrict__ source,
                                                                  uint16_t* __restrict__ g, int32_t* __restrict__ gid,
                                                                  int H, int W, int N, int chunk_rows, int r) {
-  using E = typename std::conditional<DT == WM2F_U8, uint8_t, uint32_t>::type;
-  __shared__ uint8_t ssrc[kNrMaxIds];
+  using E = typename MapElem<DT>::type;
+  __shared__ uint8_t ssrc[kMapMaxIds];
   if (source != nullptr)
     for (int j = threadIdx.x; j < N; j += kNrThreads) ssrc[j] = source[(int64_t)blockIdx.z * N + j];
   __syncthreads();
@@ -71,7 +53,7 @@ __global__ __launch_bounds__(kNrThreads) void nearest_cols_kernel(const void* __
   int32_t* idd = gid + img + x;
   const int none = r + 1;
   auto source_id = [&](uint32_t raw) {  // the id of a source pixel, -1 for every other pixel
-    const int k = key_of<DT>(raw);
+    const int k = map_id<DT>(raw);
     if (k < 0 || k >= N) return -1;
     return (source == nullptr || ssrc[k] != 0) ? k : -1;
   };
@@ -196,10 +178,10 @@ __global__ __launch_bounds__(kNrRowThreadsWide) void nearest_rows_kernel(
       int k;
       if (dtype == WM2F_U8) {
         raw = reinterpret_cast<const uint8_t*>(map)[base + i];
-        k = key_of<WM2F_U8>(raw);
+        k = map_id<WM2F_U8>(raw);
       } else {
         raw = reinterpret_cast<const uint32_t*>(map)[base + i];
-        k = dtype == WM2F_F32 ? key_of<WM2F_F32>(raw) : key_of<WM2F_I32>(raw);
+        k = dtype == WM2F_F32 ? map_id<WM2F_F32>(raw) : map_id<WM2F_I32>(raw);
       }
       if (k >= 0 && k < N && source[((row0 + rr) / H) * N + k] == 0) {
         out_id = k;
@@ -261,7 +243,7 @@ __global__ __launch_bounds__(kNrThreads) void cell_counts_kernel(const void* __r
                                                                 int32_t* __restrict__ counts, int H, int W, int N, int G,
                                                                 int cell_h, int cell_w, int off_y, int off_x, int GH,
                                                                 int GW, int TR, int TC) {
-  using E = typename std::conditional<DT == WM2F_U8, uint8_t, uint32_t>::type;
+  using E = typename MapElem<DT>::type;
   extern __shared__ __align__(16) unsigned char cellmem[];
   int* acc = reinterpret_cast<int*>(cellmem);
   const int cols = 2 * G, nacc = TR * TC * cols;
@@ -283,7 +265,7 @@ __global__ __launch_bounds__(kNrThreads) void cell_counts_kernel(const void* __r
   for (int idx = tid; idx < total; idx += kNrThreads) {
     const int yy = idx / rw, y = py0 + yy, x = px0 + idx - yy * rw;
     const int64_t p = (int64_t)y * W + x;
-    const int k = key_of<DT>((uint32_t)src[p]);
+    const int k = map_id<DT>((uint32_t)src[p]);
     if (k < 0 || k >= N) continue;
     const int gc = sgrp[k];
     if (gc >= G) continue;
@@ -299,16 +281,7 @@ __global__ __launch_bounds__(kNrThreads) void cell_counts_kernel(const void* __r
   }
 }
 
-int nearest_chunk_rows(int B, int H, int W) {
-  const int col_blocks = ceil_div(W, kNrThreads);
-  const int want = ceil_div(kNrTargetWaves, B * col_blocks * kNrWaves);
-  int chunk_rows = ceil_div(H, want);
-  chunk_rows = chunk_rows < kNrMinChunkRows ? kNrMinChunkRows : chunk_rows;
-  return chunk_rows > H ? H : chunk_rows;
-}
-
-// g first, the ids after it at a 16-byte boundary
-int64_t nearest_g_bytes(int B, int H, int W) { return ((int64_t)B * H * W * 2 + 15) / 16 * 16; }
+static_assert(kNrThreads == kMapColumnThreads, "column_chunk_rows sizes the grid of the columns pass");
 
 int isqrt_floor(int v) {
   int r = 0;
@@ -322,8 +295,8 @@ int isqrt_floor(int v) {
 using namespace wm2f;
 
 extern "C" int64_t wm2f_labelmap_nearest_workspace(int B, int H, int W) {
-  if (B <= 0 || H <= 0 || W <= 0 || H > kNrMaxSide || W > kNrMaxSide || B > kNrMaxBatch) return -1;
-  return nearest_g_bytes(B, H, W) + (int64_t)B * H * W * 4;
+  if (B <= 0 || H <= 0 || W <= 0 || H > kMapMaxSide || W > kMapMaxSide || B > kMapMaxBatch) return -1;
+  return map_g_bytes(B, H, W) + (int64_t)B * H * W * 4;
 }
 
 extern "C" int wm2f_labelmap_nearest(const void* map, int dtype, const uint8_t* source, int32_t* nearest, int32_t* d2,
@@ -332,26 +305,24 @@ extern "C" int wm2f_labelmap_nearest(const void* map, int dtype, const uint8_t* 
   WM2F_REQUIRE(B > 0 && H > 0 && W > 0 && N > 0, "%s: bad size", who);
   WM2F_REQUIRE(max_d2 >= 0, "%s: max_d2 must not be negative (got %d)", who, max_d2);
   WM2F_REQUIRE((flags & ~(WM2F_NEAREST_BLOCKED | WM2F_NEAREST_WALK_ALL)) == 0, "%s: unknown flags %d", who, flags);
-  if (H > kNrMaxSide || W > kNrMaxSide || B > kNrMaxBatch || N > kNrMaxIds || max_d2 > WM2F_NEAREST_MAX_D2) {
-    set_error("%s: sides <= %d, B <= %d, N <= %d, max_d2 <= %d (got %d x %d, %d, %d, %d)", who, kNrMaxSide, kNrMaxBatch,
-              kNrMaxIds, WM2F_NEAREST_MAX_D2, H, W, B, N, max_d2);
+  if (H > kMapMaxSide || W > kMapMaxSide || B > kMapMaxBatch || N > kMapMaxIds || max_d2 > WM2F_NEAREST_MAX_D2) {
+    set_error("%s: sides <= %d, B <= %d, N <= %d, max_d2 <= %d (got %d x %d, %d, %d, %d)", who, kMapMaxSide, kMapMaxBatch,
+              kMapMaxIds, WM2F_NEAREST_MAX_D2, H, W, B, N, max_d2);
     return WM2F_EUNSUPPORTED;
   }
   WM2F_REQUIRE(map && nearest && d2 && workspace, "%s: null pointer", who);
-  WM2F_REQUIRE(dtype == WM2F_F32 || dtype == WM2F_I32 || dtype == WM2F_U8, "%s: map must be fp32, int32 or uint8", who);
+  WM2F_REQUIRE_MAP_DTYPE(dtype, who);
   WM2F_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "%s: the workspace must be 16-byte aligned", who);
   hipStream_t s = (hipStream_t)stream;
   uint16_t* g = reinterpret_cast<uint16_t*>(workspace);
-  int32_t* gid = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(workspace) + nearest_g_bytes(B, H, W));
+  int32_t* gid = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(workspace) + map_g_bytes(B, H, W));
   const int r = isqrt_floor(max_d2);
-  const int chunk_rows = nearest_chunk_rows(B, H, W);
+  const int chunk_rows = column_chunk_rows(B, H, W, kNrMinChunkRows);
   const dim3 cgrid(ceil_div(W, kNrThreads), ceil_div(H, chunk_rows), B);
-  if (dtype == WM2F_F32)
-    hipLaunchKernelGGL((nearest_cols_kernel<WM2F_F32>), cgrid, dim3(kNrThreads), 0, s, map, source, g, gid, H, W, N, chunk_rows, r);
-  else if (dtype == WM2F_I32)
-    hipLaunchKernelGGL((nearest_cols_kernel<WM2F_I32>), cgrid, dim3(kNrThreads), 0, s, map, source, g, gid, H, W, N, chunk_rows, r);
-  else
-    hipLaunchKernelGGL((nearest_cols_kernel<WM2F_U8>), cgrid, dim3(kNrThreads), 0, s, map, source, g, gid, H, W, N, chunk_rows, r);
+  for_map_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(nearest_cols_kernel<decltype(dt)::value>, cgrid, dim3(kNrThreads), 0, s, map, source, g, gid, H, W, N,
+                       chunk_rows, r);
+  });
   WM2F_CHECK_LAUNCH(who);
 
   const int64_t rows = (int64_t)B * H;
@@ -362,20 +333,18 @@ extern "C" int wm2f_labelmap_nearest(const void* map, int dtype, const uint8_t* 
   const int blocked = (flags & WM2F_NEAREST_BLOCKED) != 0 && source != nullptr;  // without a list every instance is a source
   const int walk_all = (flags & WM2F_NEAREST_WALK_ALL) != 0;
   const dim3 rgrid((unsigned)ceil_div64(rows, rpb));
-#define WM2F_NR_ROWS(VEC)                                                                                            \
-  do {                                                                                                               \
-    auto kfn = nearest_rows_kernel<VEC>;                                                                             \
-    if (lds > 64 * 1024 &&                                                                                           \
-        hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { \
-      set_error("%s: cannot reserve %zu bytes of LDS", who, lds);                                                    \
-      return WM2F_ELAUNCH;                                                                                           \
-    }                                                                                                                \
-    hipLaunchKernelGGL(kfn, rgrid, dim3(threads), lds, s, map, dtype, source, g, gid, nearest, d2, rows, H, W, N, rpb, \
-                       r, max_d2, blocked, walk_all);                                                                \
-  } while (0)
-  if (W % 4 == 0) WM2F_NR_ROWS(true);
-  else WM2F_NR_ROWS(false);
-#undef WM2F_NR_ROWS
+  const auto launch_rows = [&](auto kfn) {
+    if (lds > 64 * 1024 &&
+        hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+      set_error("%s: cannot reserve %zu bytes of LDS", who, lds);
+      return WM2F_ELAUNCH;
+    }
+    hipLaunchKernelGGL(kfn, rgrid, dim3(threads), lds, s, map, dtype, source, g, gid, nearest, d2, rows, H, W, N, rpb, r,
+                       max_d2, blocked, walk_all);
+    return WM2F_OK;
+  };
+  const int rc = W % 4 == 0 ? launch_rows(nearest_rows_kernel<true>) : launch_rows(nearest_rows_kernel<false>);
+  if (rc != WM2F_OK) return rc;
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;
 }
@@ -389,13 +358,13 @@ extern "C" int wm2f_labelmap_cell_counts(const void* map, int dtype, const uint8
   WM2F_REQUIRE(off_y >= 0 && off_y < cell_h && off_x >= 0 && off_x < cell_w, "%s: 0 <= offset < cell (got %d, %d in %d x %d)",
                who, off_y, off_x, cell_h, cell_w);
   WM2F_REQUIRE(veto_max >= 0, "%s: veto_max must not be negative (got %d)", who, veto_max);
-  if (H > kNrMaxSide || W > kNrMaxSide || cell_h > kNrMaxSide || cell_w > kNrMaxSide || B > kNrMaxBatch || N > kNrMaxIds) {
-    set_error("%s: sides and cells <= %d, B <= %d, N <= %d (got %d x %d, cells %d x %d, %d, %d)", who, kNrMaxSide,
-              kNrMaxBatch, kNrMaxIds, H, W, cell_h, cell_w, B, N);
+  if (H > kMapMaxSide || W > kMapMaxSide || cell_h > kMapMaxSide || cell_w > kMapMaxSide || B > kMapMaxBatch || N > kMapMaxIds) {
+    set_error("%s: sides and cells <= %d, B <= %d, N <= %d (got %d x %d, cells %d x %d, %d, %d)", who, kMapMaxSide,
+              kMapMaxBatch, kMapMaxIds, H, W, cell_h, cell_w, B, N);
     return WM2F_EUNSUPPORTED;
   }
   WM2F_REQUIRE(map && group && counts, "%s: null pointer", who);
-  WM2F_REQUIRE(dtype == WM2F_F32 || dtype == WM2F_I32 || dtype == WM2F_U8, "%s: map must be fp32, int32 or uint8", who);
+  WM2F_REQUIRE_MAP_DTYPE(dtype, who);
   hipStream_t s = (hipStream_t)stream;
   const int GH = ceil_div(H + off_y, cell_h), GW = ceil_div(W + off_x, cell_w);
   int TC = ceil_div(kCellPixelsX, cell_w);
@@ -406,13 +375,10 @@ extern "C" int wm2f_labelmap_cell_counts(const void* map, int dtype, const uint8
   const dim3 grid(ceil_div(GW, TC), ceil_div(GH, TR), B);
   WM2F_REQUIRE(grid.y <= 65535u, "%s: too many tiles", who);  // at most 16384 rows of cells
   const size_t lds = (size_t)TR * TC * 2 * G * sizeof(int) + (size_t)N;
-#define WM2F_CELLS(DT)                                                                                                 \
-  hipLaunchKernelGGL((cell_counts_kernel<DT>), grid, dim3(kNrThreads), lds, s, map, group, veto_d2, veto_max, counts, H, \
-                     W, N, G, cell_h, cell_w, off_y, off_x, GH, GW, TR, TC)
-  if (dtype == WM2F_F32) WM2F_CELLS(WM2F_F32);
-  else if (dtype == WM2F_I32) WM2F_CELLS(WM2F_I32);
-  else WM2F_CELLS(WM2F_U8);
-#undef WM2F_CELLS
+  for_map_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(cell_counts_kernel<decltype(dt)::value>, grid, dim3(kNrThreads), lds, s, map, group, veto_d2,
+                       veto_max, counts, H, W, N, G, cell_h, cell_w, off_y, off_x, GH, GW, TR, TC);
+  });
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;
 }

@@ -14,9 +14,7 @@
 //                on its pixels.  Otherwise it walks the diamond of each pixel and keeps the candidate of greatest
 //                order.  Then fill or contour colour, 12 bytes out.
 // Everything is integer, nothing is accumulated: bit-identical from run to run.
-#include <type_traits>
-
-#include "common.h"
+#include "labelmap.h"
 
 namespace wm2f {
 namespace {
@@ -31,29 +29,16 @@ constexpr int kOvRows = kOvTileH + 2 * kOvMaxR;         // 40 rows: 10880 B of e
 constexpr int kOvRowQuads = kOvStride / 4;              // 34
 constexpr int kOvQuads = kOvTileW / 4 * kOvTileH / kOvThreads;  // 4 quads per lane
 constexpr int kOvLdsMaxIds = 1024;                      // 12 B per entry: 12 KiB, with the tile six workgroups per CU
-constexpr int kOvMaxSide = 16384;
-constexpr int kOvMaxBatch = 32;
-constexpr int kOvMaxIds = 4096;
-constexpr int kOvNone = -1;
+constexpr int kOvNone = -1;                             // what list_row gives for a value that is not listed
 constexpr int kOvOutside = -2;
-static_assert(kOvMaxIds <= 32767, "entries are stored as int16");
+static_assert(kMapMaxIds <= 32767, "entries are stored as int16");
 static_assert(kOvQuads * kOvThreads * 4 == kOvTileW * kOvTileH, "tile / thread mapping");
 
 // entry of a raw map value in the image's ascending id list (n of them), kOvNone when it is not listed
 template <int DT>
 __device__ __forceinline__ int entry_of(uint32_t raw, const int32_t* ids, int n) {
   int v;
-  if (DT == WM2F_F32) {
-    if (!f32_bits_to_int(raw, v)) return kOvNone;
-  } else {
-    v = (int)raw;  // int32 as it is; a uint8 arrives zero-extended
-  }
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (ids[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  return (lo < n && ids[lo] == v) ? lo : kOvNone;
+  return map_int<DT>(raw, v) ? list_row(v, ids, n) : kOvNone;
 }
 
 __device__ __forceinline__ uint32_t blend8(uint32_t img, uint32_t col, uint32_t a) {
@@ -69,7 +54,7 @@ __global__ __launch_bounds__(kOvThreads) void overlay_kernel(const uint8_t* __re
                                                              const int32_t* __restrict__ order, uint32_t def_rgba,
                                                              int inner, int outer, uint8_t* __restrict__ out, int H,
                                                              int W, int N, int vec) {
-  using E = typename std::conditional<DT == WM2F_U8, uint8_t, uint32_t>::type;
+  using E = typename MapElem<DT>::type;
   __shared__ __align__(16) int16_t tile[kOvRows * kOvStride];
   __shared__ int32_t tab[kLds ? 3 * kOvLdsMaxIds : 1];
   const int tid = threadIdx.x, b = blockIdx.z;
@@ -132,17 +117,7 @@ __global__ __launch_bounds__(kOvThreads) void overlay_kernel(const uint8_t* __re
 #pragma unroll
       for (int j = 0; j < 4; ++j) in[j] = gx + j >= 0 && gx + j < W;
       if (vec) {  // gx and W are multiples of 4: the quad is inside as a whole
-        if (DT == WM2F_U8) {
-          const uint32_t w4 = *reinterpret_cast<const uint32_t*>(p);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) raw[j] = (w4 >> (8 * j)) & 0xffu;
-        } else {
-          const uint4 v4 = *reinterpret_cast<const uint4*>(p);
-          raw[0] = v4.x;
-          raw[1] = v4.y;
-          raw[2] = v4.z;
-          raw[3] = v4.w;
-        }
+        load_map4<DT>(p, raw);
       } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -282,12 +257,12 @@ extern "C" int wm2f_labelmap_overlay(const uint8_t* image, const void* map, int 
   WM2F_REQUIRE(image && map && out, "%s: null pointer", who);
   WM2F_REQUIRE(B > 0 && H > 0 && W > 0 && N >= 0, "%s: bad size", who);
   WM2F_REQUIRE(N == 0 || (ids && n_ids && rgba && order), "%s: N > 0 needs ids, n_ids, rgba and order", who);
-  WM2F_REQUIRE(dtype == WM2F_F32 || dtype == WM2F_I32 || dtype == WM2F_U8, "%s: map must be fp32, int32 or uint8", who);
+  WM2F_REQUIRE_MAP_DTYPE(dtype, who);
   WM2F_REQUIRE(inner >= 0 && inner <= kOvMaxR && outer >= 0 && outer <= kOvMaxR, "%s: 0 <= inner, outer <= %d", who,
                kOvMaxR);
   WM2F_REQUIRE(reinterpret_cast<uintptr_t>(rgba) % 4 == 0, "%s: rgba must be 4-byte aligned", who);
-  if (H > kOvMaxSide || W > kOvMaxSide || B > kOvMaxBatch || N > kOvMaxIds) {
-    set_error("%s: sides <= %d, B <= %d, N <= %d (got %d x %d, %d, %d)", who, kOvMaxSide, kOvMaxBatch, kOvMaxIds, H, W,
+  if (H > kMapMaxSide || W > kMapMaxSide || B > kMapMaxBatch || N > kMapMaxIds) {
+    set_error("%s: sides <= %d, B <= %d, N <= %d (got %d x %d, %d, %d)", who, kMapMaxSide, kMapMaxBatch, kMapMaxIds, H, W,
               B, N);
     return WM2F_EUNSUPPORTED;
   }
@@ -296,23 +271,18 @@ extern "C" int wm2f_labelmap_overlay(const uint8_t* image, const void* map, int 
   WM2F_REQUIRE(oa + (uintptr_t)bytes <= ia || ia + (uintptr_t)bytes <= oa,
                "%s: out must not overlap image (neighbours are read)", who);
   hipStream_t s = (hipStream_t)stream;
-  const size_t esz = dtype == WM2F_U8 ? 1 : 4;
-  const int vec = W % 4 == 0 && reinterpret_cast<uintptr_t>(map) % (esz * 4) == 0 && ia % 4 == 0 && oa % 4 == 0;
+  const int vec = map_vec4_ok(map, dtype, W) && ia % 4 == 0 && oa % 4 == 0;
   const dim3 grid(ceil_div(W, kOvTileW), ceil_div(H, kOvTileH), B);
   const uint32_t* col = reinterpret_cast<const uint32_t*>(rgba);
-#define WM2F_OV_LAUNCH(DT, LDS)                                                                                      \
-  hipLaunchKernelGGL((overlay_kernel<DT, LDS>), grid, dim3(kOvThreads), 0, s, image, map, ids, n_ids, col, order, \
-                     default_rgba, inner, outer, out, H, W, N, vec)
-#define WM2F_OV_DTYPE(DT)                        \
-  do {                                           \
-    if (N <= kOvLdsMaxIds) WM2F_OV_LAUNCH(DT, true); \
-    else WM2F_OV_LAUNCH(DT, false);              \
-  } while (0)
-  if (dtype == WM2F_F32) WM2F_OV_DTYPE(WM2F_F32);
-  else if (dtype == WM2F_I32) WM2F_OV_DTYPE(WM2F_I32);
-  else WM2F_OV_DTYPE(WM2F_U8);
-#undef WM2F_OV_DTYPE
-#undef WM2F_OV_LAUNCH
+  for_map_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    const auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, dim3(kOvThreads), 0, s, image, map, ids, n_ids, col, order, default_rgba, inner, outer,
+                         out, H, W, N, vec);
+    };
+    if (N <= kOvLdsMaxIds) launch(overlay_kernel<DT, true>);
+    else launch(overlay_kernel<DT, false>);
+  });
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;
 }

@@ -17,7 +17,7 @@
 // Everything is integer but the one division per matched pair, so both results are bit-identical from run to run.
 #include <type_traits>
 
-#include "common.h"
+#include "labelmap.h"
 
 namespace wm2f {
 namespace {
@@ -206,11 +206,7 @@ __global__ __launch_bounds__(kScThreads) void semantic_confusion_kernel(const PT
       if (ok[j]) {
         int g = (int)gv[j];
         if (ids != nullptr) {
-          int lo = 0, hi = ng;
-          while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (s_ids[mid] < g) lo = mid + 1; else hi = mid;
-          }
+          const int lo = list_lower_bound(g, s_ids, ng);
           g = (lo < ng && s_ids[lo] == g) ? s_cls[lo] : background_label;
         }
         if (g >= 0 && g < C && g != ignore_index) {
@@ -248,18 +244,18 @@ __global__ __launch_bounds__(kScThreads) void semantic_confusion_kernel(const PT
 }
 
 template <typename PT, typename GT>
-void launch_confusion(bool vec, bool lds, dim3 grid, size_t shm, hipStream_t s, const void* pred, const void* gt,
+void launch_confusion(bool vec, bool lds, dim3 grid, size_t shm, hipStream_t s, const PT* pred, const GT* gt,
                       const int32_t* ids, const int32_t* cls, const int32_t* n_ids, unsigned long long* conf,
                       unsigned long long* n_out, int64_t n, int G, int C, int ignore_index, int background_label,
                       int64_t chunk) {
-#define WM2F_SC_LAUNCH(VEC, LDS)                                                                                       \
-  hipLaunchKernelGGL((semantic_confusion_kernel<PT, GT, VEC, LDS>), grid, dim3(kScThreads), shm, s, (const PT*)pred,   \
-                     (const GT*)gt, ids, cls, n_ids, conf, n_out, n, G, C, ignore_index, background_label, chunk)
-  if (vec && lds) WM2F_SC_LAUNCH(true, true);
-  else if (vec) WM2F_SC_LAUNCH(true, false);
-  else if (lds) WM2F_SC_LAUNCH(false, true);
-  else WM2F_SC_LAUNCH(false, false);
-#undef WM2F_SC_LAUNCH
+  const auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(kScThreads), shm, s, pred, gt, ids, cls, n_ids, conf, n_out, n, G, C, ignore_index,
+                       background_label, chunk);
+  };
+  if (vec && lds) launch(semantic_confusion_kernel<PT, GT, true, true>);
+  else if (vec) launch(semantic_confusion_kernel<PT, GT, true, false>);
+  else if (lds) launch(semantic_confusion_kernel<PT, GT, false, true>);
+  else launch(semantic_confusion_kernel<PT, GT, false, false>);
 }
 
 }  // namespace
@@ -320,19 +316,17 @@ extern "C" int wm2f_semantic_confusion(const void* pred, int pred_dtype, const v
   hipStream_t s = (hipStream_t)stream;
   unsigned long long* cf = reinterpret_cast<unsigned long long*>(conf);
   unsigned long long* no = reinterpret_cast<unsigned long long*>(n_out_of_range);
-#define WM2F_SC_TYPES(PT, GT_)                                                                                        \
-  launch_confusion<PT, GT_>(vec, lds, grid, shm, s, pred, gt, gt_ids, gt_cls, n_ids, cf, no, n_pixels, G, C, ignore_index, \
-                            background_label, chunk)
-  if (gt_dtype == WM2F_U8) {
-    if (pred_dtype == WM2F_I64) WM2F_SC_TYPES(int64_t, uint8_t);
-    else if (pred_dtype == WM2F_I32) WM2F_SC_TYPES(int32_t, uint8_t);
-    else WM2F_SC_TYPES(uint8_t, uint8_t);
-  } else {
-    if (pred_dtype == WM2F_I64) WM2F_SC_TYPES(int64_t, int32_t);
-    else if (pred_dtype == WM2F_I32) WM2F_SC_TYPES(int32_t, int32_t);
-    else WM2F_SC_TYPES(uint8_t, int32_t);
-  }
-#undef WM2F_SC_TYPES
+  const auto with_gt = [&](auto* p) {  // p: pred as the type it holds
+    if (gt_dtype == WM2F_U8)
+      launch_confusion(vec, lds, grid, shm, s, p, (const uint8_t*)gt, gt_ids, gt_cls, n_ids, cf, no, n_pixels, G, C,
+                       ignore_index, background_label, chunk);
+    else
+      launch_confusion(vec, lds, grid, shm, s, p, (const int32_t*)gt, gt_ids, gt_cls, n_ids, cf, no, n_pixels, G, C,
+                       ignore_index, background_label, chunk);
+  };
+  if (pred_dtype == WM2F_I64) with_gt((const int64_t*)pred);
+  else if (pred_dtype == WM2F_I32) with_gt((const int32_t*)pred);
+  else with_gt((const uint8_t*)pred);
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;
 }

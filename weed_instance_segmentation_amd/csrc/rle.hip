@@ -26,15 +26,11 @@
 //                          scan order to the run's index + 1 (atomicMax: the later run wins whatever the schedule),
 //                          rle_resolve_kernel writes values[rank - 1] where a rank was set.  Both return at once when the
 //                          status word is set, so a refused call stores nothing into the map.
-#include <type_traits>
-
-#include "common.h"
+#include "labelmap.h"
 
 namespace wm2f {
 namespace {
 
-constexpr int kRleMaxSide = 16384;
-constexpr int kRleMaxBatch = 32;
 constexpr int kRleMinGroup = 2048;   // positions of an order-0 group, at least
 constexpr int kRleMaxGroups = 1024;  // order-0 groups per image, at most
 constexpr int kRleUnroll = 8;
@@ -43,17 +39,13 @@ constexpr int kRleOut = -2;   // a value outside [-1, N)
 constexpr int kScanThreads = 256;
 constexpr int kPaintThreads = 256;
 
+// slot of a map value: 0 for the background, id + 1 for an id in [0, N), kRleOut for everything else
 template <int DT>
 __device__ __forceinline__ int slot_of(uint32_t raw, int N) {
+  if (map_is_background<DT>(raw)) return 0;
   int v;
-  if (DT == WM2F_F32) {
-    if (raw == 0xbf800000u) return 0;  // -1.0f
-    if (!f32_bits_to_int(raw, v)) return kRleOut;
-  } else {
-    v = (int)raw;  // int32 as it is; a uint8 arrives zero-extended
-    if (v == -1) return 0;
-  }
-  return (v >= 0 && v < N) ? v + 1 : kRleOut;
+  if (!map_int<DT>(raw, v)) return kRleOut;
+  return (v >= 0 && v < N) ? v + 1 : kRleOut;  // map_id_or_code's ids, one up
 }
 
 // rows of an order-0 group
@@ -75,7 +67,7 @@ __global__ __launch_bounds__(kWave) void rle_rows_kernel(const void* __restrict_
                                                          int32_t* __restrict__ out_of_range,
                                                          const int32_t* __restrict__ offsets, int32_t* __restrict__ out,
                                                          int H, int W, int N, int rows) {
-  using E = typename std::conditional<DT == WM2F_U8, uint8_t, uint32_t>::type;
+  using E = typename MapElem<DT>::type;
   extern __shared__ int32_t cursor[];  // N + 1: the group's count (count launch) or next rank (write launch) per slot
   const int lane = threadIdx.x, g = blockIdx.x, b = blockIdx.y, N1 = N + 1;
   const int HW = H * W;  // <= 2^28
@@ -142,7 +134,7 @@ __global__ __launch_bounds__(kWave) void rle_cols_kernel(const void* __restrict_
                                                          int32_t* __restrict__ out_of_range,
                                                          const int32_t* __restrict__ offsets, int32_t* __restrict__ out,
                                                          int H, int W, int N) {
-  using E = typename std::conditional<DT == WM2F_U8, uint8_t, uint32_t>::type;
+  using E = typename MapElem<DT>::type;
   const int x = blockIdx.x * kWave + threadIdx.x, b = blockIdx.y, N1 = N + 1;
   if (x >= W) return;
   const int HW = H * W;
@@ -237,8 +229,8 @@ __global__ __launch_bounds__(kPaintThreads) void rle_resolve_kernel(const int32_
 int check_sizes(const char* who, int B, int H, int W, int N, int order) {
   WM2F_REQUIRE(B > 0 && H > 0 && W > 0 && N >= 0, "%s: bad size", who);
   WM2F_REQUIRE(order == 0 || order == 1, "%s: order must be 0 (row-major) or 1 (column-major), got %d", who, order);
-  if (H > kRleMaxSide || W > kRleMaxSide || B > kRleMaxBatch || N > WM2F_RLE_MAX_IDS) {
-    set_error("%s: sides <= %d, B <= %d, N <= %d (got %d x %d, %d, %d)", who, kRleMaxSide, kRleMaxBatch, WM2F_RLE_MAX_IDS,
+  if (H > kMapMaxSide || W > kMapMaxSide || B > kMapMaxBatch || N > WM2F_RLE_MAX_IDS) {
+    set_error("%s: sides <= %d, B <= %d, N <= %d (got %d x %d, %d, %d)", who, kMapMaxSide, kMapMaxBatch, WM2F_RLE_MAX_IDS,
               H, W, B, N);
     return WM2F_EUNSUPPORTED;
   }
@@ -249,19 +241,15 @@ template <bool kWrite>
 void launch_walk(const void* map, int dtype, int32_t* table, int32_t* out_of_range, const int32_t* offsets, int32_t* out,
                  int B, int H, int W, int N, int order, hipStream_t s) {
   const size_t shm = (size_t)(N + 1) * sizeof(int32_t);
-#define WM2F_RLE_WALK(DT)                                                                                               \
-  do {                                                                                                                  \
-    if (order == 0)                                                                                                     \
-      hipLaunchKernelGGL((rle_rows_kernel<DT, kWrite>), dim3(rle_groups(H, W, 0), B), dim3(kWave), shm, s, map, table,  \
-                         out_of_range, offsets, out, H, W, N, rle_group_rows(H, W));                                    \
-    else                                                                                                                \
-      hipLaunchKernelGGL((rle_cols_kernel<DT, kWrite>), dim3(ceil_div(W, kWave), B), dim3(kWave), 0, s, map, table,     \
-                         out_of_range, offsets, out, H, W, N);                                                          \
-  } while (0)
-  if (dtype == WM2F_F32) WM2F_RLE_WALK(WM2F_F32);
-  else if (dtype == WM2F_I32) WM2F_RLE_WALK(WM2F_I32);
-  else WM2F_RLE_WALK(WM2F_U8);
-#undef WM2F_RLE_WALK
+  for_map_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    if (order == 0)
+      hipLaunchKernelGGL((rle_rows_kernel<DT, kWrite>), dim3(rle_groups(H, W, 0), B), dim3(kWave), shm, s, map, table,
+                         out_of_range, offsets, out, H, W, N, rle_group_rows(H, W));
+    else
+      hipLaunchKernelGGL((rle_cols_kernel<DT, kWrite>), dim3(ceil_div(W, kWave), B), dim3(kWave), 0, s, map, table,
+                         out_of_range, offsets, out, H, W, N);
+  });
 }
 
 }  // namespace
@@ -270,7 +258,7 @@ void launch_walk(const void* map, int dtype, int32_t* table, int32_t* out_of_ran
 using namespace wm2f;
 
 extern "C" int64_t wm2f_rle_workspace(int B, int H, int W, int N, int order) {
-  if (B <= 0 || H <= 0 || W <= 0 || N < 0 || H > kRleMaxSide || W > kRleMaxSide || B > kRleMaxBatch ||
+  if (B <= 0 || H <= 0 || W <= 0 || N < 0 || H > kMapMaxSide || W > kMapMaxSide || B > kMapMaxBatch ||
       N > WM2F_RLE_MAX_IDS || (order != 0 && order != 1))
     return -1;
   return (int64_t)B * rle_groups(H, W, order) * (N + 1) * (int64_t)sizeof(int32_t);
@@ -280,7 +268,7 @@ extern "C" int wm2f_labelmap_toggle_counts(const void* map, int dtype, int32_t* 
                                            void* workspace, int B, int H, int W, int N, int order, void* stream) {
   const char* who = "wm2f_labelmap_toggle_counts";
   WM2F_REQUIRE(map && counts && out_of_range && workspace, "%s: null pointer", who);
-  WM2F_REQUIRE(dtype == WM2F_F32 || dtype == WM2F_I32 || dtype == WM2F_U8, "%s: map must be fp32, int32 or uint8", who);
+  WM2F_REQUIRE_MAP_DTYPE(dtype, who);
   if (const int rc = check_sizes(who, B, H, W, N, order)) return rc;
   hipStream_t s = (hipStream_t)stream;
   int32_t* table = (int32_t*)workspace;
@@ -300,7 +288,7 @@ extern "C" int wm2f_labelmap_toggles(const void* map, int dtype, const int32_t* 
                                      void* workspace, int B, int H, int W, int N, int order, void* stream) {
   const char* who = "wm2f_labelmap_toggles";
   WM2F_REQUIRE(map && offsets && positions && workspace, "%s: null pointer", who);
-  WM2F_REQUIRE(dtype == WM2F_F32 || dtype == WM2F_I32 || dtype == WM2F_U8, "%s: map must be fp32, int32 or uint8", who);
+  WM2F_REQUIRE_MAP_DTYPE(dtype, who);
   if (const int rc = check_sizes(who, B, H, W, N, order)) return rc;
   launch_walk<true>(map, dtype, (int32_t*)workspace, nullptr, offsets, positions, B, H, W, N, order, (hipStream_t)stream);
   WM2F_CHECK_LAUNCH(who);
@@ -308,7 +296,7 @@ extern "C" int wm2f_labelmap_toggles(const void* map, int dtype, const int32_t* 
 }
 
 extern "C" int64_t wm2f_rle_paint_workspace(int B, int H, int W) {
-  if (B <= 0 || H <= 0 || W <= 0 || H > kRleMaxSide || W > kRleMaxSide || B > kRleMaxBatch) return -1;
+  if (B <= 0 || H <= 0 || W <= 0 || H > kMapMaxSide || W > kMapMaxSide || B > kMapMaxBatch) return -1;
   return (int64_t)B * H * W * (int64_t)sizeof(int32_t);
 }
 

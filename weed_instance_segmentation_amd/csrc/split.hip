@@ -22,17 +22,12 @@
 //   split_assign   the extra groups' ids in raster order of their peaks, and their info rows
 //   split_paint    out[p]
 // Everything is integer; the atomics are max and add on integers, so no result depends on an order.
-#include <type_traits>
-
-#include "common.h"
+#include "labelmap.h"
 
 namespace wm2f {
 namespace {
 
 constexpr int kSpThreads = 256;
-constexpr int kSpMaxSide = 16384;
-constexpr int kSpMaxBatch = 32;
-constexpr int kSpMaxIds = 4096;
 constexpr int kSpMaxRounds = 32;
 constexpr int kSpMaxDen = 1024;
 constexpr int kSpChunk = 4 * kSpThreads;  // pixels per workgroup of the numbering passes
@@ -79,18 +74,6 @@ __host__ inline SpWs sp_carve(void* ws, int B, int H, int W, int M) {
   return w;
 }
 
-// the id of a raw map value in [0, N), -1 for everything else (wm2f_labelmap_clean's rule)
-template <int DT>
-__device__ __forceinline__ int sp_id_of(uint32_t raw, int N) {
-  int v;
-  if (DT == WM2F_F32) {
-    if (!f32_bits_to_int(raw, v)) return -1;
-  } else {
-    v = (int)raw;  // int32 as it is; a uint8 arrives zero-extended
-  }
-  return (v >= 0 && v < N) ? v : -1;
-}
-
 __device__ __forceinline__ unsigned long long sp_key(int d2, int lin) {
   return ((unsigned long long)(uint32_t)d2 << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)lin);
 }
@@ -125,7 +108,7 @@ template <int DT>
 __global__ __launch_bounds__(kSpThreads) void split_ascent_kernel(const void* __restrict__ map,
                                                                   const int32_t* __restrict__ d2, SpWs ws, int H, int W,
                                                                   int N) {
-  using E = typename std::conditional<DT == WM2F_U8, uint8_t, uint32_t>::type;
+  using E = typename MapElem<DT>::type;
   const int n_px = H * W;
   const int p = blockIdx.x * kSpThreads + threadIdx.x;
   const int64_t img = (int64_t)blockIdx.y * n_px;
@@ -133,7 +116,7 @@ __global__ __launch_bounds__(kSpThreads) void split_ascent_kernel(const void* __
   if (p < n_px) {
     const E* src = reinterpret_cast<const E*>(map) + img;
     const int32_t* dd = d2 + img;
-    const int k = sp_id_of<DT>((uint32_t)src[p], N);
+    const int k = map_id_below<DT>((uint32_t)src[p], N);
     int up = p;
     if (k >= 0) {
       const int y = p / W, x = p - y * W;
@@ -146,7 +129,7 @@ __global__ __launch_bounds__(kSpThreads) void split_ascent_kernel(const void* __
           const int yy = y + dy, xx = x + dx;
           if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
           const int q = yy * W + xx;
-          if (sp_id_of<DT>((uint32_t)src[q], N) != k) continue;
+          if (map_id_below<DT>((uint32_t)src[q], N) != k) continue;
           const unsigned long long kq = sp_key(dd[q], q);
           if (kq > top) {
             top = kq;
@@ -362,7 +345,7 @@ __global__ __launch_bounds__(kSpThreads) void split_paint_kernel(SpWs ws, int32_
 }
 
 bool sp_size_ok(int B, int H, int W, int N, int M) {
-  return H <= kSpMaxSide && W <= kSpMaxSide && B <= kSpMaxBatch && N <= M && M <= kSpMaxIds;
+  return H <= kMapMaxSide && W <= kMapMaxSide && B <= kMapMaxBatch && N <= M && M <= kMapMaxIds;
 }
 
 }  // namespace
@@ -381,7 +364,7 @@ extern "C" int wm2f_labelmap_split(const void* map, int dtype, const int32_t* d2
   const char* who = "wm2f_labelmap_split";
   WM2F_REQUIRE(B > 0 && H > 0 && W > 0 && N >= 0 && M >= 0, "%s: bad size", who);
   if (!sp_size_ok(B, H, W, N, M)) {
-    set_error("%s: sides <= %d, B <= %d, N <= M <= %d (got %d x %d, %d, %d, %d)", who, kSpMaxSide, kSpMaxBatch, kSpMaxIds,
+    set_error("%s: sides <= %d, B <= %d, N <= M <= %d (got %d x %d, %d, %d, %d)", who, kMapMaxSide, kMapMaxBatch, kMapMaxIds,
               H, W, B, N, M);
     return WM2F_EUNSUPPORTED;
   }
@@ -390,13 +373,13 @@ extern "C" int wm2f_labelmap_split(const void* map, int dtype, const int32_t* d2
                who, kSpMaxDen, num, den);
   WM2F_REQUIRE(min_peak_d2 >= 0, "%s: min_peak_d2 must not be negative", who);
   WM2F_REQUIRE(map && d2 && out && status && workspace && (info || M == 0), "%s: null pointer", who);
-  WM2F_REQUIRE(dtype == WM2F_F32 || dtype == WM2F_I32 || dtype == WM2F_U8, "%s: map must be fp32, int32 or uint8", who);
+  WM2F_REQUIRE_MAP_DTYPE(dtype, who);
   WM2F_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0 && reinterpret_cast<uintptr_t>(info) % 16 == 0 &&
                    reinterpret_cast<uintptr_t>(status) % 16 == 0,
                "%s: workspace, info and status must be 16-byte aligned", who);
   const int64_t all_px = (int64_t)B * H * W;
   const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + (uintptr_t)all_px * 4;
-  const uintptr_t m0 = reinterpret_cast<uintptr_t>(map), m1 = m0 + (uintptr_t)all_px * (dtype == WM2F_U8 ? 1 : 4);
+  const uintptr_t m0 = reinterpret_cast<uintptr_t>(map), m1 = m0 + (uintptr_t)all_px * map_elem_bytes(dtype);
   const uintptr_t d0 = reinterpret_cast<uintptr_t>(d2), d1 = d0 + (uintptr_t)all_px * 4;
   WM2F_REQUIRE((o1 <= m0 || m1 <= o0) && (o1 <= d0 || d1 <= o0), "%s: out overlaps map or d2", who);
 
@@ -408,12 +391,9 @@ extern "C" int wm2f_labelmap_split(const void* map, int dtype, const int32_t* d2
   const dim3 chunk_grid((unsigned)chunks, (unsigned)B);
   const int n_init = B * (M > kSpCounters ? M : kSpCounters);
   hipLaunchKernelGGL(split_init_kernel, dim3(ceil_div(n_init, kSpThreads)), dim3(kSpThreads), 0, s, ws, info, B, M);
-  if (dtype == WM2F_F32)
-    hipLaunchKernelGGL(split_ascent_kernel<WM2F_F32>, px_grid, dim3(kSpThreads), 0, s, map, d2, ws, H, W, N);
-  else if (dtype == WM2F_I32)
-    hipLaunchKernelGGL(split_ascent_kernel<WM2F_I32>, px_grid, dim3(kSpThreads), 0, s, map, d2, ws, H, W, N);
-  else
-    hipLaunchKernelGGL(split_ascent_kernel<WM2F_U8>, px_grid, dim3(kSpThreads), 0, s, map, d2, ws, H, W, N);
+  for_map_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(split_ascent_kernel<decltype(dt)::value>, px_grid, dim3(kSpThreads), 0, s, map, d2, ws, H, W, N);
+  });
   hipLaunchKernelGGL(split_flatten_kernel, px_grid, dim3(kSpThreads), 0, s, ws, n_px, 0);
   WM2F_CHECK_LAUNCH(who);
   const long long num2 = (long long)num * num, den2 = (long long)den * den;

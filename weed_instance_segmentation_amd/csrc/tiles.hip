@@ -11,8 +11,8 @@
 //   tile_compose : out = remap[owner tile][local id], one workgroup per strip of rows of one cell.
 // All integer; no float takes part; every result is independent of the schedule.  Every index read from a device table
 // is clamped to the array it addresses before use.
-#include "common.h"
 #include "labelling.h"
+#include "labelmap.h"
 
 namespace wm2f {
 namespace {
@@ -27,16 +27,12 @@ constexpr int kTmPairPixels = 65536;    // pixels of a rectangle per workgroup (
 constexpr int kTmCellPixels = 16384;    // pixels of a cell per workgroup
 constexpr int kTmScanThreads = 1024;
 
-// slot of a map value: 0 "no id", id + 1 for an id in [0, n).  A float is an id by f32_bits_to_int's rule.
+// slot of a map value: 0 "no id", id + 1 for an id in [0, n)
 template <bool kF32>
 __device__ __forceinline__ int tile_slot(uint32_t raw, int n) {
   int v;
-  if (kF32) {
-    if (!f32_bits_to_int(raw, v)) return 0;
-  } else {
-    v = (int)raw;
-  }
-  return (v >= 0 && v < n) ? v + 1 : 0;
+  if (!map_int<kF32 ? WM2F_F32 : WM2F_I32>(raw, v)) return 0;
+  return (v >= 0 && v < n) ? v + 1 : 0;  // map_id_below's ids, one up
 }
 
 __device__ __forceinline__ int clamp_n(int n, int N) { return n < 0 ? 0 : (n > N ? N : n); }
@@ -401,17 +397,13 @@ extern "C" int wm2f_tile_pair_counts(const void* tiles, int dtype, const int32_t
   const bool lds = nb <= kTmLdsBins;
   const size_t shm = lds ? (size_t)nb * sizeof(int32_t) : 0;
   const uint32_t* tp = (const uint32_t*)tiles;
-  if (dtype == WM2F_F32) {
+  for_map_dtype_f32_i32(dtype, [&](auto dt) {
+    constexpr bool kF32 = decltype(dt)::value == WM2F_F32;
     if (lds)
-      hipLaunchKernelGGL((tile_pairs_kernel<true, true>), grid, dim3(kTmThreads), shm, s, tp, n_ids, pairs, hist, T, th, tw, N);
+      hipLaunchKernelGGL((tile_pairs_kernel<kF32, true>), grid, dim3(kTmThreads), shm, s, tp, n_ids, pairs, hist, T, th, tw, N);
     else
-      hipLaunchKernelGGL((tile_pairs_kernel<true, false>), grid, dim3(kTmThreads), shm, s, tp, n_ids, pairs, hist, T, th, tw, N);
-  } else {
-    if (lds)
-      hipLaunchKernelGGL((tile_pairs_kernel<false, true>), grid, dim3(kTmThreads), shm, s, tp, n_ids, pairs, hist, T, th, tw, N);
-    else
-      hipLaunchKernelGGL((tile_pairs_kernel<false, false>), grid, dim3(kTmThreads), shm, s, tp, n_ids, pairs, hist, T, th, tw, N);
-  }
+      hipLaunchKernelGGL((tile_pairs_kernel<kF32, false>), grid, dim3(kTmThreads), shm, s, tp, n_ids, pairs, hist, T, th, tw, N);
+  });
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;
 }
@@ -432,10 +424,10 @@ extern "C" int wm2f_tile_owned_counts(const void* tiles, int dtype, const int32_
   const int rpb = kTmCellPixels / tw > 1 ? kTmCellPixels / tw : 1;
   const dim3 grid(ceil_div(th, rpb), T);
   const uint32_t* tp = (const uint32_t*)tiles;
-  if (dtype == WM2F_F32)
-    hipLaunchKernelGGL((tile_owned_kernel<true>), grid, dim3(kTmThreads), 0, s, tp, n_ids, geom, owned, th, tw, N);
-  else
-    hipLaunchKernelGGL((tile_owned_kernel<false>), grid, dim3(kTmThreads), 0, s, tp, n_ids, geom, owned, th, tw, N);
+  for_map_dtype_f32_i32(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(tile_owned_kernel<decltype(dt)::value == WM2F_F32>, grid, dim3(kTmThreads), 0, s, tp, n_ids, geom,
+                       owned, th, tw, N);
+  });
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;
 }
@@ -487,10 +479,10 @@ extern "C" int wm2f_tile_compose(const void* tiles, int dtype, const int32_t* n_
   const int rpb = kTmCellPixels / tw > 1 ? kTmCellPixels / tw : 1;
   const dim3 grid(ceil_div(th, rpb), T);
   const uint32_t* tp = (const uint32_t*)tiles;
-  if (dtype == WM2F_F32)
-    hipLaunchKernelGGL((tile_compose_kernel<true>), grid, dim3(kTmThreads), 0, s, tp, n_ids, geom, remap, out, th, tw, N, H, W);
-  else
-    hipLaunchKernelGGL((tile_compose_kernel<false>), grid, dim3(kTmThreads), 0, s, tp, n_ids, geom, remap, out, th, tw, N, H, W);
+  for_map_dtype_f32_i32(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(tile_compose_kernel<decltype(dt)::value == WM2F_F32>, grid, dim3(kTmThreads), 0, s, tp, n_ids, geom,
+                       remap, out, th, tw, N, H, W);
+  });
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;
 }

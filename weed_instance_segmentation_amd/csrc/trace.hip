@@ -21,9 +21,7 @@
 //   emit     trace_emit_kernel: a flagged place stores its point at (inclusive flag prefix) - 1.
 // Between them the host layer runs prefix sums over edge-sized arrays and one sort over the loops (ops/trace.py).
 // Every store is guarded by the range of the array it goes to, so a bad table cannot write elsewhere.
-#include <type_traits>
-
-#include "common.h"
+#include "labelmap.h"
 
 namespace wm2f {
 namespace {
@@ -33,31 +31,18 @@ constexpr int kTraceThreads = 256;    // per-edge kernels
 constexpr int kTraceScanThreads = 1024;
 constexpr int kTraceMaxBatch = 4096;
 constexpr int kTraceEdgeArrays = 9;   // key, next, prev, leader, rank, and four more for the jumping
-constexpr int kIdBackground = -1;
-constexpr int kIdOut = -2;      // a value outside [-1, N)
-constexpr int kIdOffMap = -3;   // beyond the map
-
-template <int DT>
-__device__ __forceinline__ int id_of(uint32_t raw, int N) {
-  int v;
-  if (DT == WM2F_F32) {
-    if (raw == 0xbf800000u) return kIdBackground;  // -1.0f
-    if (!f32_bits_to_int(raw, v)) return kIdOut;
-  } else {
-    v = (int)raw;  // int32 as it is; a uint8 arrives zero-extended
-    if (v == -1) return kIdBackground;
-  }
-  return (v >= 0 && v < N) ? v : kIdOut;
-}
+constexpr int kIdBackground = kMapBackground;
+constexpr int kIdOut = kMapOutOfRange;  // a value outside [-1, N)
+constexpr int kIdOffMap = -3;           // beyond the map
 
 template <int DT>
 struct MapReader {
-  using E = typename std::conditional<DT == WM2F_U8, uint8_t, uint32_t>::type;
+  using E = typename MapElem<DT>::type;
   const E* base;  // of the image
   int H, W, N;
   __device__ __forceinline__ int at(int y, int x) const {
     if (y < 0 || y >= H || x < 0 || x >= W) return kIdOffMap;
-    return id_of<DT>((uint32_t)base[y * W + x], N);
+    return map_id_or_code<DT>((uint32_t)base[y * W + x], N);
   }
 };
 
@@ -277,7 +262,7 @@ __global__ __launch_bounds__(kTraceThreads) void trace_loops_kernel(const void* 
   const int j = lead_prefix[e] - 1;
   if (!in_range(j, n_loops)) return;
   const int g = key[e] >> 2, HW = H * W;
-  int id = in_range(g, B * HW) ? id_of<DT>((uint32_t)reinterpret_cast<const T*>(map)[g], N) : 0;
+  int id = in_range(g, B * HW) ? map_id_or_code<DT>((uint32_t)reinterpret_cast<const T*>(map)[g], N) : 0;
   if (id < 0) id = 0;  // never: an edge belongs to a pixel with an id
   const int b = g / HW;
   const int pe = prev[e];
@@ -346,7 +331,7 @@ bool trace_sizes_ok(int B, int H, int W, int N) {
 int trace_blocks(int B, int H, int W) { return ceil_div(B * H * W, kTracePixels); }
 
 int check_trace(const char* who, int dtype, int B, int H, int W, int N) {
-  WM2F_REQUIRE(dtype == WM2F_F32 || dtype == WM2F_I32 || dtype == WM2F_U8, "%s: map must be fp32, int32 or uint8", who);
+  WM2F_REQUIRE_MAP_DTYPE(dtype, who);
   WM2F_REQUIRE(B > 0 && H > 0 && W > 0 && N >= 0, "%s: bad size", who);
   if (!trace_sizes_ok(B, H, W, N)) {
     set_error("%s: 4 * B * H * W < 2^31, B <= %d, N <= %d (got %d x %d x %d, N = %d)", who, kTraceMaxBatch,
@@ -365,17 +350,6 @@ EdgeArrays edge_arrays(void* edge_workspace, int E) {
   const int64_t n = E;
   return {p, p + n, p + 2 * n, p + 3 * n, p + 4 * n, p + 5 * n, p + 6 * n, p + 7 * n, p + 8 * n};
 }
-
-#define WM2F_TRACE_DISPATCH(dtype, CALL) \
-  do {                                   \
-    if (dtype == WM2F_F32) {             \
-      CALL(WM2F_F32);                    \
-    } else if (dtype == WM2F_I32) {      \
-      CALL(WM2F_I32);                    \
-    } else {                             \
-      CALL(WM2F_U8);                     \
-    }                                    \
-  } while (0)
 
 }  // namespace
 }  // namespace wm2f
@@ -409,10 +383,10 @@ extern "C" int wm2f_trace_count(const void* map, int dtype, int32_t* counts, voi
   uint32_t* words = (uint32_t*)workspace;
   int32_t* block_totals = (int32_t*)workspace + (int64_t)B * H * W;
   WM2F_REQUIRE(hipMemsetAsync(counts, 0, (size_t)(B + 1) * sizeof(int32_t), s) == hipSuccess, "%s: clearing failed", who);
-#define WM2F_TRACE_COUNT(DT) \
-  hipLaunchKernelGGL(trace_count_kernel<DT>, dim3(blocks), dim3(kTracePixels), 0, s, map, words, block_totals, counts, B, H, W, N)
-  WM2F_TRACE_DISPATCH(dtype, WM2F_TRACE_COUNT);
-#undef WM2F_TRACE_COUNT
+  for_map_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(trace_count_kernel<decltype(dt)::value>, dim3(blocks), dim3(kTracePixels), 0, s, map, words,
+                       block_totals, counts, B, H, W, N);
+  });
   WM2F_CHECK_LAUNCH(who);
   hipLaunchKernelGGL(trace_block_scan_kernel, dim3(1), dim3(kTraceScanThreads), 0, s, block_totals, blocks, counts);
   WM2F_CHECK_LAUNCH(who);
@@ -431,11 +405,10 @@ extern "C" int wm2f_trace_link(const void* map, int dtype, const void* workspace
   const EdgeArrays a = edge_arrays(edge_workspace, E);
   // a map that changed since the count launch leaves words unwritten: they must still be in range
   WM2F_REQUIRE(hipMemsetAsync(a.key, 0, (size_t)3 * E * sizeof(int32_t), s) == hipSuccess, "%s: clearing failed", who);
-#define WM2F_TRACE_LINK(DT)                                                                                          \
-  hipLaunchKernelGGL(trace_link_kernel<DT>, dim3(trace_blocks(B, H, W)), dim3(kTracePixels), 0, s, map, words,       \
-                     block_offsets, a.key, a.next, a.prev, E, B, H, W, N)
-  WM2F_TRACE_DISPATCH(dtype, WM2F_TRACE_LINK);
-#undef WM2F_TRACE_LINK
+  for_map_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(trace_link_kernel<decltype(dt)::value>, dim3(trace_blocks(B, H, W)), dim3(kTracePixels), 0, s, map,
+                       words, block_offsets, a.key, a.next, a.prev, E, B, H, W, N);
+  });
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;
 }
@@ -487,11 +460,10 @@ extern "C" int wm2f_trace_loops(const void* map, int dtype, const void* edge_wor
   WM2F_REQUIRE(hipMemsetAsync(loop_key, 0, (size_t)n_loops * sizeof(int64_t), s) == hipSuccess &&
                    hipMemsetAsync(loop_len, 0, (size_t)n_loops * sizeof(int32_t), s) == hipSuccess,
                "%s: clearing failed", who);
-#define WM2F_TRACE_LOOPS(DT)                                                                                            \
-  hipLaunchKernelGGL(trace_loops_kernel<DT>, dim3(ceil_div(E, kTraceThreads)), dim3(kTraceThreads), 0, s, map, a.key,   \
-                     a.prev, a.leader, a.rank, lead_prefix, loop_key, loop_len, E, n_loops, B, H, W, N)
-  WM2F_TRACE_DISPATCH(dtype, WM2F_TRACE_LOOPS);
-#undef WM2F_TRACE_LOOPS
+  for_map_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(trace_loops_kernel<decltype(dt)::value>, dim3(ceil_div(E, kTraceThreads)), dim3(kTraceThreads), 0, s,
+                       map, a.key, a.prev, a.leader, a.rank, lead_prefix, loop_key, loop_len, E, n_loops, B, H, W, N);
+  });
   WM2F_CHECK_LAUNCH(who);
   return WM2F_OK;
 }

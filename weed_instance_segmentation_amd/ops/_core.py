@@ -101,6 +101,71 @@ def _dtype_code(t: torch.Tensor, allowed, error: str) -> int:
     return _DTYPE_CODES[t.dtype]
 
 
+def _id_maps_dtype(maps: torch.Tensor, who: str, what: str = "a tensor", contiguous: bool = True):
+    """The first half of `_id_maps`: (maps, dtype code) of maps that are a tensor on the GPU, fp32, int32 or uint8."""
+    if not isinstance(maps, torch.Tensor):
+        raise TypeError(f"{who}: expected {what}")
+    if contiguous:
+        maps = _req(maps, "maps", maps.dtype)
+    else:
+        _on_gpu(maps, "maps")
+    return maps, _dtype_code(maps, (torch.float32, torch.int32, torch.uint8), f"{who}: maps fp32 / int32 / uint8, got {maps.dtype}")
+
+
+def _id_maps_size(maps: torch.Tensor, who: str, detail: str | None = None, bad: bool = False):
+    """The second half: (B, H, W) of maps that are (B, H, W) and not empty."""
+    if maps.dim() != 3:
+        raise ValueError(f"{who}: maps must be (B, H, W), got {tuple(maps.shape)}")
+    B, H, W = (int(v) for v in maps.shape)
+    if B == 0 or H == 0 or W == 0 or bad:
+        raise ValueError(f"{who}: bad size" + ("" if detail is None else f" {tuple(maps.shape)}{detail}"))
+    return B, H, W
+
+
+def _id_maps(maps: torch.Tensor, who: str, what: str = "a tensor", detail: str | None = None, bad: bool = False,
+             contiguous: bool = True):
+    """What a wrapper of an id-map kernel (csrc/labelmap.h) opens with: (maps, dtype code, B, H, W) of (B, H, W) maps that
+    are on the GPU, fp32, int32 or uint8, and not empty.  `what` completes "expected ..."; an empty map, or `bad` -- the
+    caller's own sizes are wrong --, is "bad size", followed by the shape and `detail` where the caller names its sizes.
+    contiguous=False leaves a strided view as it is, for a caller that may still refuse the size.  A caller with a check
+    of its own between the two halves calls them itself."""
+    maps, dt = _id_maps_dtype(maps, who, what, contiguous)
+    return (maps, dt, *_id_maps_size(maps, who, detail, bad))
+
+
+def _id_maps_d2(maps: torch.Tensor, d2: torch.Tensor, who: str, detail: str | None = None, bad: bool = False):
+    """`_id_maps` for an op that also reads the maps' `labelmap_distance`: (maps, dtype code, d2, B, H, W).  Its shape
+    error names both tensors."""
+    maps, dt = _id_maps_dtype(maps, who, "tensors")
+    d2 = _req(d2, "d2", torch.int32)
+    if maps.dim() != 3 or d2.shape != maps.shape:
+        raise ValueError(f"{who}: maps and d2 must be (B, H, W), got {tuple(maps.shape)} and {tuple(d2.shape)}")
+    return (maps, dt, d2, *_id_maps_size(maps, who, detail, bad))
+
+
+def _id_rows(who: str, B: int, ids: torch.Tensor | None, n_ids: torch.Tensor | None, N: int | None):
+    """The result rows of a per-instance op as (ids, n_ids, N): without `ids`, row r is id r of [0, N); with `ids` (B, N)
+    int32 ascending and `n_ids` (B) of them valid, row r of image b is the raw id ids[b][r]."""
+    if (ids is None) != (n_ids is None):
+        raise ValueError(f"{who}: ids and n_ids go together")
+    if ids is not None:
+        ids, n_ids = _req(ids, "ids", torch.int32), _req(n_ids, "n_ids", torch.int32)
+        if ids.dim() != 2 or ids.shape[0] != B or n_ids.shape != (B,) or (N is not None and int(N) != ids.shape[1]):
+            raise ValueError(f"{who}: shapes disagree")
+        N = int(ids.shape[1])
+    elif N is None:
+        raise ValueError(f"{who}: N is needed without an id list")
+    if int(N) < 0:
+        raise ValueError(f"{who}: bad size")
+    return ids, n_ids, int(N)
+
+
+def _workspace(nbytes: int, device, floor: int = 1) -> torch.Tensor:
+    """`nbytes` of scratch memory, at least `floor`: a workspace query answers -1 for an unsupported size, and the launch
+    that follows reports it, so the tensor only has to exist."""
+    return torch.empty(max(int(nbytes), floor), device=device, dtype=torch.uint8)
+
+
 def _levels(level_hw):
     """The host table (h0, w0, h1, w1, ...) of K1's levels."""
     return host_i32([x for hw in level_hw for x in hw])

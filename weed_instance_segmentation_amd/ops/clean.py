@@ -6,7 +6,7 @@ import torch
 
 from .. import _lib
 from .._lib import load
-from ._core import _dtype_code, _launch, _p, _req
+from ._core import _dtype_code, _id_maps, _launch, _p, _workspace
 
 _KEEP = {"all": _lib.WM2F_CLEAN_KEEP_ALL, "largest": _lib.WM2F_CLEAN_KEEP_LARGEST}
 # the parts of the chain in order, each its own tagged launch so that a kernel timer sees them
@@ -23,21 +23,13 @@ def labelmap_clean(maps: torch.Tensor, N: int, keep: str = "all", min_area: int 
     out (B, H, W) `out_dtype` (int32 or fp32) with -1 where free; stats (B, N, 8) int64
     [area_in, pieces_in, pieces_kept, area_kept, holes_filled, pixels_filled, area_out, new_id]; n_out (B) int32.
     Everything stays on the device."""
-    if not isinstance(maps, torch.Tensor):
-        raise TypeError("labelmap_clean: expected a tensor")
-    maps = _req(maps, "maps", maps.dtype)
-    dt = _dtype_code(maps, (torch.float32, torch.int32, torch.uint8),
-                     f"labelmap_clean: maps fp32 / int32 / uint8, got {maps.dtype}")
+    N, min_area = int(N), int(min_area)
+    maps, dt, B, H, W = _id_maps(maps, "labelmap_clean", detail=f", N = {N}, or min_area = {min_area}",
+                                 bad=N < 0 or min_area < 0)
     if out_dtype not in (torch.int32, torch.float32):
         raise TypeError(f"labelmap_clean: out_dtype int32 or fp32, got {out_dtype}")
-    if maps.dim() != 3:
-        raise ValueError(f"labelmap_clean: maps must be (B, H, W), got {tuple(maps.shape)}")
     if keep not in _KEEP:
         raise ValueError(f"labelmap_clean: keep must be 'all' or 'largest', got {keep!r}")
-    B, H, W = (int(v) for v in maps.shape)
-    N, min_area = int(N), int(min_area)
-    if N < 0 or B == 0 or H == 0 or W == 0 or min_area < 0:
-        raise ValueError(f"labelmap_clean: bad size {tuple(maps.shape)}, N = {N}, or min_area = {min_area}")
     limit = -1 if max_hole_area is None else int(max_hole_area)
     if limit < 0 and max_hole_area is not None:
         raise ValueError(f"labelmap_clean: max_hole_area must not be negative, got {max_hole_area}")
@@ -45,8 +37,7 @@ def labelmap_clean(maps: torch.Tensor, N: int, keep: str = "all", min_area: int 
     out = torch.empty(B, H, W, device=dev, dtype=out_dtype)
     stats = torch.empty(B, N, 8, device=dev, dtype=torch.int64)
     n_out = torch.empty(B, device=dev, dtype=torch.int32)
-    nbytes = int(load().wm2f_labelmap_clean_workspace(B, H, W, N))
-    ws = torch.empty(max(nbytes, 8), device=dev, dtype=torch.uint8)  # an unsupported size: the launch reports it
+    ws = _workspace(load().wm2f_labelmap_clean_workspace(B, H, W, N), dev, 8)
     odt = _dtype_code(out, (torch.int32, torch.float32), "labelmap_clean: out_dtype")
     for phase, tag in _PHASES:
         if phase == _lib.WM2F_CLEAN_HOLES and not fill_holes:

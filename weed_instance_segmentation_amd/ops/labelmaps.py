@@ -6,7 +6,7 @@ from __future__ import annotations
 import torch
 
 from .._lib import load
-from ._core import _dtype_code, _launch, _p, _req
+from ._core import _dtype_code, _id_maps, _id_maps_d2, _id_rows, _launch, _p, _req, _workspace
 
 
 def labelmap_to_masks(label_map: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
@@ -130,20 +130,10 @@ def labelmap_boundary(maps: torch.Tensor, d: int) -> torch.Tensor:
     """(B, H, W) id maps (fp32 with -1 background, int32 or uint8) -> (B, H, W) int32 band maps
     (wm2f_labelmap_boundary): a pixel keeps its id where the (2d+1) x (2d+1) square around it leaves the image or meets
     another id -- the boundary band of its instance -- and is -1 where it is interior or has no id."""
-    if not isinstance(maps, torch.Tensor):
-        raise TypeError("labelmap_boundary: expected a tensor")
-    maps = _req(maps, "maps", maps.dtype)
-    dt = _dtype_code(maps, (torch.float32, torch.int32, torch.uint8),
-                     f"labelmap_boundary: maps fp32 / int32 / uint8, got {maps.dtype}")
-    if maps.dim() != 3:
-        raise ValueError(f"labelmap_boundary: maps must be (B, H, W), got {tuple(maps.shape)}")
-    B, H, W = (int(v) for v in maps.shape)
     d = int(d)
-    if B == 0 or H == 0 or W == 0 or d < 1:
-        raise ValueError(f"labelmap_boundary: bad size {tuple(maps.shape)}, d = {d}")
+    maps, dt, B, H, W = _id_maps(maps, "labelmap_boundary", detail=f", d = {d}", bad=d < 1)
     out = torch.empty(B, H, W, device=maps.device, dtype=torch.int32)
-    nbytes = int(load().wm2f_labelmap_boundary_workspace(B, H, W))
-    ws = torch.empty(max(nbytes, 1), device=maps.device, dtype=torch.uint8)  # an unsupported size: the launch reports it
+    ws = _workspace(load().wm2f_labelmap_boundary_workspace(B, H, W), maps.device)
     _launch("wm2f_labelmap_boundary", maps, _p(maps), dt, _p(out), _p(ws), B, H, W, d, tag="labelmap_boundary")
     return out
 
@@ -154,26 +144,8 @@ def labelmap_instance_stats(maps: torch.Tensor, ids: torch.Tensor | None = None,
     [area, xmin, ymin, xmax, ymax, sum_x, sum_y, 0] per id (wm2f_labelmap_instance_stats), xmax / ymax inclusive, an id
     without a pixel [0, W, H, -1, -1, 0, 0, 0].  Without `ids`, row r is id r of [0, N).  With `ids` (B, N) int32
     ascending and `n_ids` (B) of them valid, row r is the raw id ids[b][r]."""
-    if not isinstance(maps, torch.Tensor):
-        raise TypeError("labelmap_instance_stats: expected tensors")
-    maps = _req(maps, "maps", maps.dtype)
-    dt = _dtype_code(maps, (torch.float32, torch.int32, torch.uint8),
-                     f"labelmap_instance_stats: maps fp32 / int32 / uint8, got {maps.dtype}")
-    if maps.dim() != 3:
-        raise ValueError(f"labelmap_instance_stats: maps must be (B, H, W), got {tuple(maps.shape)}")
-    B, H, W = (int(v) for v in maps.shape)
-    if (ids is None) != (n_ids is None):
-        raise ValueError("labelmap_instance_stats: ids and n_ids go together")
-    if ids is not None:
-        ids, n_ids = _req(ids, "ids", torch.int32), _req(n_ids, "n_ids", torch.int32)
-        if ids.dim() != 2 or ids.shape[0] != B or n_ids.shape != (B,) or (N is not None and int(N) != ids.shape[1]):
-            raise ValueError("labelmap_instance_stats: shapes disagree")
-        N = int(ids.shape[1])
-    elif N is None:
-        raise ValueError("labelmap_instance_stats: N is needed without an id list")
-    N = int(N)
-    if N < 0 or B == 0 or H == 0 or W == 0:
-        raise ValueError("labelmap_instance_stats: bad size")
+    maps, dt, B, H, W = _id_maps(maps, "labelmap_instance_stats", "tensors")
+    ids, n_ids, N = _id_rows("labelmap_instance_stats", B, ids, n_ids, N)
     stats = torch.empty(B, N, 8, device=maps.device, dtype=torch.int64)
     if N == 0:
         return stats
@@ -186,19 +158,9 @@ def labelmap_distance(maps: torch.Tensor, border_outside: bool = True) -> torch.
     pixel to the nearest position that does not carry its id (wm2f_labelmap_distance), 0 for a pixel without an id.
     `border_outside`: the positions just beyond the image count as not carrying the id; without it only real pixels do,
     and a pixel whose id fills its whole image gets INT32_MAX."""
-    if not isinstance(maps, torch.Tensor):
-        raise TypeError("labelmap_distance: expected a tensor")
-    maps = _req(maps, "maps", maps.dtype)
-    dt = _dtype_code(maps, (torch.float32, torch.int32, torch.uint8),
-                     f"labelmap_distance: maps fp32 / int32 / uint8, got {maps.dtype}")
-    if maps.dim() != 3:
-        raise ValueError(f"labelmap_distance: maps must be (B, H, W), got {tuple(maps.shape)}")
-    B, H, W = (int(v) for v in maps.shape)
-    if B == 0 or H == 0 or W == 0:
-        raise ValueError(f"labelmap_distance: bad size {tuple(maps.shape)}")
+    maps, dt, B, H, W = _id_maps(maps, "labelmap_distance", detail="")
     d2 = torch.empty(B, H, W, device=maps.device, dtype=torch.int32)
-    nbytes = int(load().wm2f_labelmap_distance_workspace(B, H, W))
-    ws = torch.empty(max(nbytes, 1), device=maps.device, dtype=torch.uint8)  # an unsupported size: the launch reports it
+    ws = _workspace(load().wm2f_labelmap_distance_workspace(B, H, W), maps.device)
     _launch("wm2f_labelmap_distance", maps, _p(maps), dt, _p(d2), _p(ws), B, H, W, int(bool(border_outside)),
             tag="labelmap_distance")
     return d2
@@ -211,27 +173,8 @@ def labelmap_aim_points(maps: torch.Tensor, d2: torch.Tensor, ids: torch.Tensor 
     (wm2f_labelmap_aim_points): a pixel of the instance where d2 is largest -- among equals the one nearest the rounded
     centroid of `stats` (`labelmap_instance_stats` of the same maps and rows; without it this term is 0), then the first
     in raster order; [-1, -1, 0, 0] for an id without a pixel.  `ids` / `n_ids` / `N` as in `labelmap_instance_stats`."""
-    if not isinstance(maps, torch.Tensor):
-        raise TypeError("labelmap_aim_points: expected tensors")
-    maps = _req(maps, "maps", maps.dtype)
-    dt = _dtype_code(maps, (torch.float32, torch.int32, torch.uint8),
-                     f"labelmap_aim_points: maps fp32 / int32 / uint8, got {maps.dtype}")
-    d2 = _req(d2, "d2", torch.int32)
-    if maps.dim() != 3 or d2.shape != maps.shape:
-        raise ValueError(f"labelmap_aim_points: maps and d2 must be (B, H, W), got {tuple(maps.shape)} and {tuple(d2.shape)}")
-    B, H, W = (int(v) for v in maps.shape)
-    if (ids is None) != (n_ids is None):
-        raise ValueError("labelmap_aim_points: ids and n_ids go together")
-    if ids is not None:
-        ids, n_ids = _req(ids, "ids", torch.int32), _req(n_ids, "n_ids", torch.int32)
-        if ids.dim() != 2 or ids.shape[0] != B or n_ids.shape != (B,) or (N is not None and int(N) != ids.shape[1]):
-            raise ValueError("labelmap_aim_points: shapes disagree")
-        N = int(ids.shape[1])
-    elif N is None:
-        raise ValueError("labelmap_aim_points: N is needed without an id list")
-    N = int(N)
-    if N < 0 or B == 0 or H == 0 or W == 0:
-        raise ValueError("labelmap_aim_points: bad size")
+    maps, dt, d2, B, H, W = _id_maps_d2(maps, d2, "labelmap_aim_points")
+    ids, n_ids, N = _id_rows("labelmap_aim_points", B, ids, n_ids, N)
     if stats is not None:
         stats = _req(stats, "stats", torch.int64)
         if stats.shape != (B, N, 8):
@@ -239,8 +182,7 @@ def labelmap_aim_points(maps: torch.Tensor, d2: torch.Tensor, ids: torch.Tensor 
     points = torch.empty(B, N, 4, device=maps.device, dtype=torch.int32)
     if N == 0:
         return points
-    nbytes = int(load().wm2f_labelmap_aim_points_workspace(B, N))
-    ws = torch.empty(max(nbytes, 8), device=maps.device, dtype=torch.uint8)  # an unsupported size: the launch reports it
+    ws = _workspace(load().wm2f_labelmap_aim_points_workspace(B, N), maps.device, 8)
     _launch("wm2f_labelmap_aim_points", maps, _p(maps), dt, _p(d2), _p(ids), _p(n_ids), _p(stats), _p(points), _p(ws),
             B, H, W, N, tag="labelmap_aim_points")
     return points
@@ -263,17 +205,8 @@ def labelmap_nearest(maps: torch.Tensor, N: int, max_d2: int, source: torch.Tens
     (B, N) uint8 / bool: which instances are sources (None: all).  `blocked`: a pixel of an instance that is no source is
     written as its own id with d2 = 0; otherwise it is a query like a free pixel.  `walk_all` switches the rows pass's
     early "none" off (same results; for measurements)."""
-    if not isinstance(maps, torch.Tensor):
-        raise TypeError("labelmap_nearest: expected a tensor")
-    maps = _req(maps, "maps", maps.dtype)
-    dt = _dtype_code(maps, (torch.float32, torch.int32, torch.uint8),
-                     f"labelmap_nearest: maps fp32 / int32 / uint8, got {maps.dtype}")
-    if maps.dim() != 3:
-        raise ValueError(f"labelmap_nearest: maps must be (B, H, W), got {tuple(maps.shape)}")
-    B, H, W = (int(v) for v in maps.shape)
     N, max_d2 = int(N), int(max_d2)
-    if B == 0 or H == 0 or W == 0 or N < 1 or max_d2 < 0:
-        raise ValueError(f"labelmap_nearest: bad size {tuple(maps.shape)}, N = {N}, max_d2 = {max_d2}")
+    maps, dt, B, H, W = _id_maps(maps, "labelmap_nearest", detail=f", N = {N}, max_d2 = {max_d2}", bad=N < 1 or max_d2 < 0)
     if source is not None:
         source = _req(source, "source", source.dtype if source.dtype in (torch.bool, torch.uint8) else torch.uint8)
         if source.shape != (B, N):
@@ -281,8 +214,7 @@ def labelmap_nearest(maps: torch.Tensor, N: int, max_d2: int, source: torch.Tens
         source = source.view(torch.uint8)
     nearest = torch.empty(B, H, W, device=maps.device, dtype=torch.int32)
     d2 = torch.empty(B, H, W, device=maps.device, dtype=torch.int32)
-    nbytes = int(load().wm2f_labelmap_nearest_workspace(B, H, W))
-    ws = torch.empty(max(nbytes, 1), device=maps.device, dtype=torch.uint8)  # an unsupported size: the launch reports it
+    ws = _workspace(load().wm2f_labelmap_nearest_workspace(B, H, W), maps.device)
     flags = (1 if blocked else 0) | (2 if walk_all else 0)
     _launch("wm2f_labelmap_nearest", maps, _p(maps), dt, _p(source), _p(nearest), _p(d2), _p(ws), B, H, W, N, max_d2, flags,
             tag="labelmap_nearest")
@@ -300,21 +232,14 @@ def labelmap_cell_counts(maps: torch.Tensor, group: torch.Tensor, G: int, cell, 
     `cell` = (h, w) pixels, shifted by `offset` = (off_y, off_x) with 0 <= off < cell, the pixels of the instances of
     every group 0 .. G-1 (group value 255: not counted).  Column g counts the pixels with veto_d2 > veto_max (all of them
     without `veto_d2`), column G + g the others."""
-    if not isinstance(maps, torch.Tensor):
-        raise TypeError("labelmap_cell_counts: expected a tensor")
-    maps = _req(maps, "maps", maps.dtype)
-    dt = _dtype_code(maps, (torch.float32, torch.int32, torch.uint8),
-                     f"labelmap_cell_counts: maps fp32 / int32 / uint8, got {maps.dtype}")
-    if maps.dim() != 3:
-        raise ValueError(f"labelmap_cell_counts: maps must be (B, H, W), got {tuple(maps.shape)}")
-    B, H, W = (int(v) for v in maps.shape)
+    G, (ch, cw), (oy, ox) = int(G), (int(v) for v in cell), (int(v) for v in offset)
+    maps, dt, B, H, W = _id_maps(
+        maps, "labelmap_cell_counts", detail=f", cell {ch} x {cw}, offset ({oy}, {ox}), G = {G}",
+        bad=ch < 1 or cw < 1 or not (0 <= oy < ch and 0 <= ox < cw) or not 1 <= G <= CELL_MAX_GROUPS)
     group = _req(group, "group", torch.uint8)
     if group.dim() != 2 or group.shape[0] != B or group.shape[1] < 1:
         raise ValueError(f"labelmap_cell_counts: group must be ({B}, N), got {tuple(group.shape)}")
-    N, G = int(group.shape[1]), int(G)
-    (ch, cw), (oy, ox) = (int(v) for v in cell), (int(v) for v in offset)
-    if B == 0 or H == 0 or W == 0 or ch < 1 or cw < 1 or not (0 <= oy < ch and 0 <= ox < cw) or not 1 <= G <= CELL_MAX_GROUPS:
-        raise ValueError(f"labelmap_cell_counts: bad size {tuple(maps.shape)}, cell {ch} x {cw}, offset ({oy}, {ox}), G = {G}")
+    N = int(group.shape[1])
     if veto_d2 is not None:
         veto_d2 = _req(veto_d2, "veto_d2", torch.int32)
         if veto_d2.shape != maps.shape:

@@ -7,24 +7,16 @@ import torch
 
 from .. import _lib
 from .._lib import Wm2fError, load
-from ._core import _dtype_code, _launch, _p, _req
+from ._core import _id_maps, _launch, _p, _req
 
 
 def _toggle_args(maps, N, order, who):
-    if not isinstance(maps, torch.Tensor):
-        raise TypeError(f"{who}: expected tensors")
-    maps = _req(maps, "maps", maps.dtype)
-    dt = _dtype_code(maps, (torch.float32, torch.int32, torch.uint8), f"{who}: maps fp32 / int32 / uint8, got {maps.dtype}")
-    if maps.dim() != 3:
-        raise ValueError(f"{who}: maps must be (B, H, W), got {tuple(maps.shape)}")
-    B, H, W = (int(v) for v in maps.shape)
+    maps, dt, B, H, W = _id_maps(maps, who, "tensors")
     N, order = int(N), int(order)
     if order not in (0, 1):
         raise ValueError(f"{who}: order is 0 (row-major) or 1 (column-major), got {order}")
     if N < 0 or N > _lib.WM2F_RLE_MAX_IDS:
         raise ValueError(f"{who}: N must be in [0, {_lib.WM2F_RLE_MAX_IDS}], got {N}")
-    if B == 0 or H == 0 or W == 0:
-        raise ValueError(f"{who}: bad size")
     return maps, dt, B, H, W, N, order
 
 

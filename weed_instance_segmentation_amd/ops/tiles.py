@@ -4,7 +4,7 @@ from __future__ import annotations
 import torch
 
 from .._lib import load
-from ._core import _dtype_code, _launch, _p, _req
+from ._core import _dtype_code, _launch, _p, _req, _workspace
 
 
 def _tiles(tiles: torch.Tensor, n_ids: torch.Tensor, who: str):
@@ -105,8 +105,7 @@ def tile_link(hist: torch.Tensor, pairs: torch.Tensor, labels: torch.Tensor, n_i
     dev = labels.device
     remap = torch.empty(T, N, device=dev, dtype=torch.int32)
     n_merged = torch.empty(1, device=dev, dtype=torch.int32)
-    nbytes = int(load().wm2f_tile_merge_workspace(T, N, P))
-    ws = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)  # an unsupported size: the launch reports it
+    ws = _workspace(load().wm2f_tile_merge_workspace(T, N, P), dev, 16)
     _launch("wm2f_tile_link", labels, _p(hist), _p(pairs), _p(labels), _p(n_ids), _p(owned), _p(remap), _p(n_merged), _p(ws),
             T, N, P, num, den, tag="tile_link")
     return remap, n_merged

@@ -5,7 +5,7 @@ import torch
 
 from .. import _lib
 from .._lib import load
-from ._core import _dtype_code, _launch, _on_gpu, _p
+from ._core import _id_maps, _launch, _p
 
 CRACK, PIXEL = 0, 1  # coords
 
@@ -28,20 +28,12 @@ def labelmap_trace(maps: torch.Tensor, N: int, coords: int = PIXEL, simplify: bo
     the loops between them, and TWO device-to-host copies: the edge count, then the loop and point counts.  Raises
     ValueError when a map holds a value outside [-1, N)."""
     who = "labelmap_trace"
-    if not isinstance(maps, torch.Tensor):
-        raise TypeError(f"{who}: expected tensors")
-    _on_gpu(maps, "maps")
-    dt = _dtype_code(maps, (torch.float32, torch.int32, torch.uint8), f"{who}: maps fp32 / int32 / uint8, got {maps.dtype}")
-    if maps.dim() != 3:
-        raise ValueError(f"{who}: maps must be (B, H, W), got {tuple(maps.shape)}")
-    B, H, W = (int(v) for v in maps.shape)
+    maps, dt, B, H, W = _id_maps(maps, who, "tensors", contiguous=False)
     N, coords, simplify = int(N), int(coords), bool(simplify)
     if coords not in (CRACK, PIXEL):
         raise ValueError(f"{who}: coords is 0 (crack) or 1 (pixel), got {coords}")
     if N < 0 or N > _lib.WM2F_RLE_MAX_IDS:
         raise ValueError(f"{who}: N must be in [0, {_lib.WM2F_RLE_MAX_IDS}], got {N}")
-    if B == 0 or H == 0 or W == 0:
-        raise ValueError(f"{who}: bad size")
     lib = load()
     size = int(lib.wm2f_trace_workspace(B, H, W, N))
     if size < 0:
