@@ -1618,6 +1618,55 @@ int wm2f_labelmap_split(const void* map, int dtype, const int32_t* d2, int32_t* 
                         void* workspace, int B, int H, int W, int N, int M, int num, int den, int min_peak_d2, int rounds,
                         void* stream);
 
+/* ---- per-instance shape sums: moments, sides, border counts, convex hull ------------------------
+ * What wm2f_labelmap_instance_stats does not say about an instance: how long, how ragged and how convex it is.  The
+ * device returns exact integers; the float traits (axes, orientation, perimeter, solidity ...) are a few float64
+ * operations on them (instances.shape_from_sums).  tests/shape_reference.py restates every rule in numpy / scipy.
+ * Maps, ids / n_ids / N and "a value that is no listed id belongs to nothing" are wm2f_labelmap_instance_stats'.
+ *
+ * wm2f_labelmap_shape_stats: shape (B, N, 10) int64 per instance, x and y the pixel indices (point masses at pixel
+ *   centres):  [0] area  [1] sum x  [2] sum y  [3] sum x^2  [4] sum y^2  [5] sum xy
+ *   [6] sides: the pixel sides between a pixel of the instance and anything else, the outside of the image included (the
+ *       length of the instance's crack contours);
+ *   [7] p_straight  [8] p_diag  [9] p_mixed: a pixel of instance r is a BORDER pixel of r when one of its four
+ *       neighbours is not r (outside the image is not r).  A border pixel with a border pixels of r among its four
+ *       neighbours and b among its diagonal ones has the code 1 + 2a + 10b; codes 5, 7, 15, 17, 25, 27 count into
+ *       p_straight, 21 and 33 into p_diag, 13 and 23 into p_mixed, every other code nowhere.  The 4-neighbourhood
+ *       perimeter of skimage is p_straight + sqrt(2) p_diag + (1 + sqrt(2)) / 2 p_mixed; a lone pixel has 0.
+ *   An id without a pixel has an all-zero row.  At the limits area <= 2^28 and x^2 < 2^28: every sum is below 2^57 and
+ *   fits int64.  Three launches (clear, moments: one read of the map; border: a second read through 64 x 32 tiles with
+ *   a halo of 2).  Accumulators are in LDS up to N = 1024 (52 KiB at that N for the moments), in the result above.
+ *
+ * wm2f_labelmap_hull: the convex hull of every instance's pixel SQUARES, that is of the corners (x, y), (x+1, y),
+ *   (x, y+1), (x+1, y+1) of its pixels on the corner lattice [0, W] x [0, H] (the "crack" coordinates of the polygons).
+ *   stats (B, N, 8): wm2f_labelmap_instance_stats of the same map and rows (the boxes).  hull (B, N, 3) int64:
+ *   [n_vertices, area2, feret2]: the number of hull vertices, twice the hull's area (the shoelace sum, exact), the
+ *   largest squared distance between two vertices; [0, 0, 0] for an id without a pixel; n_vertices = -1 for an instance
+ *   the row table was too short for.
+ *   The vertices are strictly convex (no collinear point is kept), start at the vertex with the smallest (y, then x)
+ *   and go on towards increasing x: with y pointing down every consecutive cross product
+ *   (b - a) x (c - b) = (bx - ax)(cy - by) - (by - ay)(cx - bx) is POSITIVE (clockwise on the screen).
+ *   rows: the capacity of the row table, at least the sum of the box heights of all B N instances (at most B N H).
+ *   workspace: wm2f_labelmap_hull_workspace(B, N, rows) bytes (-1 for a bad size), 8-byte aligned, no clearing:
+ *   8 (B N + 1) for the instances' first rows, 8 per row for (xmin, xmax) of every (instance, row), 16 per row and 32
+ *   per instance for the vertex slots -- instance i owns 2 (h_i + 2) points, more than the 2 (h_i + 1) a hull can have.
+ *   The vertices stay in the workspace; wm2f_labelmap_hull_vertices copies them out.
+ *   Four launches: scan of the box heights (one workgroup), table init, rows (one read of the map, atomicMin /
+ *   atomicMax per run), chain (a wave per instance: Andrew's monotone chain down the right and the left side in
+ *   int64 cross products, the shoelace sum, the largest distance by brute force).
+ * wm2f_labelmap_hull_vertices: vertices (B, N, K, 2) int32 <- the first K vertices (x, y) of every instance from the
+ *   workspace wm2f_labelmap_hull left (same stats, hull, rows), (-1, -1) past n_vertices.  One launch.
+ * Limits: H, W <= 16384, B <= 32, N <= 4096, rows <= 2^30, K <= 2 (16384 + 2), else WM2F_EUNSUPPORTED, reported before
+ *   a pointer is looked at; a size below 1, a null pointer, ids without n_ids or another dtype: WM2F_EINVAL.  Integer
+ *   atomics only: bit-identical from run to run.  No call allocates, keeps state or waits for the device. */
+int wm2f_labelmap_shape_stats(const void* map, int dtype, const int32_t* ids, const int32_t* n_ids, int64_t* shape, int B,
+                              int H, int W, int N, void* stream);
+int64_t wm2f_labelmap_hull_workspace(int B, int N, int64_t rows);
+int wm2f_labelmap_hull(const void* map, int dtype, const int32_t* ids, const int32_t* n_ids, const int64_t* stats,
+                       int64_t* hull, void* workspace, int64_t rows, int B, int H, int W, int N, void* stream);
+int wm2f_labelmap_hull_vertices(const int64_t* stats, const int64_t* hull, const void* workspace, int64_t rows,
+                                int32_t* vertices, int B, int H, int N, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,7 @@ from .postprocess import Mask2FormerInstancePostProcessor  # noqa: F401
 from .metrics import MeanAveragePrecision  # noqa: F401
 from .instances import (CleanOptions, SplitOptions, aim_points, boundary_dilation, boundary_maps,  # noqa: F401
                         clean_label_maps, distance_maps, grow_label_maps, instance_statistics, nearest_instance_maps,
-                        split_label_maps)
+                        shape_from_sums, shape_statistics, split_label_maps)
 from .treatment import TreatmentOptions, load_treatment_grid, save_treatment_grid, treatment_grid  # noqa: F401
 from .rle import (coco_results, decode_rle, encode_label_maps, rle_from_string, rle_to_string,  # noqa: F401
                   save_coco_results)

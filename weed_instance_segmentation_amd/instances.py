@@ -44,6 +44,16 @@ csrc/split.hip.  The post-processor, the tiled route, `test_with_metrics` and th
 `nearest_instance_maps` and `grow_label_maps` look outward from the plants: every pixel's nearest
 source instance within a cap and the exact squared distance to it, the smallest id among equally near ones, in two
 launches of csrc/nearest.hip whatever the number of instances.  `treatment.py` builds the sprayer's cell grid on them.
+
+    from weed_instance_segmentation_amd import shape_statistics
+    traits = shape_statistics(prediction["segmentation"], n=len(prediction["segments_info"]))
+    traits["axis_major_length"], traits["orientation"], traits["perimeter"], traits["solidity"]
+
+`shape_statistics` says what shape a plant has: the axes, eccentricity and orientation of its second
+moments, skimage's 4-neighbourhood perimeter and the circularity, and from the exact convex hull of its pixel squares
+the convex area, solidity, largest Feret diameter and convexity.  csrc/shape.hip returns exact integer sums in a fixed
+chain of launches whatever the number of instances; `shape_from_sums` turns them into float64 traits on either device.
+The post-processor, `merge_tile_results` and `segment_tiled` add them with `return_shape_stats=True`.
 """
 from __future__ import annotations
 
@@ -344,6 +354,167 @@ def add_aim_points(segments, rows) -> None:
         x, y, d2max = (int(v) for v in rows[int(info["id"])][:3])
         info["aim_point"] = (x, y) if x >= 0 else None
         info["clearance"] = float(np.sqrt(np.float64(d2max))) if x >= 0 else float("nan")
+
+
+# ---------------------------------------------------------------------------------------------- shape traits (section 40)
+SQRT2 = math.sqrt(2.0)
+# the float traits `return_shape_stats=True` adds to a `segments_info` entry, in the order of `shape_trait_rows`' columns
+SHAPE_TRAITS = ("orientation", "axis_major_length", "axis_minor_length", "eccentricity", "perimeter", "crack_length",
+                "equivalent_diameter", "extent", "circularity", "area_convex", "solidity", "feret_diameter_max",
+                "hull_perimeter", "convexity")
+
+
+def shape_from_sums(shape: torch.Tensor, stats: torch.Tensor | None = None, hull=None) -> dict:
+    """(..., N, 10) int64 rows of `ops.labelmap_shape_stats` -> a dict of traits, float64 unless said otherwise, NaN for
+    an id without a pixel (where `stats_to_boxes` gives NaN).  Pure torch; works on either device.
+
+    With A the area and the raw sums Sx, Sy, Sxx, Syy, Sxy of the pixel indices (point masses at pixel centres):
+    - "area" (int64) and "centroid" (..., N, 2) = (Sx / A, Sy / A).
+    - "moments_central" (..., N, 3) = (mu20, mu02, mu11), the variances and the covariance of x and y, computed without
+      cancellation: with the integers cx = round(Sx / A), cy = round(Sy / A), exactly in int64
+      M20 = Sxx - 2 cx Sx + cx^2 A, M02 likewise, M11 = Sxy - cx Sy - cy Sx + cx cy A (below 2^59 at the kernels' limits),
+      then mu20 = M20 / A - (Sx / A - cx)^2, mu02 likewise, mu11 = M11 / A - (Sx / A - cx)(Sy / A - cy); the small
+      differences Sx / A - cx are formed as (Sx - cx A) / A, exact in the numerator.
+    - inertia eigenvalues l1,2 = (mu20 + mu02) / 2 +- sqrt(4 mu11^2 + (mu20 - mu02)^2) / 2;
+      "axis_major_length" = 4 sqrt(l1), "axis_minor_length" = 4 sqrt(l2) (skimage's), "eccentricity" = sqrt(1 - l2 / l1),
+      0 when l1 = 0.
+    - "orientation" = atan2(2 mu11, mu20 - mu02) / 2: the angle of the major axis from the +x axis in image coordinates
+      (y down), in (-pi/2, pi/2], 0 when both arguments are 0.  skimage measures its `orientation` from the row axis:
+      it is pi/2 minus this angle, wrapped into [-pi/2, pi/2].
+    - "perimeter" = p_straight + sqrt(2) p_diag + (1 + sqrt(2)) / 2 p_mixed (skimage's 4-neighbourhood perimeter),
+      "crack_length" (int64) = sides, "equivalent_diameter" = sqrt(4 A / pi), "circularity" = 4 pi A / perimeter^2 (NaN
+      when the perimeter is 0).
+    - with `stats` (the (..., N, 8) rows of `ops.labelmap_instance_stats`): "bbox" (int64, COCO) and "extent" = A / (w h).
+    - with `hull`, the (..., N, 3) rows of `ops.labelmap_hull` or the pair (rows, points) of its vertices=True:
+      "n_hull_vertices" (int64), "area_convex" = area2 / 2, "solidity" = A / area_convex, "feret_diameter_max" =
+      sqrt(feret2), and from the points "hull_perimeter" and "convexity" = hull_perimeter / crack_length.  The hull is
+      the exact polygon of the pixel squares, so area_convex counts area where skimage counts the pixels of a rasterised
+      hull."""
+    f64 = torch.float64
+    A, Sx, Sy, Sxx, Syy, Sxy = (shape[..., k] for k in range(6))
+    some = A > 0
+    nan = torch.full(A.shape, float("nan"), dtype=f64, device=shape.device)
+    Af = A.to(f64)
+    A1 = A.clamp(min=1)
+    cx, cy = (2 * Sx + A1) // (2 * A1), (2 * Sy + A1) // (2 * A1)  # round half up, in integers
+    M20 = Sxx - 2 * cx * Sx + cx * cx * A
+    M02 = Syy - 2 * cy * Sy + cy * cy * A
+    M11 = Sxy - cx * Sy - cy * Sx + cx * cy * A
+    dx, dy = (Sx - cx * A).to(f64) / Af, (Sy - cy * A).to(f64) / Af  # 0 / 0 = NaN for an empty instance
+    mu20, mu02, mu11 = M20.to(f64) / Af - dx * dx, M02.to(f64) / Af - dy * dy, M11.to(f64) / Af - dx * dy
+    root = torch.sqrt(4 * mu11 * mu11 + (mu20 - mu02) ** 2)
+    l1 = (mu20 + mu02) / 2 + root / 2
+    l2 = ((mu20 + mu02) / 2 - root / 2).clamp(min=0)  # NaN stays NaN
+    ecc = torch.sqrt((1 - l2 / torch.where(l1 > 0, l1, torch.ones_like(l1))).clamp(min=0))
+    perimeter = shape[..., 7].to(f64) + SQRT2 * shape[..., 8].to(f64) + (1 + SQRT2) / 2 * shape[..., 9].to(f64)
+    out = {
+        "area": A,
+        "centroid": torch.stack([Sx.to(f64) / Af, Sy.to(f64) / Af], -1),
+        "moments_central": torch.stack([mu20, mu02, mu11], -1),
+        "orientation": torch.atan2(2 * mu11 + 0.0, mu20 - mu02) / 2,  # + 0.0: never atan2(-0.0, negative) = -pi
+        "axis_major_length": 4 * torch.sqrt(l1.clamp(min=0)),
+        "axis_minor_length": 4 * torch.sqrt(l2),
+        "eccentricity": torch.where(some, torch.where(l1 > 0, ecc, torch.zeros_like(ecc)), nan),
+        "perimeter": torch.where(some, perimeter, nan),
+        "crack_length": shape[..., 6],
+        "equivalent_diameter": torch.where(some, torch.sqrt(4 * Af / math.pi), nan),
+        "circularity": torch.where(some & (perimeter > 0), 4 * math.pi * Af / (perimeter * perimeter), nan),
+    }
+    if stats is not None:
+        _, bbox, _ = stats_to_boxes(stats)
+        out["bbox"] = bbox
+        out["extent"] = torch.where(some, Af / (bbox[..., 2] * bbox[..., 3]).to(f64), nan)
+    if hull is not None:
+        rows, points = hull if isinstance(hull, (tuple, list)) else (hull, None)
+        area_convex = rows[..., 1].to(f64) / 2
+        out["n_hull_vertices"] = rows[..., 0]
+        out["area_convex"] = torch.where(some, area_convex, nan)
+        out["solidity"] = torch.where(some, Af / area_convex, nan)
+        out["feret_diameter_max"] = torch.where(some, torch.sqrt(rows[..., 2].to(f64)), nan)
+        if points is not None:
+            K = points.shape[-2]
+            k = torch.arange(K, device=points.device).expand(rows.shape[:-1] + (K,))
+            nv = rows[..., 0:1]
+            nxt = torch.where(k + 1 < nv, k + 1, torch.zeros_like(k))
+            p = points.to(f64)
+            q = torch.gather(p, -2, nxt.unsqueeze(-1).expand(p.shape))
+            edge = torch.sqrt(((q - p) ** 2).sum(-1))
+            hull_perimeter = torch.where(k < nv, edge, torch.zeros_like(edge)).sum(-1)
+            out["hull_perimeter"] = torch.where(some, hull_perimeter, nan)
+            out["convexity"] = torch.where(some, hull_perimeter / shape[..., 6].to(f64), nan)
+    return out
+
+
+def shape_rows(maps: torch.Tensor, N: int, ids: torch.Tensor | None = None, n_ids: torch.Tensor | None = None,
+               hull: bool = True):
+    """(B, H, W) device id maps -> (shape, stats, hull) of `ops.labelmap_shape_stats`, `ops.labelmap_instance_stats` and
+    `ops.labelmap_hull(vertices=True)` (None without `hull`) for the same rows."""
+    shape = ops.labelmap_shape_stats(maps, ids, n_ids, N=N)
+    stats = ops.labelmap_instance_stats(maps, ids, n_ids, N=N)
+    return shape, stats, (ops.labelmap_hull(maps, ids, n_ids, N=N, stats=stats, vertices=True) if hull else None)
+
+
+def shape_trait_rows(maps: torch.Tensor, N: int) -> torch.Tensor:
+    """The device half of `return_shape_stats=True`: (B, H, W) device id maps whose instances are the ids 0 .. N-1 ->
+    (B, N, len(SHAPE_TRAITS)) float64, the traits of `shape_from_sums` in the order of SHAPE_TRAITS."""
+    if N == 0:
+        return torch.zeros(maps.shape[0], 0, len(SHAPE_TRAITS), dtype=torch.float64, device=maps.device)
+    traits = shape_from_sums(*shape_rows(maps, N))
+    return torch.stack([traits[name].to(torch.float64) for name in SHAPE_TRAITS], -1)
+
+
+def add_shape_traits(segments, rows) -> None:
+    """The host half of `return_shape_stats=True`: rows (n, len(SHAPE_TRAITS)) host values for the ids 0 .. n-1 -> one
+    key per trait on every entry: floats (NaN for an instance without a pixel), "crack_length" an int."""
+    for info in segments:
+        row = rows[int(info["id"])]
+        for name, v in zip(SHAPE_TRAITS, row):
+            info[name] = int(v) if name == "crack_length" else float(v)
+
+
+def shape_statistics(segmentation, n: int | None = None, ids=None, hull: bool = True, return_hull_vertices: bool = False) -> dict:
+    """The shape of every instance of one (H, W) id map or a (B, H, W) stack (maps, `n` and `ids` as for
+    `instance_statistics`): elongation and orientation from the second moments, perimeter and circularity, and with
+    `hull` the convex hull's area, solidity, largest Feret diameter, perimeter and convexity.
+
+    Returns the dict of device tensors `shape_from_sums` describes (every key, the hull's only with `hull`), each (..., N)
+    or (..., N, k) in the caller's order of ids; `return_hull_vertices=True` adds "hull_vertices" (..., N, K, 2) int32:
+    the hull's vertices (x, y) on the pixel-corner lattice, (-1, -1) past "n_hull_vertices" (`ops.labelmap_hull`).  An id
+    without a pixel has area 0 and NaN traits.  Eight launches of csrc/shape.hip (one of them the clearing of the result) and two of
+    csrc/instance_stats.hip whatever the number of instances; with `hull` one scalar is copied to the host to size the vertex block (DESIGN
+    section 40).  Not computed: Crofton perimeter, minimum Feret width, Euler number, Hu moments."""
+    if (n is None) == (ids is None):
+        raise ValueError("shape_statistics: give either n (ids 0 .. n-1) or ids")
+    seg = _id_maps(segmentation, "shape_statistics")
+    if return_hull_vertices and not hull:
+        raise ValueError("shape_statistics: return_hull_vertices needs hull=True")
+    back = None
+    if ids is not None:
+        raw = [int(v) for v in ids]
+        order = sorted(set(raw))
+        if len(order) != len(raw):
+            raise ValueError("shape_statistics: ids must be distinct")
+        back = [order.index(v) for v in raw]
+    if not torch.cuda.is_available():
+        raise _lib.Wm2fError("shape_statistics runs on a GPU only (no CPU fallback): no device is visible")
+    dev = seg.device if seg.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    maps = seg.to(dev)
+    maps = maps.unsqueeze(0) if seg.dim() == 2 else maps
+    B = maps.shape[0]
+    if ids is None:
+        shape, stats, hulls = shape_rows(maps, int(n), hull=hull)
+    else:
+        N = max(1, len(order))
+        ids_t = torch.tensor(order + [0] * (N - len(order)), dtype=torch.int32).expand(B, N).contiguous().to(dev)
+        n_ids = torch.full((B,), len(order), dtype=torch.int32).to(dev)
+        shape, stats, hulls = shape_rows(maps, N, ids_t, n_ids, hull=hull)
+        sel = torch.tensor(back, dtype=torch.int64).to(dev)  # the caller's order
+        shape, stats = shape[:, sel], stats[:, sel]
+        hulls = None if hulls is None else (hulls[0][:, sel], hulls[1][:, sel])
+    out = shape_from_sums(shape, stats, hulls)
+    if return_hull_vertices:
+        out["hull_vertices"] = hulls[1]
+    return {k: v[0] for k, v in out.items()} if seg.dim() == 2 else out
 
 
 @dataclasses.dataclass(frozen=True)

@@ -61,8 +61,9 @@ from .k2 import masked_xattn, masked_xattn_bf16_applies
 from .k3 import (attn_mask_build, mask_einsum, mask_einsum_attn_mask, mask_einsum_bf16, mask_einsum_bf16_bwd,
                  mask_einsum_bf16_bwd_applies, mask_einsum_bwd, mask_einsum_bwd_applies, nchw_to_pixel_major_bf16)
 from .labelmaps import (cell_grid_shape, coco_match, coco_match_min, labelmap_aim_points, labelmap_boundary,
-                        labelmap_cell_counts, labelmap_distance, labelmap_instance_stats, labelmap_nearest,
-                        labelmap_pair_counts, labelmap_to_masks, mask_pair_counts, panoptic_match, semantic_confusion_)
+                        labelmap_cell_counts, labelmap_distance, labelmap_hull, labelmap_instance_stats, labelmap_nearest,
+                        labelmap_pair_counts, labelmap_shape_stats, labelmap_to_masks, mask_pair_counts, panoptic_match,
+                        semantic_confusion_)
 from .layernorm import add_layernorm, add_layernorm_train, add_layernorm_train_applies
 from .loss import mask_loss_rows, point_sample, point_sample_levels, select_top_points
 from .matcher import lsa_batched, matcher_cost

@@ -188,6 +188,70 @@ def labelmap_aim_points(maps: torch.Tensor, d2: torch.Tensor, ids: torch.Tensor 
     return points
 
 
+SHAPE_COLUMNS = 10
+SHAPE_LDS_MAX_IDS = 1024          # wm2f_labelmap_shape_stats: accumulators in LDS up to this N, in the result above
+HULL_BOUND_ROWS = 4 * 1024 * 1024  # labelmap_hull: a row table of B N H rows is allocated as it is up to this size (96 MiB)
+
+
+def labelmap_shape_stats(maps: torch.Tensor, ids: torch.Tensor | None = None, n_ids: torch.Tensor | None = None,
+                         N: int | None = None) -> torch.Tensor:
+    """(B, H, W) id maps (fp32 with -1 background, int32 or uint8) -> (B, N, 10) int64
+    [area, sum_x, sum_y, sum_xx, sum_yy, sum_xy, sides, p_straight, p_diag, p_mixed] per id
+    (wm2f_labelmap_shape_stats): the raw moments of the pixel indices, the pixel sides between the instance and anything
+    else (the outside of the image included) and the three border-pixel counts of the 4-neighbourhood perimeter; an id
+    without a pixel has an all-zero row.  `ids` / `n_ids` / `N` as in `labelmap_instance_stats`."""
+    maps, dt, B, H, W = _id_maps(maps, "labelmap_shape_stats", "tensors")
+    ids, n_ids, N = _id_rows("labelmap_shape_stats", B, ids, n_ids, N)
+    shape = torch.empty(B, N, SHAPE_COLUMNS, device=maps.device, dtype=torch.int64)
+    if N == 0:
+        return shape
+    _launch("wm2f_labelmap_shape_stats", maps, _p(maps), dt, _p(ids), _p(n_ids), _p(shape), B, H, W, N, tag="shape_stats")
+    return shape
+
+
+def labelmap_hull(maps: torch.Tensor, ids: torch.Tensor | None = None, n_ids: torch.Tensor | None = None,
+                  N: int | None = None, stats: torch.Tensor | None = None, vertices: bool = False):
+    """(B, H, W) id maps (fp32 with -1 background, int32 or uint8) -> hull (B, N, 3) int64
+    [n_vertices, area2, feret2] per id (wm2f_labelmap_hull): the convex hull of the instance's pixel squares on the
+    corner lattice [0, W] x [0, H] -- its number of vertices, twice its area (exact) and the largest squared distance
+    between two vertices; [0, 0, 0] for an id without a pixel.  `ids` / `n_ids` / `N` as in `labelmap_instance_stats`;
+    `stats`: that op's result for the same maps and rows (computed here when None).
+
+    vertices=True returns (hull, points): points (B, N, K, 2) int32, a padded block with K = the largest n_vertices (at
+    least 1), row [b, r, k] the k-th vertex (x, y) of the instance and (-1, -1) past its n_vertices.  The vertices are
+    strictly convex, start at the smallest (y, then x) and go on towards increasing x (clockwise on the screen: with y
+    down every consecutive cross product is positive).
+
+    Host copies: none while the row table's bound B N H is at most HULL_BOUND_ROWS rows; above it copy 1, the sum of the
+    box heights (one int64), sizes the table.  vertices=True adds copy 2, the largest n_vertices (one int64), which
+    sizes the block.  The three scalars never need more than copy 1."""
+    maps, dt, B, H, W = _id_maps(maps, "labelmap_hull", "tensors")
+    ids, n_ids, N = _id_rows("labelmap_hull", B, ids, n_ids, N)
+    hull = torch.empty(B, N, 3, device=maps.device, dtype=torch.int64)
+    if N == 0:
+        return (hull, torch.empty(B, 0, 1, 2, device=maps.device, dtype=torch.int32)) if vertices else hull
+    if stats is None:
+        stats = labelmap_instance_stats(maps, ids, n_ids, N=N)
+    else:
+        stats = _req(stats, "stats", torch.int64)
+        if stats.shape != (B, N, 8):
+            raise ValueError(f"labelmap_hull: stats must be ({B}, {N}, 8), got {tuple(stats.shape)}")
+    rows = B * N * H
+    if rows > HULL_BOUND_ROWS:
+        heights = torch.where(stats[..., 0] > 0, stats[..., 4] - stats[..., 2] + 1, torch.zeros_like(stats[..., 0]))
+        rows = int(heights.sum())  # copy 1
+    ws = _workspace(load().wm2f_labelmap_hull_workspace(B, N, rows), maps.device, 8)
+    _launch("wm2f_labelmap_hull", maps, _p(maps), dt, _p(ids), _p(n_ids), _p(stats), _p(hull), _p(ws), rows, B, H, W, N,
+            tag="labelmap_hull")
+    if not vertices:
+        return hull
+    K = max(1, int(hull[..., 0].max()))  # copy 2
+    points = torch.empty(B, N, K, 2, device=maps.device, dtype=torch.int32)
+    _launch("wm2f_labelmap_hull_vertices", maps, _p(stats), _p(hull), _p(ws), rows, _p(points), B, H, N, K,
+            tag="labelmap_hull_vertices")
+    return hull, points
+
+
 # wm2f_labelmap_nearest's bounds and launch shape (include/wm2f.h), for callers and tests
 NEAREST_MAX_D2 = 1024 * 1024
 NEAREST_MIN_CHUNK_ROWS = 32   # columns pass: rows of a chunk, at least (exactly, for a small map taller than this)

@@ -108,7 +108,8 @@ class Mask2FormerInstancePostProcessor:
                                            overlap_mask_area_threshold: float = 0.8, target_sizes=None,
                                            return_coco_annotation: bool = False, return_binary_maps: bool = False,
                                            return_instance_stats: bool = False, return_polygons: bool = False,
-                                           clean=None, return_aim_points: bool = False, split=None):
+                                           clean=None, return_aim_points: bool = False, split=None,
+                                           return_shape_stats: bool = False):
         """`clean=CleanOptions(...)` (not an argument of the dependency; `instances.CleanOptions`) repairs every id map on
         the device before anything is taken from it: pieces below `min_area` dropped, with
         keep="largest" one connected piece per instance, with fill_holes=True enclosed background painted.  Entries of
@@ -137,7 +138,13 @@ class Mask2FormerInstancePostProcessor:
         free id and a new `segments_info` entry after the existing ones -- a copy of its parent's (label, score) with its
         own "id" and "split_from": the parent's id.  Statistics, aim points, the encoding, polygons and, with
         `return_binary_maps=True`, the stack (cut from the map, as with `clean=`) describe the split map.  split=None
-        changes nothing."""
+        changes nothing.
+        `return_shape_stats=True` (not an argument of the dependency) adds the shape traits of `instances.SHAPE_TRAITS`
+        -- "orientation", "axis_major_length", "axis_minor_length", "eccentricity", "perimeter", "crack_length" (an int),
+        "equivalent_diameter", "extent", "circularity", "area_convex", "solidity", "feret_diameter_max", "hull_perimeter",
+        "convexity"; floats, NaN for an instance without a pixel -- to every `segments_info` entry, as
+        `shape_statistics` gives them for the returned id map -- after painting, after `clean=` and `split=`, at the
+        target size -- once per distinct target size, with one more device-to-host copy."""
         if return_coco_annotation and return_binary_maps:
             raise ValueError("return_coco_annotation and return_binary_maps can not be both set to True.")
         if clean is not None:
@@ -188,6 +195,9 @@ class Mask2FormerInstancePostProcessor:
         new_id_all = torch.full((B, Q), -1, dtype=torch.int64, device=dev) if clean is not None else None
         aim_all = torch.zeros(B, n_ids, 4, dtype=torch.int32, device=dev) if return_aim_points else None
         split_all = torch.zeros(B, n_ids + 1, dtype=torch.int64, device=dev) if split is not None else None
+        if return_shape_stats:
+            from .instances import SHAPE_TRAITS, add_shape_traits, shape_trait_rows
+            shape_all = torch.zeros(B, n_ids, len(SHAPE_TRAITS), dtype=torch.float64, device=dev)
         for size in dict.fromkeys(sizes):  # one launch group per distinct target size
             rows = [i for i in range(B) if sizes[i] == size]
             ridx = torch.tensor(rows, device=dev)
@@ -218,6 +228,8 @@ class Mask2FormerInstancePostProcessor:
             if return_aim_points:
                 from .instances import aim_point_rows
                 aim_all[ridx] = aim_point_rows(seg, n_ids)
+            if return_shape_stats:
+                shape_all[ridx] = shape_trait_rows(seg, n_ids)
             if return_coco_annotation:  # one encode per distinct target size, whatever the number of instances
                 from .rle import encode_label_maps
                 for i, rles in zip(rows, encode_label_maps(seg, n=n_ids, format="hf")):
@@ -239,6 +251,8 @@ class Mask2FormerInstancePostProcessor:
         if return_aim_points:
             from .instances import add_aim_points
             aim_cpu = aim_all.cpu().numpy()
+        if return_shape_stats:
+            shape_cpu = shape_all.cpu().numpy()
         results = []
         for i in range(B):
             ks = torch.nonzero(keep_cpu[i]).flatten().tolist()
@@ -258,6 +272,8 @@ class Mask2FormerInstancePostProcessor:
                     seg_info["centroid"] = tuple(centroid[i][r]) if area[i][r] > 0 else None
             if return_aim_points:
                 add_aim_points(segments, aim_cpu[i])
+            if return_shape_stats:
+                add_shape_traits(segments, shape_cpu[i])
             segmentation = seg_out[i]
             if return_coco_annotation:
                 segmentation = rle_out[i]

@@ -154,7 +154,8 @@ def _tile_tables(results, T: int):
 
 
 def merge_tile_results(results, grid: TileGrid, merge_threshold=(1, 2), return_instance_stats: bool = False,
-                       clean=None, return_aim_points: bool = False, split=None) -> dict:
+                       clean=None, return_aim_points: bool = False, split=None,
+                       return_shape_stats: bool = False) -> dict:
     """Merge the per-tile results of `post_process_instance_segmentation(target_sizes=[(grid.th, grid.tw)] * T)` (tiles in
     `grid` order) into one image's result: {"segmentation": (H, W) int32 on the device with -1 background,
     "segments_info": [...]}, entries as `merged_segments_info` gives them.
@@ -178,7 +179,10 @@ def merge_tile_results(results, grid: TileGrid, merge_threshold=(1, 2), return_i
     `split=SplitOptions(...)` parts touching plants of the merged (and cleaned) field map as the post-processor's
     `split=` does -- the tile merge can only join instances, this parts them: a part split off gets
     the next free id and an entry after the merged ones, a copy of its parent's with its own "id" and "split_from";
-    statistics and aim points describe the split map."""
+    statistics and aim points describe the split map.
+
+    `return_shape_stats=True` adds the shape traits of the merged (cleaned, split) map's instances, as the post-processor
+    does; they travel in a device-to-host copy of their own, being float64."""
     results = list(results)
     T = grid.n_tiles
     if len(results) != T:
@@ -235,6 +239,10 @@ def merge_tile_results(results, grid: TileGrid, merge_threshold=(1, 2), return_i
     if return_aim_points and n_stats:
         from .instances import add_aim_points, aim_point_rows
         back.append(aim_point_rows(out.unsqueeze(0), n_rows).reshape(-1).to(torch.int64))
+    shape_dev = None
+    if return_shape_stats and n_stats:
+        from .instances import add_shape_traits, shape_trait_rows
+        shape_dev = shape_trait_rows(out.unsqueeze(0), n_rows)[0]
     host = torch.cat(back).cpu()  # the one device-to-host copy
     segments = merged_segments_info(host[:T * N].view(T, N).numpy(), int(host[T * N]), results)
     rest = host[T * N + 1:]
@@ -259,6 +267,8 @@ def merge_tile_results(results, grid: TileGrid, merge_threshold=(1, 2), return_i
         rest = rest[n_rows * 8:]
     if return_aim_points and segments:
         add_aim_points(segments, rest[:n_rows * 4].view(-1, 4).numpy())
+    if shape_dev is not None and segments:
+        add_shape_traits(segments, shape_dev.cpu().numpy())
     return {"segmentation": out, "segments_info": segments}
 
 
@@ -277,7 +287,7 @@ def _device_image(image) -> torch.Tensor:
 def segment_tiled(image, model, processor, tile: int = 1024, overlap: int = 256, batch_size: int = 4,
                   threshold: float = 0.5, mask_threshold: float = 0.5, overlap_mask_area_threshold: float = 0.8,
                   merge_threshold=(1, 2), return_instance_stats: bool = False, clean=None,
-                  return_aim_points: bool = False, split=None) -> dict:
+                  return_aim_points: bool = False, split=None, return_shape_stats: bool = False) -> dict:
     """Instance segmentation of an image of any size at native resolution: overlapping tiles (`tile_windows`), `batch_size`
     of them at a time through `processor(images=...)`, `model(pixel_values=...)` under no_grad and
     `processor.post_process_instance_segmentation(target_sizes=tile size)`, then `merge_tile_results`.  The image (PIL
@@ -287,7 +297,7 @@ def segment_tiled(image, model, processor, tile: int = 1024, overlap: int = 256,
     called with `images=` alone, so its own size settings decide how a tile is fed.  `clean=CleanOptions(...)` repairs
     the merged map (`merge_tile_results`); the tiles themselves are merged as predicted; `return_aim_points=True` adds the
     merged map's aim points and clearances there; `split=SplitOptions(...)` parts touching plants of the merged map
-    there.  Returns `merge_tile_results`'s dictionary."""
+    there; `return_shape_stats=True` adds the merged map's shape traits there.  Returns `merge_tile_results`'s dictionary."""
     batch_size = int(batch_size)
     if batch_size < 1:
         raise ValueError(f"segment_tiled: batch_size must be at least 1, got {batch_size}")
@@ -304,7 +314,8 @@ def segment_tiled(image, model, processor, tile: int = 1024, overlap: int = 256,
                 outputs, threshold=threshold, mask_threshold=mask_threshold,
                 overlap_mask_area_threshold=overlap_mask_area_threshold, target_sizes=[(grid.th, grid.tw)] * len(batch))
     return merge_tile_results(results, grid, merge_threshold=merge_threshold, return_instance_stats=return_instance_stats,
-                              clean=clean, return_aim_points=return_aim_points, split=split)
+                              clean=clean, return_aim_points=return_aim_points, split=split,
+                              return_shape_stats=return_shape_stats)
 
 
 # ---------------------------------------------------------------------------------------------- the semantic route
