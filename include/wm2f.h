@@ -1667,6 +1667,42 @@ int wm2f_labelmap_hull(const void* map, int dtype, const int32_t* ids, const int
 int wm2f_labelmap_hull_vertices(const int64_t* stats, const int64_t* hull, const void* workspace, int64_t rows,
                                 int32_t* vertices, int B, int H, int N, int K, void* stream);
 
+/* ---- crop rows: the Hough vote of the voting pixels, instances against a set of lines -----------
+ * Positions along a direction are integers in units of 2^-14 pixel.  A direction is a pair (c, s) = (rint(cos th 2^14),
+ * rint(sin th 2^14)) with th in [0, pi), so s >= 0: th is the direction of the row NORMAL.  A pixel (x, y) -- indices,
+ * not centres -- lies at rho = x c + y s + off with off = -min(0, c) (W - 1), which makes rho >= 0 over the image.  At
+ * the limits every product is at most 2^28 and rho is below 2^29.  tests/rows_reference.py restates every rule in numpy.
+ *
+ * wm2f_labelmap_row_votes: map (B, H, W) fp32 / int32 / uint8, decoded as an id of [0, N) or nothing; vote (B, N) uint8:
+ *   a pixel of id i votes when vote[b][i] != 0.  cs (T, 2) int32: the directions, taken as given (the host computes
+ *   th_t = pi t / T; the kernel does no trigonometry).  A voting pixel's bin for direction t is
+ *   (x c_t + y s_t + off_t) >> shift: bins of 2^(shift - 14) pixels, R = (((W + H - 2) << 14) >> shift) + 1 of them.
+ *   acc (B, T, R) int32 <- the vote counts; energy (B, T) int64 <- the sum over the bins of acc^2 (below 2^44).  Both
+ *   are written in full: no clearing needed.
+ *   Three launches: clear; votes (64 x 64 pixel tiles, the voters compacted once, LDS histograms of 16 directions x 128
+ *   bins, their non-zero bins added to acc by integer atomics; one read of the map when there are at least 2048 tiles,
+ *   up to ceil(T / 16) reads of a small one); energy (a workgroup per row of acc).
+ *   Limits: 1 <= T <= 1024, H, W <= 16384, B <= 32, N <= 4096, else WM2F_EUNSUPPORTED; a size below 1 or a shift outside
+ *   [14, 20]: WM2F_EINVAL; both are decided before a pointer is looked at.
+ *
+ * wm2f_labelmap_row_bands: map, ids / n_ids / N as wm2f_labelmap_instance_stats takes them.  line (B, 4) int32
+ *   [c, s, off, K] per image; rho (B, Kmax) int32: the positions of the image's rows, ascending, the first K valid
+ *   (K is clamped to [0, Kmax]; rho may be NULL when Kmax = 0); band >= 0: a half-width, same unit.
+ *   A pixel is IN A BAND when |rho(p) - rho_k| <= band for the row k nearest to it; with K = 0 no pixel is.
+ *   counts (B, N, 3) int64 per instance: [0] its pixels  [1] those in a band  [2] the sum of rho(p) over them (below
+ *   2^58); an id without a pixel has an all-zero row.  zone (B, H, W) uint8, optional: 1 for a pixel in a band, 0
+ *   otherwise, written for every pixel whatever its id.
+ *   Two launches (clear; one read of the map, the row positions in LDS and a binary search per pixel).  Accumulators
+ *   are in LDS up to N = 1024, in the result above.
+ *   Limits: Kmax <= 1024, H, W <= 16384, B <= 32, N <= 4096, else WM2F_EUNSUPPORTED, reported before a pointer is looked
+ *   at; a size below 1, Kmax or band below 0, a null pointer, ids without n_ids or another dtype: WM2F_EINVAL.
+ * Integer atomics only: bit-identical from run to run.  No call allocates, keeps state or waits for the device. */
+int wm2f_labelmap_row_votes(const void* map, int dtype, const uint8_t* vote, const int32_t* cs, int32_t* acc,
+                            int64_t* energy, int B, int H, int W, int N, int T, int shift, void* stream);
+int wm2f_labelmap_row_bands(const void* map, int dtype, const int32_t* ids, const int32_t* n_ids, const int32_t* line,
+                            const int32_t* rho, int64_t* counts, uint8_t* zone, int B, int H, int W, int N, int Kmax,
+                            int band, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ from .instances import (CleanOptions, SplitOptions, aim_points, boundary_dilatio
                         clean_label_maps, distance_maps, grow_label_maps, instance_statistics, nearest_instance_maps,
                         shape_from_sums, shape_statistics, split_label_maps)
 from .treatment import TreatmentOptions, load_treatment_grid, save_treatment_grid, treatment_grid  # noqa: F401
+from .rows import RowOptions, annotate_rows, crop_rows  # noqa: F401
 from .rle import (coco_results, decode_rle, encode_label_maps, rle_from_string, rle_to_string,  # noqa: F401
                   save_coco_results)
 from .contours import (instance_polygons, save_via_annotations, trace_label_maps, via_annotations)  # noqa: F401

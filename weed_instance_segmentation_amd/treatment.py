@@ -24,6 +24,7 @@ import torch
 
 from . import _lib, ops
 from .instances import _id_maps, nearest_rows, squared_cap
+from .rows import ZONES, row_zone
 
 FORMAT = "wm2f-treatment-grid"
 VERSION = 1
@@ -112,7 +113,7 @@ def on_cell_area(cells, H: int, W: int, cell, offset) -> int:
     return int((np.asarray(cells, np.int64) * rows[:, None] * cols[None, :]).sum())
 
 
-def treatment_grid(result: dict, options: TreatmentOptions) -> dict:
+def treatment_grid(result: dict, options: TreatmentOptions, rows: dict | None = None, zone: str | None = None) -> dict:
     """The sprayer grid of one segmentation result (see the module's text).  `result["segmentation"]` is an (H, W) id
     map, host or device, whose instances are the `id`s of `result["segments_info"]`; an id of the map that has no entry
     is a plant of no class: it keeps its pixels and is neither treated nor protected.
@@ -122,9 +123,19 @@ def treatment_grid(result: dict, options: TreatmentOptions) -> dict:
     a float) and `treated_fraction_exact` (the same as a Fraction), `instances` (per target instance `id`, `label_id`,
     `treated`: the fraction of its own pixels that lie in on-cells, and `vetoed_fraction`: the fraction within the
     protection distance; NaN for an instance without a pixel), and the geometry: `cell`, `offset`, `image_size` (H, W),
-    `grid_size` (GH, GW).  The arrays are host numpy arrays."""
+    `grid_size` (GH, GW).  The arrays are host numpy arrays.
+
+    `zone` restricts the treatment to one side of the crop rows `rows` (`crop_rows` of the same result, DESIGN section
+    41): "inter_row" keeps a grown target pixel only outside the row bands (a hoe between the rows), "intra_row" only
+    inside them (an in-row tool).  The grown map is masked before the cells are counted; `treated` keeps its meaning.
+    With `zone` None nothing changes, whatever `rows` is."""
     if not isinstance(options, TreatmentOptions):
         raise TypeError(f"treatment_grid: options must be a TreatmentOptions, got {type(options).__name__}")
+    if zone is not None:
+        if zone not in ZONES:
+            raise ValueError(f"treatment_grid: zone must be one of {ZONES} or None, got {zone!r}")
+        if not isinstance(rows, dict) or not rows.get("found"):
+            raise ValueError("treatment_grid: zone needs rows that were found (crop_rows(...)['found'] is True)")
     if not isinstance(result, dict) or "segmentation" not in result or "segments_info" not in result:
         raise ValueError("treatment_grid: result must be a dict with 'segmentation' and 'segments_info'")
     seg = _id_maps(result["segmentation"], "treatment_grid")
@@ -152,6 +163,9 @@ def treatment_grid(result: dict, options: TreatmentOptions) -> dict:
     veto_d2, veto_max = None, squared_cap(options.protect, "treatment_grid")
     if protected.any():
         _, veto_d2 = nearest_rows(maps, N, veto_max, protected[:N], False)
+    if zone is not None:
+        in_band = row_zone(maps, rows) != 0
+        grown = torch.where((in_band if zone == "intra_row" else ~in_band).unsqueeze(0), grown, torch.full_like(grown, -1))
     group = torch.from_numpy(np.where(target, 0, 255).astype(np.uint8)).to(dev).unsqueeze(0)
     counts = ops.labelmap_cell_counts(grown, group, 1, options.cell, options.offset, veto_d2, veto_max)[0]
     cells_dev = counts[..., 0] >= int(options.min_pixels)
