@@ -160,6 +160,7 @@ def test_backbone_stem_route_and_determinism(ops, monkeypatch):
     (F.conv2d + bias_relu_maxpool) to 1e-5 max |ref|, two forwards bit-identical, and the split cache follows the fold."""
     from weed_instance_segmentation_amd import Mask2FormerConfig
     from weed_instance_segmentation_amd.backbone_resnet import build_backbone
+    from weed_instance_segmentation_amd.derived import derived_peek
     torch.manual_seed(0)
     cfg = dict(Mask2FormerConfig(num_labels=3).backbone_config)
     cfg["out_features"] = ["stem", "stage1", "stage2", "stage3", "stage4"]
@@ -172,9 +173,9 @@ def test_backbone_stem_route_and_determinism(ops, monkeypatch):
     emb = net.embedder.embedder
     with torch.no_grad():
         got = net(x)
-        split0 = emb._wm2f_split["stem"][2]
+        split0 = derived_peek(emb, "stem")
         again = net(x)
-        assert emb._wm2f_split["stem"][2] is split0
+        assert derived_peek(emb, "stem") is split0
         with monkeypatch.context() as mp:
             mp.setattr(ops, "stem_conv_pool_applies", lambda *a: False)
             ref = net(x)
@@ -187,5 +188,5 @@ def test_backbone_stem_route_and_determinism(ops, monkeypatch):
     with torch.no_grad():
         emb.normalization.running_var.mul_(3.0)  # a new BatchNorm fold
         got2 = net(x)
-    assert emb._wm2f_split["stem"][2] is not split0
+    assert derived_peek(emb, "stem") is not split0
     assert not torch.equal(got2[0], got[0])

@@ -274,6 +274,7 @@ def test_row_ordered_split_is_the_split_of_the_permuted_weight(ops):
 
 # ------------------------------------------------------------------------------------------------------------ 7. cache
 def test_cached_splits_follow_in_place_weight_updates(ops):
+    from weed_instance_segmentation_amd.derived import derived_peek
     torch.manual_seed(3)
     owner = torch.nn.Module()
     fc1, fc2 = torch.nn.Linear(D, 1024).cuda(), torch.nn.Linear(1024, D).cuda()
@@ -292,7 +293,7 @@ def test_cached_splits_follow_in_place_weight_updates(ops):
 
     first = cached()
     assert torch.equal(first, fresh())
-    kept = owner.__dict__["_wm2f_split"]["fc1_ffn"][2]
+    kept = derived_peek(owner, "fc1_ffn")
     assert ops.split_weight_rows_cached(owner, "fc1_ffn", fc1.weight) is kept  # no re-split without a change
     for lin in (fc1, fc2):
         before = cached()

@@ -15,6 +15,7 @@ import torch  # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import weed_instance_segmentation_amd as W  # noqa: E402
 from weed_instance_segmentation_amd import backbone_resnet as R  # noqa: E402
+from weed_instance_segmentation_amd.derived import derived_peek  # noqa: E402
 
 
 def timed(fn, steps=5, warmup=2):
@@ -43,11 +44,12 @@ def main():
         out = bb(x)
         res["stock_vs_fused_max_rel"] = max(float((a - b).abs().max() / a.abs().max()) for a, b in zip(ref, out))
         res["stock_ms"] = timed(lambda: bb(x))
-        # channels_last: folded weights are cached .contiguous(); convert the cache entries after the first call
+        # channels_last: folded weights are cached .contiguous(); give the cached tensors the other layout after the first call
         xcl = x.contiguous(memory_format=torch.channels_last)
         for m in bb.modules():
-            if hasattr(m, "_fold") and "w" in m._fold:
-                m._fold["w"] = m._fold["w"].contiguous(memory_format=torch.channels_last)
+            fold = derived_peek(m, "fold")
+            if fold is not None:
+                fold[0].data = fold[0].contiguous(memory_format=torch.channels_last)
         out = bb(xcl)
         res["nhwc_out_is_channels_last"] = bool(out[-1].is_contiguous(memory_format=torch.channels_last))
         res["nhwc_vs_fused_max_rel"] = max(float((a - b).abs().max() / a.abs().max()) for a, b in zip(ref, out))

@@ -26,6 +26,7 @@ from .augment import (AugmentParams, CopyPaste, CopyPasteParams, PhotometricPara
 from .data import CopyPasteBatcher, copy_paste  # noqa: F401
 from .visualize import (build_overlay_tables, convert_gt_map_to_result, render_label_overlay,  # noqa: F401
                         render_segmentation, render_segmentations, save_comparison)
+from .derived import drop_derived  # noqa: F401
 from .precision import get_inference_precision, inference_precision, set_inference_precision  # noqa: F401
 from .tiling import (TileGrid, blend_tile_scores, merge_tile_results, segment_tiled, segment_tiled_semantic,  # noqa: F401
                      tile_windows)

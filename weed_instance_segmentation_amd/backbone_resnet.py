@@ -12,6 +12,7 @@ import torch
 from torch import nn
 
 from . import ops
+from .derived import derived
 
 
 def _infer_gpu(x: torch.Tensor) -> bool:
@@ -38,18 +39,14 @@ def _split_3x3(conv: nn.Conv2d, x: torch.Tensor, w: torch.Tensor) -> bool:
             and ops.conv3x3_applies(x, w, conv.stride[0]))
 
 
-def _folded(conv: nn.Conv2d, bn: nn.BatchNorm2d, cache: dict):
+def _folded(layer: nn.Module, conv: nn.Conv2d, bn: nn.BatchNorm2d):
     """Inference-time BatchNorm folding: conv(x, w) * g/sqrt(v+eps) + (b - m*g/sqrt(v+eps)) == conv(x, w', b').
-    Cached per (weight / statistics version), so the fold is recomputed only after the parameters change."""
-    key = (conv.weight._version, bn.weight._version, bn.bias._version, bn.running_mean._version,
-           bn.running_var._version, conv.weight.device, conv.weight.dtype)
-    if cache.get("key") != key:
-        with torch.no_grad():
-            scale = bn.weight * torch.rsqrt(bn.running_var + bn.eps)
-            cache["w"] = (conv.weight * scale[:, None, None, None]).contiguous()
-            cache["b"] = (bn.bias - bn.running_mean * scale).contiguous()
-            cache["key"] = key
-    return cache["w"], cache["b"]
+    Derived for `layer`, the owner of conv and bn, so redone only after a parameter or statistic changes."""
+    def make():
+        scale = bn.weight * torch.rsqrt(bn.running_var + bn.eps)
+        return (conv.weight * scale[:, None, None, None]).contiguous(), (bn.bias - bn.running_mean * scale).contiguous()
+    p, s = bn._parameters, bn._buffers  # (read directly: five Module.__getattr__ calls cost more than the lookup itself)
+    return derived(layer, "fold", (conv._parameters["weight"], p["weight"], p["bias"], s["running_mean"], s["running_var"]), make)
 
 
 class ConvLayer(nn.Module):
@@ -58,7 +55,6 @@ class ConvLayer(nn.Module):
         self.convolution = nn.Conv2d(cin, cout, kernel_size, stride, kernel_size // 2, bias=False)
         self.normalization = nn.BatchNorm2d(cout)
         self.activation = nn.ReLU() if activation else nn.Identity()
-        self._fold: dict = {}
 
     def forward(self, x, residual=None, extra_bias=None, force_relu=False):
         """`residual` / `extra_bias` / `force_relu` let a bottleneck fold its shortcut add and final ReLU
@@ -67,12 +63,12 @@ class ConvLayer(nn.Module):
         relu = force_relu or isinstance(self.activation, nn.ReLU)
         if not self.training and not torch.is_grad_enabled():
             # inference: convolution with folded BatchNorm statistics; bias (+ residual) + ReLU in ONE pass
-            w, b = _folded(c, self.normalization, self._fold)
+            w, b = _folded(self, c, self.normalization)
             if extra_bias is not None:
                 b = b + extra_bias
             if _split_1x1(c, x, w) and (residual is None or relu):
                 # 1x1: one split-bf16 GEMM with bias (+ residual) + ReLU in its store
-                ws = ops.split_weight_cached(self, "conv", w.view(w.shape[0], w.shape[1]), base=w)
+                ws = ops.split_weight_cached(self, "conv", w)
                 return ops.conv1x1(x, w, b, residual, relu, c.stride[0], w_split=ws)
             if _split_3x3(c, x, w) and residual is None and relu:
                 # 3x3: one split-bf16 implicit GEMM with bias + ReLU in its store; the folded w is the cache's identity,
@@ -100,7 +96,6 @@ class ShortCut(nn.Module):
         super().__init__()
         self.convolution = nn.Conv2d(cin, cout, 1, stride, bias=False)
         self.normalization = nn.BatchNorm2d(cout)
-        self._fold: dict = {}
 
     def forward(self, x):
         return self.normalization(self.convolution(x))
@@ -109,9 +104,9 @@ class ShortCut(nn.Module):
         """Inference: the shortcut convolution WITHOUT its folded bias, and that bias (the bottleneck adds it
         in its fused epilogue)."""
         c = self.convolution
-        w, b = _folded(c, self.normalization, self._fold)
+        w, b = _folded(self, c, self.normalization)
         if _split_1x1(c, x, w):
-            ws = ops.split_weight_cached(self, "conv", w.view(w.shape[0], w.shape[1]), base=w)
+            ws = ops.split_weight_cached(self, "conv", w)
             return ops.conv1x1(x, w, None, stride=c.stride[0], w_split=ws), b
         return torch.nn.functional.conv2d(x, w, None, c.stride), b
 
@@ -160,7 +155,7 @@ class _Embedder(nn.Module):
                 and (pool.kernel_size, pool.stride, pool.padding, pool.dilation, pool.ceil_mode) == (3, 2, 1, 1, False)):
             # inference: bias + ReLU + 3x3 / 2 max pool in one pass over the raw convolution output
             c = e.convolution
-            w, b = _folded(c, e.normalization, e._fold)
+            w, b = _folded(e, c, e.normalization)
             if ((c.stride, c.padding, c.dilation, c.groups) == ((2, 2), (3, 3), (1, 1), 1)
                     and ops.stem_conv_pool_applies(x, w)):
                 # 7x7 / 2 convolution, bias, ReLU and pool in one split-bf16 kernel; the folded w is the cache's identity,

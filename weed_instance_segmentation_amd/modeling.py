@@ -33,6 +33,7 @@ from torch import nn
 from . import ops
 from .backbone_resnet import build_backbone
 from .configuration import Mask2FormerConfig
+from .derived import derived
 from .loss import Mask2FormerLoss
 
 
@@ -105,7 +106,6 @@ class MSDeformAttn(nn.Module):
         self.attention_weights = nn.Linear(embed_dim, num_heads * n_levels * n_points)
         self.value_proj = nn.Linear(embed_dim, embed_dim)
         self.output_proj = nn.Linear(embed_dim, embed_dim)
-        self._cat: dict = {}
 
     def _offsets_logits_weight(self, lanes: bool = False):
         """[sampling_offsets ; attention_weights] as ONE (288, 256) projection for the inference path:
@@ -113,18 +113,15 @@ class MSDeformAttn(nn.Module):
         lanes=True: the same rows in the kernel's record order (ops.k1_lane_order, wm2f_msdeform_fused_lanes_fwd) -- a row
         permutation of the weight, nothing else."""
         so, aw = self.sampling_offsets, self.attention_weights
-        key = (so.weight._version, so.bias._version, aw.weight._version, aw.bias._version, so.weight.device)
-        if self._cat.get("key") != key:
-            with torch.no_grad():
-                w, b = torch.cat([so.weight, aw.weight], 0).contiguous(), torch.cat([so.bias, aw.bias], 0).contiguous()
-                self._cat = dict(key=key, w=w, b=b)
-                H, L, P = self.n_heads, self.n_levels, self.n_points
-                if L == 3 and P == 4:
-                    idx = ops.k1_lane_order(H).to(w.device)
-                    self._cat.update(w_lanes=w[idx].contiguous(), b_lanes=b[idx].contiguous())
-        if lanes:
-            return self._cat["w_lanes"], self._cat["b_lanes"]
-        return self._cat["w"], self._cat["b"]
+
+        def make():
+            w, b = torch.cat([so.weight, aw.weight], 0), torch.cat([so.bias, aw.bias], 0)
+            if lanes:
+                idx = ops.k1_lane_order(self.n_heads).to(w.device)
+                w, b = w[idx], b[idx]
+            return w.contiguous(), b.contiguous()
+        return derived(self, "offsets_logits_cat_lanes" if lanes else "offsets_logits_cat",
+                       (so.weight, so.bias, aw.weight, aw.bias), make)
 
     def forward(self, hidden, pos, ref, level_hw, hp=None, hidden_lp=None, project=True):
         """hidden (B,S,C); pos (S,C) shared by the batch; ref (S,L,2); hp = hidden + pos if already known (training: possibly in
@@ -171,9 +168,7 @@ class MSDeformAttn(nn.Module):
             else:
                 value = vp(hidden).view(B, S, H, C // H)
             if hm_rows:
-                if "ws_lanes" not in self._cat:
-                    self._cat["ws_lanes"] = ops.split_weight(w)
-                rows = ops.token_linear(hp, w, b, out_group=36, w_split=self._cat["ws_lanes"])
+                rows = ops.token_linear(hp, w, b, out_group=36, w_split=ops.split_weight_cached(self, "offsets_logits_lanes", w))
             else:
                 rows = F.linear(hp, w, b)
             out = ops.ms_deform_attn_fused_lanes(value, level_hw, rows, H, head_major=hm_rows, value_head_major=hm_value,
@@ -381,7 +376,7 @@ class Mask2FormerPixelDecoder(nn.Module):
             outs.append(layer(out))
         if norm is not None:
             mp = self.mask_projection
-            ws = ops.split_weight_cached(self, "mask_projection", mp.weight.view(mp.weight.shape[0], mp.weight.shape[1]), base=mp.weight)
+            ws = ops.split_weight_cached(self, "mask_projection", mp.weight)
             return ops.conv1x1_gn(outs[-1], mp.weight, mp.bias, w_split=ws, norm=norm), outs[:3]
         if fast:
             return self._conv1x1(self.mask_projection, outs[-1], "mask_projection"), outs[:3]
@@ -402,7 +397,7 @@ class Mask2FormerPixelDecoder(nn.Module):
         statistics pass, which for the input projections also adds the bias (bias=False)."""
         w = conv.weight
         if ops.CONV_GN_FUSED and ops.conv_group_stats_applies(w.shape[0], groups) and self._split1x1(conv, x):
-            ws = ops.split_weight_cached(self, name, w.view(w.shape[0], w.shape[1]), base=w)
+            ws = ops.split_weight_cached(self, name, w)
             return ops.conv1x1_gn(x, w, conv.bias, w_split=ws, stats_groups=groups)
         return self._conv1x1(conv, x, name, bias=bias), None
 
@@ -410,9 +405,8 @@ class Mask2FormerPixelDecoder(nn.Module):
         """Inference: a 1x1 convolution on the split-bf16 kernel (ops.conv1x1) where it applies, else the module's own
         convolution; bias=False leaves the module's bias out (a later pass adds it)."""
         w = conv.weight
-        if (ops.CONV1X1_SPLIT and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
-                and conv.groups == 1 and ops.conv1x1_applies(x, w)):
-            ws = ops.split_weight_cached(self, name, w.view(w.shape[0], w.shape[1]), base=w)
+        if self._split1x1(conv, x):
+            ws = ops.split_weight_cached(self, name, w)
             return ops.conv1x1(x, w, conv.bias if bias else None, w_split=ws)
         return F.conv2d(x, w, conv.bias if bias else None, conv.stride, conv.padding)
 
@@ -476,15 +470,11 @@ class SelfAttention(nn.Module):
 
     def _qk_weight(self):
         """Inference: [q_proj * scaling ; k_proj] as ONE (2E, E) projection of h + qpos (two GEMM launches and the scaling pass
-        become one GEMM); cached per parameter version."""
+        become one GEMM)."""
         qp, kp = self.q_proj, self.k_proj
-        key = (qp.weight._version, qp.bias._version, kp.weight._version, kp.bias._version, qp.weight.device, qp.weight.dtype)
-        c = self.__dict__.setdefault("_qk", {})
-        if c.get("key") != key:
-            with torch.no_grad():
-                c.update(key=key, w=torch.cat([qp.weight * self.scaling, kp.weight], 0).contiguous(),
-                         b=torch.cat([qp.bias * self.scaling, kp.bias], 0).contiguous())
-        return c["w"], c["b"]
+        return derived(self, "qk", (qp.weight, qp.bias, kp.weight, kp.bias),
+                       lambda: (torch.cat([qp.weight * self.scaling, kp.weight], 0).contiguous(),
+                                torch.cat([qp.bias * self.scaling, kp.bias], 0).contiguous()))
 
     def forward(self, h, qpos):
         B, Q, E = h.shape
@@ -535,15 +525,9 @@ class MaskedCrossAttention(nn.Module):
         return k, v
 
     def _q_weight(self):
-        """Inference: the query projection with 1 / sqrt(head_dim) folded in (one launch less per layer); cached per version."""
-        E = self.embed_dim
-        key = (self.in_proj_weight._version, self.in_proj_bias._version, self.in_proj_weight.device, self.in_proj_weight.dtype)
-        c = self.__dict__.setdefault("_qw", {})
-        if c.get("key") != key:
-            with torch.no_grad():
-                sc = 1.0 / math.sqrt(self.head_dim)
-                c.update(key=key, w=(self.in_proj_weight[:E] * sc).contiguous(), b=(self.in_proj_bias[:E] * sc).contiguous())
-        return c["w"], c["b"]
+        """Inference: the query projection with 1 / sqrt(head_dim) folded in (one launch less per layer)."""
+        E, sc, w, b = self.embed_dim, 1.0 / math.sqrt(self.head_dim), self.in_proj_weight, self.in_proj_bias
+        return derived(self, "q", (w, b), lambda: ((w[:E] * sc).contiguous(), (b[:E] * sc).contiguous()))
 
     def forward(self, query_in, k, v, mask, row_open):
         E = self.embed_dim

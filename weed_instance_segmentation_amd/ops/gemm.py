@@ -1,12 +1,11 @@
 """The split-bf16 GEMMs and convolutions, and the token Linears' weight gradient."""
 from __future__ import annotations
 
-import weakref
-
 import torch
 
 from .. import ops as _flags  # the package itself: SPLIT_PRECISION is assigned on it and read when a split kernel is called
 from .._lib import load
+from ..derived import derived
 from ._core import _launch, _p, _req
 from .fused import bias_act_, bias_relu_maxpool
 
@@ -44,6 +43,12 @@ def split_weight(weight: torch.Tensor) -> torch.Tensor:
     return ws
 
 
+def _check_split(w_split: torch.Tensor, nbytes: int, x: torch.Tensor, message: str) -> None:
+    """A caller's split weight: `nbytes` bytes of uint8 on x's device, or ValueError(message)."""
+    if w_split.dtype != torch.uint8 or w_split.numel() != nbytes or w_split.device != x.device:
+        raise ValueError(message)
+
+
 ROWS_NATURAL, ROWS_FFN = 0, 1  # WM2F_ROWS_* of include/wm2f.h
 
 
@@ -65,36 +70,23 @@ def split_weight_rows(weight: torch.Tensor, row_order: int = ROWS_FFN) -> torch.
     return ws
 
 
-def _split_cached(owner, name: str, weight: torch.Tensor, ident: torch.Tensor, make) -> torch.Tensor:
-    """make(weight), kept in owner.__dict__ under `name` and redone when `ident` (held by weak reference) is another
-    tensor or has another version, or the weight another storage, device or shape."""
-    c = owner.__dict__.setdefault("_wm2f_split", {})
-    key = (ident._version, weight.data_ptr(), weight.device, tuple(weight.shape))
-    hit = c.get(name)
-    if hit is None or hit[0]() is not ident or hit[1] != key:
-        hit = (weakref.ref(ident), key, make(weight))
-        c[name] = hit
-    return hit[2]
-
-
 def split_weight_cached(owner, name: str, weight: torch.Tensor, base: torch.Tensor | None = None,
                         tap_major: bool = False) -> torch.Tensor:
-    """split_weight(weight), kept in owner.__dict__ under `name` and redone when the weight changes: another tensor (held by
-    weak reference: `base` when weight is a fresh view of it each call), another version, storage or device.
+    """split_weight(weight), cached for `owner` under `name` by derived() and redone when the weight changes (`base` when
+    weight is a fresh view of it each call).  A 1x1 convolution kernel (N, K, 1, 1) is split as (N, K).
     tap_major=True: weight is a convolution kernel, split in the K order its kernel reads: (N, Cin, 3, 3) as conv3x3 does
     (split_weight_3x3), (64, Cin, 7, 7) as stem_conv_pool does (split_weight_stem)."""
     if not tap_major:
-        make = split_weight
+        make = lambda: split_weight(weight.view(weight.shape[0], -1) if weight.dim() == 4 else weight)
     else:
-        make = split_weight_stem if tuple(weight.shape[2:]) == (7, 7) else split_weight_3x3
-    return _split_cached(owner, name, weight, weight if base is None else base, make)
+        make = lambda: (split_weight_stem if tuple(weight.shape[2:]) == (7, 7) else split_weight_3x3)(weight)
+    return derived(owner, name, (weight if base is None else base,), make)
 
 
 def split_weight_rows_cached(owner, name: str, weight: torch.Tensor, row_order: int = ROWS_FFN) -> torch.Tensor:
-    """split_weight_rows(weight, row_order), cached as split_weight_cached caches split_weight: keyed on the parameter
-    itself (version, storage, device) under `name`, which must be a name of its own (the plain split of the same weight
-    lives under another)."""
-    return _split_cached(owner, name, weight, weight, lambda w: split_weight_rows(w, row_order))
+    """split_weight_rows(weight, row_order), cached as split_weight_cached caches split_weight, under a `name` of its own
+    (the plain split of the same weight lives under another)."""
+    return derived(owner, name, (weight,), lambda: split_weight_rows(weight, row_order))
 
 
 def split_weight_3x3(weight: torch.Tensor) -> torch.Tensor:
@@ -142,8 +134,8 @@ def token_linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, relu
     if split:
         if w_split is None:
             w_split = split_weight(weight)
-        elif w_split.dtype != torch.uint8 or w_split.numel() != N * K * 6 or w_split.device != x.device:
-            raise ValueError("token_linear: w_split is not split_weight(weight)")
+        else:
+            _check_split(w_split, N * K * 6, x, "token_linear: w_split is not split_weight(weight)")
         pieces, lvl = _split_pieces()
         _launch("wm2f_token_linear_split_fwd_p", x, _p(x), _p(w_split), _p(bias), _p(residual), _p(gamma), _p(beta), _p(pos),
                 _p(out), _p(out_pos), M, K, N, 1 if relu else 0, pos_rows, eps, int(out_group), pieces,
@@ -198,8 +190,8 @@ def token_ffn(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Ten
             raise ValueError("token_ffn: pos rows do not divide the token count")
         out_pos = torch.empty_like(out)
     for ws, what in ((w1_split, "w1_split is not split_weight_rows(w1, ROWS_FFN)"), (w2_split, "w2_split is not split_weight(w2)")):
-        if ws is not None and (ws.dtype != torch.uint8 or ws.numel() != F_ * K * 6 or ws.device != x.device):
-            raise ValueError("token_ffn: " + what)
+        if ws is not None:
+            _check_split(ws, F_ * K * 6, x, "token_ffn: " + what)
     if w1_split is None:
         w1_split = split_weight_rows(w1, ROWS_FFN)
     if w2_split is None:
@@ -262,8 +254,8 @@ def conv1x1(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = N
             raise ValueError(f"conv1x1: residual {tuple(residual.shape)}, output ({B}, {N}, {Ho}, {Wo})")
     if w_split is None:
         w_split = split_weight(w2)
-    elif w_split.dtype != torch.uint8 or w_split.numel() != N * K * 6 or w_split.device != x.device:
-        raise ValueError("conv1x1: w_split is not split_weight(weight)")
+    else:
+        _check_split(w_split, N * K * 6, x, "conv1x1: w_split is not split_weight(weight)")
     out = torch.empty(B, N, Ho, Wo, device=x.device, dtype=torch.float32)
     pieces, lvl = _split_pieces()
     _launch("wm2f_conv1x1_split_fwd_p", x, _p(x), _p(w_split), _p(bias), _p(residual), _p(out), B, K, N, H, W, int(stride),
@@ -303,8 +295,8 @@ def conv1x1_gn(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None 
             raise ValueError(f"conv1x1_gn: bias {tuple(bias.shape)} for {N} channels")
     if w_split is None:
         w_split = split_weight(w2)
-    elif w_split.dtype != torch.uint8 or w_split.numel() != N * K * 6 or w_split.device != x.device:
-        raise ValueError("conv1x1_gn: w_split is not split_weight(weight)")
+    else:
+        _check_split(w_split, N * K * 6, x, "conv1x1_gn: w_split is not split_weight(weight)")
     stats = nstats = ngamma = nbeta = None
     nG, neps, nrelu = 0, 0.0, False
     if norm is not None:
@@ -335,8 +327,8 @@ def conv3x3_stats(x: torch.Tensor, weight: torch.Tensor, groups: int, stride: in
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     if w_split is None:
         w_split = split_weight_3x3(_req(weight, "weight"))
-    elif w_split.dtype != torch.uint8 or w_split.numel() != N * 9 * Cin * 6 or w_split.device != x.device:
-        raise ValueError("conv3x3_stats: w_split is not split_weight_3x3(weight)")
+    else:
+        _check_split(w_split, N * 9 * Cin * 6, x, "conv3x3_stats: w_split is not split_weight_3x3(weight)")
     out = torch.empty(B, N, Ho, Wo, device=x.device, dtype=torch.float32)
     stats = torch.empty(B, int(groups), 2, device=x.device, dtype=torch.float64)
     pieces, lvl = _split_pieces()
@@ -387,8 +379,8 @@ def conv3x3(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = N
             raise ValueError(f"conv3x3: bias {tuple(bias.shape)} for {N} channels")
     if w_split is None:
         w_split = split_weight_3x3(_req(weight, "weight"))
-    elif w_split.dtype != torch.uint8 or w_split.numel() != N * 9 * Cin * 6 or w_split.device != x.device:
-        raise ValueError("conv3x3: w_split is not split_weight_3x3(weight)")
+    else:
+        _check_split(w_split, N * 9 * Cin * 6, x, "conv3x3: w_split is not split_weight_3x3(weight)")
     out = torch.empty(B, N, Ho, Wo, device=x.device, dtype=torch.float32)
     pieces, lvl = _split_pieces()
     _launch("wm2f_conv3x3_split_fwd_p", x, _p(x), _p(w_split), _p(bias), _p(out), B, Cin, N, H, W, int(stride),
@@ -462,8 +454,8 @@ def stem_conv_pool(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, w_
         raise ValueError(f"stem_conv_pool: bias {tuple(bias.shape)} for {N} channels")
     if w_split is None:
         w_split = split_weight_stem(weight)
-    elif w_split.dtype != torch.uint8 or w_split.numel() != N * STEM_K * 6 or w_split.device != x.device:
-        raise ValueError("stem_conv_pool: w_split is not split_weight_stem(weight)")
+    else:
+        _check_split(w_split, N * STEM_K * 6, x, "stem_conv_pool: w_split is not split_weight_stem(weight)")
     out = torch.empty(B, N, ((H - 1) // 2) // 2 + 1, ((W - 1) // 2) // 2 + 1, device=x.device, dtype=torch.float32)
     pieces, lvl = _split_pieces()
     _launch("wm2f_stem7x7_pool_fwd_p", x, _p(x), _p(w_split), _p(bias), _p(out), B, Cin, N, H, W, int(grid), pieces,

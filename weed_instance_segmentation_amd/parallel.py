@@ -33,6 +33,8 @@ import torch
 import torch.distributed as dist
 from torch import nn
 
+from .derived import drop_derived
+
 
 class _Done:
     def wait(self):
@@ -229,6 +231,7 @@ class DataParallelEngine:
         if self.world > 1:  # identical replicas: rank 0's weights and buffers win
             for t in list(model.parameters()) + list(model.buffers()):
                 broadcast_from(t.data, 0, process_group)
+            drop_derived(model)  # no cache key sees a write through .data
         self.buckets = GradBuckets(model.parameters(), bucket_bytes, process_group, exchange)
         if optimizer is None:  # train.py:174 (AdamW, lr 5e-5).  On a GPU the fused form: ONE kernel over all parameters instead of
             # the multi-tensor form's ~14 launches per 1k tensors (1.7 -> 0.3 ms per config-2 step); same update rule
