@@ -575,6 +575,29 @@ int wm2f_conv1x1_split_gn_fwd_p(const void* x, const void* w_split, const void* 
                                 const void* norm_stats, const void* norm_gamma, const void* norm_beta, int norm_G, float norm_eps,
                                 int norm_relu, int B, int K, int N, int Hi, int Wi, int stride, int config, int pieces,
                                 void* stream);
+/* wm2f_conv1x1_split_dual_fwd_p: two 1x1 convolutions onto one output map as ONE GEMM over the concatenated K (a ResNet
+ *                        bottleneck's conv3 plus its projection shortcut), NCHW fp32, the split arithmetic of
+ *                        wm2f_conv1x1_split_fwd_p at `pieces`:
+ *                            out (B, N, Ho, Wo) = max(W1 (N, K1) . x1 (B, K1, Ho, Wo)
+ *                                                     + W2 (N, K2) . x2 (B, K2, H2, W2) sampled at (stride2 ho, stride2 wo)
+ *                                                     + bias[N], 0).
+ *                        ws1, ws2 = wm2f_token_linear_split_weight of W1 and of W2, two separate buffers: that split is
+ *                        k-step major, so ws1 followed by ws2 is byte for byte the split of [W1 | W2], and the kernel reads
+ *                        the two through two pointers.  The k-steps of source 1 come first, in order, then those of source 2;
+ *                        each k-step is summed from zero and added to the accumulator with one fp32 add.  An output therefore
+ *                        sees one MFMA sequence under every config, B and sub-batch (deterministic, no split-K, no atomics),
+ *                        and a source whose weight is all zero adds nothing: the result is then bit for bit
+ *                        wm2f_conv1x1_split_fwd_p of the other source with bias and ReLU.  Pixels of x2 that stride2 skips are
+ *                        never read.  An inf or a NaN in a sampled pixel of either source makes that pixel's N outputs
+ *                        non-finite and no other.
+ *                        Refused with WM2F_EINVAL before any launch, out untouched: a null pointer (bias included);
+ *                        K1 % 32, K2 % 32 or N % 64 non-zero; stride2 outside {1, 2}; (H2 - 1) / stride2 + 1 != Ho or the same
+ *                        for W; one image of x1, x2 or out, or either split, at or above 2 GiB; a config >= 0 whose tile does
+ *                        not divide N (or outside the table); pieces outside {1, 2, 3}.  config = -1: the tile pick of
+ *                        wm2f_conv1x1_split_config(N, Ho * Wo, B, CUs), which does not depend on K. */
+int wm2f_conv1x1_split_dual_fwd_p(const void* x1, const void* ws1, const void* x2, const void* ws2, const void* bias, void* out,
+                                  int B, int K1, int K2, int N, int Ho, int Wo, int H2, int W2, int stride2, int config,
+                                  int pieces, void* stream);
 int wm2f_conv3x3_split_fwd_p(const void* x, const void* w_split, const void* bias, void* out, int B, int Cin, int N, int Hi,
                              int Wi, int stride, int relu, int config, int pieces, void* stream);
 int wm2f_conv3x3_split_stats_fwd_p(const void* x, const void* w_split, void* out, void* stats_out, int G_out, int B, int Cin,

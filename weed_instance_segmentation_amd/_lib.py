@@ -127,6 +127,7 @@ SIGNATURES = {
     "wm2f_token_ffn_split_fwd_p": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _I, _I, _I, c_int64, c_float, _I, _P]),
     "wm2f_conv1x1_split_fwd_p": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_conv1x1_split_gn_fwd_p": (c_int, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, c_float, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "wm2f_conv1x1_split_dual_fwd_p": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_conv3x3_split_fwd_p": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_conv3x3_split_stats_fwd_p": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_stem7x7_pool_fwd_p": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),

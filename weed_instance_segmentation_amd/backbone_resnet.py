@@ -127,10 +127,30 @@ class BottleNeckLayer(nn.Module):
         if not self.training and not torch.is_grad_enabled():
             h = self.layer[1](self.layer[0](x))
             if isinstance(self.shortcut, ShortCut):
+                out = self._conv3_plus_shortcut(h, x)
+                if out is not None:
+                    return out
                 sc, sc_bias = self.shortcut.folded_raw(x)
                 return self.layer[2](h, residual=sc, extra_bias=sc_bias, force_relu=True)
             return self.layer[2](h, residual=x, force_relu=True)
         return self.activation(self.layer(x) + self.shortcut(x))
+
+    def _conv3_plus_shortcut(self, h, x):
+        """Inference: relu(conv3(h) + shortcut(x)) as ONE split GEMM over the concatenated K (ops.conv1x1_dual),
+        or None where that does not apply and the raw shortcut plus conv3's residual epilogue run.  Each convolution keeps
+        its own fold and split under its own layer; the block owns only the sum of the two folded biases."""
+        if not ops.SHORTCUT_FOLD:
+            return None
+        l3, sc = self.layer[2], self.shortcut
+        c3, cs = l3.convolution, sc.convolution
+        w3, b3 = _folded(l3, c3, l3.normalization)
+        wsc, bsc = _folded(sc, cs, sc.normalization)
+        if not (c3.stride == (1, 1) and _split_1x1(c3, h, w3) and _split_1x1(cs, x, wsc)
+                and ops.conv1x1_dual_applies(h, w3, x, wsc, cs.stride[0])):
+            return None
+        bias = derived(self, "shortcut_bias", (b3, bsc), lambda: b3 + bsc)  # a new fold gives new bias objects
+        return ops.conv1x1_dual(h, w3, x, wsc, bias, cs.stride[0], w1_split=ops.split_weight_cached(l3, "conv", w3),
+                                w2_split=ops.split_weight_cached(sc, "conv", wsc))
 
 
 class Stage(nn.Module):

@@ -26,6 +26,13 @@
 // store (input projections, adapter_1), the NORM instance normalises its operand as it loads it (mask_projection).  The
 // stored output of a STATS instance is bit for bit that of the plain one; "no atomics" holds for the output, the
 // statistics are added into an fp64 workspace with one atomic pair per (workgroup, group).
+//
+// Two sources (the DUAL instances): a bottleneck's conv3 and its projection shortcut as ONE GEMM over the
+// concatenated K,  y = relu([W1 | W2] . [x1 ; x2 sampled] + bias).  The k-steps of source 1 come first, then those of
+// source 2, each from its own split weight (the split is k-step major, so the two splits laid end to end ARE the split of
+// [W1 | W2]) and its own image; the source of a k-step is chosen with wave-uniform selects.
+#include <type_traits>
+
 #include "common.h"
 #include "group_norm.h"
 
@@ -85,6 +92,13 @@ struct C1Args {
   int nG, nrelu;
 };
 
+// DUAL: source 1 is (x, ws, K) above, read at stride 1 (Hi x Wi is the output map); source 2 follows it in K
+struct C1DualArgs : C1Args {
+  const float* x2;
+  const void* ws2;
+  int K2, H2, W2, stride2;
+};
+
 __device__ __forceinline__ void c1_barrier() {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -97,9 +111,11 @@ __device__ __forceinline__ void c1_barrier() {
 // workgroup into LDS behind the ring (gn_affine / gn_apply: the bits group_norm_apply_kernel writes).
 // P = the pieces of each operand that take part: 3 = all six products, 2 = h and m (m.h, h.m, h.h), 1 = h
 // alone (h.h).  The split weight is the three-piece one at every P; the ring holds the first P pieces of each row tile.
-template <int NRT, int WN, int EPI, bool STATS = false, bool NORM = false, int P = 3>
-__global__ __launch_bounds__(kThreads) void conv1x1_split_kernel(C1Args a) {
+// DUAL: k-steps 0 .. K / 32 - 1 read (ws, x), the next K2 / 32 read (ws2, x2 sampled at stride2); + bias + ReLU only.
+template <int NRT, int WN, int EPI, bool STATS = false, bool NORM = false, int P = 3, bool DUAL = false>
+__global__ __launch_bounds__(kThreads) void conv1x1_split_kernel(std::conditional_t<DUAL, C1DualArgs, C1Args> a) {
   static_assert(P >= 1 && P <= 3, "one, two or three pieces");
+  static_assert(!DUAL || (EPI == kBiasRelu && !STATS && !NORM), "two sources: + bias + ReLU, no GroupNorm on either side");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [2][NT / 16][P][64][16 B] (+ NORM: [2][K] floats)
   constexpr int kRowTiles = WN * NRT;
   constexpr int kPanelBytes = kRowTiles * P * kFrag;
@@ -111,7 +127,9 @@ __global__ __launch_bounds__(kThreads) void conv1x1_split_kernel(C1Args a) {
   const int nb = blockIdx.x, b = blockIdx.z;
   const int n_wg = nb * kRowTiles * 16;            // first channel of the workgroup
   const int p_w = blockIdx.y * kPT + wp * kCT * 16;  // first pixel of the wave
-  const int n_ks = a.K / kKStep;
+  const int n_ks1 = a.K / kKStep;  // k-steps of the (first) source
+  int n_ks = n_ks1;
+  if constexpr (DUAL) n_ks += a.K2 / kKStep;
   const int HWi = a.Hi * a.Wi;
 
   // per-image buffers (each below 2 GiB: checked by the host)
@@ -129,6 +147,23 @@ __global__ __launch_bounds__(kThreads) void conv1x1_split_kernel(C1Args a) {
   }
   const unsigned ch_bytes = (unsigned)HWi * 4;
 
+  // DUAL: the same three things for the second source -- per-image resources, pixel offsets, channel stride
+  __amdgpu_buffer_rsrc_t w2_rs = w_rs, x2_rs = x_rs;
+  unsigned xo2[kCT] = {kOob, kOob};
+  unsigned ch_bytes2 = ch_bytes;
+  if constexpr (DUAL) {
+    const int HW2 = a.H2 * a.W2;
+    w2_rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.ws2, 0, a.N * a.K2 * 6, 0x00020000);
+    x2_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(a.x2 + (int64_t)b * a.K2 * HW2), 0, a.K2 * HW2 * 4, 0x00020000);
+#pragma unroll
+    for (int c = 0; c < kCT; ++c) {
+      const int p = p_w + c * 16 + j;
+      const int ho = p / a.Wo, wo = p - ho * a.Wo;
+      xo2[c] = p < a.P ? (unsigned)(((8 * g) * HW2 + a.stride2 * (ho * a.W2 + wo)) * 4) : kOob;
+    }
+    ch_bytes2 = (unsigned)HW2 * 4;
+  }
+
   float* ntab = reinterpret_cast<float*>(smem + 2 * kPanelBytes);  // NORM: scale[K], shift[K] of image b
   if (NORM) {
     const int ncpg = a.K / a.nG;
@@ -142,20 +177,31 @@ __global__ __launch_bounds__(kThreads) void conv1x1_split_kernel(C1Args a) {
   }
 
   f32x8 xr[kCT];
-  auto issue = [&](int ks) {
+  // ring slot ks & 1 and xr <- k-step ksl of the source (wr, xs, po, cb)
+  auto issue_from = [&](int ks, int ksl, const __amdgpu_buffer_rsrc_t wr, const __amdgpu_buffer_rsrc_t xs, const unsigned (&po)[kCT],
+                        unsigned cb) {
     unsigned char* dst = smem + (ks & 1) * kPanelBytes;
-    const int src = (ks * (a.N / 16) + n_wg / 16) * 3 * kFrag;
+    const int src = (ksl * (a.N / 16) + n_wg / 16) * 3 * kFrag;
     for (int f = wave; f < kPieces; f += kWaves) {
       const int fs = P == 3 ? f : (f / P) * 3 + f % P;  // ring piece f = piece f % P of row tile f / P
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rs, (lds_ptr_t)(dst + f * kFrag), 16, lane * 16, src + fs * kFrag, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (lds_ptr_t)(dst + f * kFrag), 16, lane * 16, src + fs * kFrag, 0, 0);
     }
-    const unsigned kb = (unsigned)(ks * kKStep) * ch_bytes;
+    const unsigned kb = (unsigned)(ksl * kKStep) * cb;
 #pragma unroll
     for (int c = 0; c < kCT; ++c) {
-      const unsigned o = xo[c] == kOob ? kOob : xo[c] + kb;
+      const unsigned o = po[c] == kOob ? kOob : po[c] + kb;
 #pragma unroll
       for (int i = 0; i < 8; ++i)
-        xr[c][i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(x_rs, o, i * ch_bytes, 0));
+        xr[c][i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xs, o, i * cb, 0));
+    }
+  };
+  auto issue = [&](int ks) {
+    if constexpr (DUAL) {  // wave-uniform selects and one load sequence: no branch around the x loads (§13.3)
+      const bool second = ks >= n_ks1;
+      const unsigned po[kCT] = {second ? xo2[0] : xo[0], second ? xo2[1] : xo[1]};
+      issue_from(ks, second ? ks - n_ks1 : ks, second ? w2_rs : w_rs, second ? x2_rs : x_rs, po, second ? ch_bytes2 : ch_bytes);
+    } else {
+      issue_from(ks, ks, w_rs, x_rs, xo, ch_bytes);
     }
   };
 
@@ -293,6 +339,22 @@ void (*pick_cfg(int ci, int epi, int opt))(C1Args) {
     case 3: return pick_epi<8, 1, P>(epi, opt);
     default: return pick_epi<4, 1, P>(epi, opt);
   }
+}
+
+// The two-source instances: every configuration and piece count, + bias + ReLU.
+template <int P>
+void (*pick_dual_cfg(int ci))(C1DualArgs) {
+  switch (ci) {
+    case 0: return conv1x1_split_kernel<16, 1, kBiasRelu, false, false, P, true>;
+    case 1: return conv1x1_split_kernel<8, 2, kBiasRelu, false, false, P, true>;
+    case 2: return conv1x1_split_kernel<4, 4, kBiasRelu, false, false, P, true>;
+    case 3: return conv1x1_split_kernel<8, 1, kBiasRelu, false, false, P, true>;
+    default: return conv1x1_split_kernel<4, 1, kBiasRelu, false, false, P, true>;
+  }
+}
+
+void (*pick_dual(int ci, int pieces))(C1DualArgs) {
+  return pieces == 3 ? pick_dual_cfg<3>(ci) : (pieces == 2 ? pick_dual_cfg<2>(ci) : pick_dual_cfg<1>(ci));
 }
 
 void (*pick_kernel(int ci, int epi, int opt, int pieces))(C1Args) {
@@ -459,4 +521,70 @@ extern "C" int wm2f_conv1x1_split_gn_fwd_p(const void* x, const void* w_split, c
   WM2F_REQUIRE(stats_out || norm_stats, "%s: neither a statistics output nor a normalised operand", who);
   const C1Gn gn = {stats_out, G_out, norm_stats, norm_gamma, norm_beta, norm_G, norm_eps, norm_relu ? 1 : 0};
   return conv1x1_launch(who, x, w_split, bias, nullptr, out, gn, B, K, N, Hi, Wi, stride, 0, config, pieces, stream);
+}
+
+extern "C" int wm2f_conv1x1_split_dual_fwd_p(const void* x1, const void* ws1, const void* x2, const void* ws2, const void* bias,
+                                             void* out, int B, int K1, int K2, int N, int Ho, int Wo, int H2, int W2, int stride2,
+                                             int config, int pieces, void* stream) {
+  const char* who = "wm2f_conv1x1_split_dual_fwd_p";
+  WM2F_REQUIRE(pieces >= 1 && pieces <= 3, "%s: pieces = %d (1, 2 and 3 are built)", who, pieces);
+  WM2F_REQUIRE(x1 && ws1 && x2 && ws2 && bias && out, "%s: null pointer", who);
+  WM2F_REQUIRE(B > 0 && K1 > 0 && K2 > 0 && N > 0 && Ho > 0 && Wo > 0 && H2 > 0 && W2 > 0, "%s: non-positive size", who);
+  WM2F_REQUIRE(K1 % kKStep == 0 && K2 % kKStep == 0 && N % 64 == 0,
+               "%s: K1 = %d and K2 = %d must be multiples of %d and N = %d of 64", who, K1, K2, kKStep, N);
+  WM2F_REQUIRE(stride2 == 1 || stride2 == 2, "%s: stride2 %d (1 and 2 are built)", who, stride2);
+  WM2F_REQUIRE((H2 - 1) / stride2 + 1 == Ho && (W2 - 1) / stride2 + 1 == Wo,
+               "%s: x2 (%d, %d) at stride %d does not sample onto the (%d, %d) output map", who, H2, W2, stride2, Ho, Wo);
+  const int64_t P = (int64_t)Ho * Wo;
+  WM2F_REQUIRE((int64_t)K1 * P * 4 < (1ll << 31) && (int64_t)K2 * H2 * W2 * 4 < (1ll << 31) && (int64_t)N * P * 4 < (1ll << 31),
+               "%s: one image of x1 / x2 / out must stay below 2 GiB (32-bit buffer offsets)", who);
+  WM2F_REQUIRE((int64_t)N * K1 * 6 < (1ll << 31) && (int64_t)N * K2 * 6 < (1ll << 31),
+               "%s: each split weight must stay below 2 GiB", who);
+  int n_cu = 0;
+  if (cu_count(&n_cu) != 0) {
+    set_error("%s: cannot query the device", who);
+    return WM2F_ELAUNCH;
+  }
+  WM2F_REQUIRE(config >= -1 && config < kNumCfg, "%s: configuration %d out of range", who, config);
+  const int ci = config >= 0 ? config : choose_cfg(N, (int)P, B, n_cu);  // the one-source rule: K plays no part in it
+  WM2F_REQUIRE(ci >= 0 && N % (kCfg[ci].wn * kCfg[ci].nrt * 16) == 0, "%s: no configuration %d for N = %d", who, ci, N);
+  const int nt = kCfg[ci].wn * kCfg[ci].nrt * 16, pt = (kWaves / kCfg[ci].wn) * kCT * 16;
+  C1DualArgs a;
+  a.x = (const float*)x1;
+  a.ws = ws1;
+  a.bias = (const float*)bias;
+  a.residual = nullptr;
+  a.out = (float*)out;
+  a.K = K1;
+  a.N = N;
+  a.Hi = Ho;
+  a.Wi = Wo;
+  a.Wo = Wo;
+  a.P = (int)P;
+  a.stride = 1;
+  a.stats = nullptr;
+  a.G = 1;
+  a.cpg = 4;
+  a.nstats = nullptr;
+  a.ngamma = a.nbeta = nullptr;
+  a.neps = 0.f;
+  a.nG = 1;
+  a.nrelu = 0;
+  a.x2 = (const float*)x2;
+  a.ws2 = ws2;
+  a.K2 = K2;
+  a.H2 = H2;
+  a.W2 = W2;
+  a.stride2 = stride2;
+  const size_t lds = (size_t)2 * (nt / 16) * pieces * kFrag;
+  void (*kfn)(C1DualArgs) = pick_dual(ci, pieces);
+  // per call: the attribute belongs to the current device
+  hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) {
+    set_error("%s: cannot raise dynamic LDS to %zu: %s", who, lds, hipGetErrorString(e));
+    return WM2F_ELAUNCH;
+  }
+  hipLaunchKernelGGL(kfn, dim3(N / nt, ceil_div((int)P, pt), B), dim3(kThreads), lds, (hipStream_t)stream, a);
+  WM2F_CHECK_LAUNCH(who);
+  return WM2F_OK;
 }

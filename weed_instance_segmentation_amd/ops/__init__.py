@@ -27,6 +27,11 @@ CONV3X3_SPLIT = True
 # layer_1's raw output in its operand load.  False keeps the separate statistics and apply passes (the reference of the tests).
 CONV_GN_FUSED = True
 
+# The inference forward of a ResNet bottleneck with a projection shortcut runs conv3 and the shortcut as ONE split GEMM over
+# the concatenated K while this is True and conv1x1_dual_applies: the shortcut's full-width output never reaches
+# memory.  False keeps the raw shortcut launch and conv3's residual epilogue (the reference of the tests).
+SHORTCUT_FOLD = True
+
 # The inference forward of a pixel-decoder encoder layer runs fc1 + ReLU and fc2 + LayerNorm (+ pos) as ONE kernel while this
 # is True and token_ffn_applies: the (tokens, 1024) intermediate never reaches memory.  False keeps the two
 # token_linear launches (the reference of the tests: the fused kernel gives their bits).
@@ -49,7 +54,7 @@ from .clean import labelmap_clean
 from .copy_paste import copy_paste
 from .fused import (add_broadcast, bias_act_, bias_relu_maxpool, group_norm_act_, group_norm_act_from_stats_, group_norm_tokens_,
                     group_norm_tokens_from_stats_, resize_bilinear, resize_pyramid, tokens_to_nchw)
-from .gemm import (conv1x1, conv1x1_applies, conv1x1_gn, conv3x3, conv3x3_applies, conv3x3_stats, conv_group_stats_applies,
+from .gemm import (conv1x1, conv1x1_applies, conv1x1_dual, conv1x1_dual_applies, conv1x1_gn, conv3x3, conv3x3_applies, conv3x3_stats, conv_group_stats_applies,
                    ROWS_FFN, ROWS_NATURAL, ffn_row_order, linear_tokens, split_weight, split_weight_3x3,
                    split_weight_cached, split_weight_rows, split_weight_rows_cached, split_weight_stem, stem_conv_pool,
                    stem_conv_pool_applies, stem_weight_columns, stem_weight_matrix, token_ffn, token_ffn_applies,

@@ -263,6 +263,55 @@ def conv1x1(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = N
     return out
 
 
+def conv1x1_dual_applies(x1: torch.Tensor, w1: torch.Tensor, x2: torch.Tensor, w2: torch.Tensor, stride2: int = 1) -> bool:
+    """Shapes wm2f_conv1x1_split_dual_fwd_p is built for: each (x, weight) pair inside conv1x1_applies (x1 at stride 1, x2 at
+    stride2), the same device, batch and N, and x2 sampled at stride2 landing on x1's map."""
+    if stride2 not in (1, 2) or not (conv1x1_applies(x1, w1, 1) and conv1x1_applies(x2, w2, stride2)):
+        return False
+    _, _, Ho, Wo = x1.shape
+    _, _, H2, W2 = x2.shape
+    return (x1.device == x2.device and x1.shape[0] == x2.shape[0] and int(w1.shape[0]) == int(w2.shape[0])
+            and (H2 - 1) // stride2 + 1 == Ho and (W2 - 1) // stride2 + 1 == Wo)
+
+
+def conv1x1_dual(x1: torch.Tensor, w1: torch.Tensor, x2: torch.Tensor, w2: torch.Tensor, bias: torch.Tensor, stride2: int = 1,
+                 w1_split: torch.Tensor | None = None, w2_split: torch.Tensor | None = None, config: int = -1,
+                 split: bool = True) -> torch.Tensor:
+    """relu(conv1x1(x1, w1) + conv1x1(x2, w2, stride2) + bias) as ONE GEMM over the concatenated K (inference, no autograd;
+    wm2f_conv1x1_split_dual_fwd_p): a bottleneck's conv3 on x1 (B, K1, Ho, Wo) plus its projection shortcut on
+    x2 (B, K2, H2, W2), whose full-width output never reaches memory.  w1_split / w2_split = split_weight of each weight seen
+    as (N, K) if the caller keeps them -- two separate splits, read through two pointers.  config as conv1x1's.
+    split=False, and shapes outside conv1x1_dual_applies: the two-call route,
+        conv1x1(x1, w1, bias, residual=conv1x1(x2, w2, stride=stride2), relu=True)
+    on the same `split`."""
+    if bias is None:
+        raise ValueError("conv1x1_dual: the epilogue is + bias + ReLU")
+    if not split or not conv1x1_dual_applies(x1, w1, x2, w2, stride2):
+        sc = conv1x1(x2, w2, None, stride=stride2, split=split, w_split=w2_split if split else None)
+        if not x1.is_cuda:  # the same in torch ops (bias_act_ is a GPU kernel)
+            w4 = w1 if w1.dim() == 4 else w1.view(*w1.shape, 1, 1)
+            return torch.relu(torch.nn.functional.conv2d(x1, w4) + bias[None, :, None, None] + sc)
+        return conv1x1(x1, w1, bias, sc, True, 1, split=split, w_split=w1_split if split else None)
+    x1, x2, bias = _req(x1, "x1"), _req(x2, "x2"), _req(bias, "bias")
+    N, K1, K2 = int(w1.shape[0]), int(w1.shape[1]), int(w2.shape[1])
+    B, _, Ho, Wo = x1.shape
+    _, _, H2, W2 = x2.shape
+    if bias.shape != (N,):
+        raise ValueError(f"conv1x1_dual: bias {tuple(bias.shape)} for {N} channels")
+    splits = []
+    for w, ws, K, name in ((w1, w1_split, K1, "w1"), (w2, w2_split, K2, "w2")):
+        if ws is None:
+            ws = split_weight(_req(w.reshape(N, K), name))
+        else:
+            _check_split(ws, N * K * 6, x1, f"conv1x1_dual: {name}_split is not split_weight({name})")
+        splits.append(ws)
+    out = torch.empty(B, N, Ho, Wo, device=x1.device, dtype=torch.float32)
+    pieces, lvl = _split_pieces()
+    _launch("wm2f_conv1x1_split_dual_fwd_p", x1, _p(x1), _p(splits[0]), _p(x2), _p(splits[1]), _p(bias), _p(out), B, K1, K2, N,
+            Ho, Wo, H2, W2, int(stride2), int(config), pieces, tag=f"conv1x1_K{K1}+{K2}_N{N}_P{Ho * Wo}{lvl}")
+    return out
+
+
 def conv_group_stats_applies(channels: int, groups: int) -> bool:
     """Group sizes for which the split convolutions' epilogue produces the GroupNorm statistics of its output
     (conv1x1_gn, conv3x3_stats): groups of 4, 8 or 16 channels, each inside one 16-channel row tile of the kernel.  Any
