@@ -1726,6 +1726,70 @@ int wm2f_labelmap_row_bands(const void* map, int dtype, const int32_t* ids, cons
                             const int32_t* rho, int64_t* counts, uint8_t* zone, int B, int H, int W, int N, int Kmax,
                             int band, void* stream);
 
+/* ---- skeletons: parallel thinning of id maps, per-instance skeleton sums -------------------------
+ * What the other per-instance calls do not say about a plant: how long its leaves and stems are, how many ends it has
+ * and how wide its parts are.  tests/skeleton_reference.py restates every rule in numpy; no library's thinning is
+ * claimed to give the same bytes.
+ *
+ * wm2f_labelmap_skeleton
+ * Input: map (B, H, W) WM2F_F32, WM2F_I32 or WM2F_U8, ids by wm2f_labelmap_instance_stats' rule; the instances are the
+ *   ids 0 .. N-1, every other pixel is background (as for wm2f_labelmap_clean).
+ * State: an int32 map s, s[p] = id while p is alive, -1 otherwise.  At the start every instance pixel is alive.
+ * Neighbours of a live pixel p of id k:  p2 = N, p3 = NE, p4 = E, p5 = SE, p6 = S, p7 = SW, p8 = W, p9 = NW (N is y - 1,
+ *   E is x + 1).  pi = 1 iff that pixel is inside the image and alive with the same id k; another id counts as
+ *   background, so all instances thin at once and never interact.
+ * Deletion rule (Guo and Hall, CACM 32(3), 1989, algorithm A1: two sub-iterations):
+ *   C  = (!p2 & (p3 | p4)) + (!p4 & (p5 | p6)) + (!p6 & (p7 | p8)) + (!p8 & (p9 | p2))
+ *   N1 = (p9 | p2) + (p3 | p4) + (p5 | p6) + (p7 | p8)
+ *   N2 = (p2 | p3) + (p4 | p5) + (p6 | p7) + (p8 | p9)
+ *   N  = min(N1, N2)
+ *   m0 = (p6 | p7 | !p9) & p8          (first sub-iteration)
+ *   m1 = (p2 | p3 | !p5) & p4          (second sub-iteration)
+ *   p is deleted in sub-iteration j  iff  C = 1 and 2 <= N <= 3 and mj = 0.
+ *   A sub-iteration is synchronous: every decision reads the state at its start.  An iteration is sub-iteration 0, then
+ *   sub-iteration 1.  The result is the state after `rounds` iterations.  An iteration that deletes nothing leaves a
+ *   fixed point, so every later one deletes nothing either.
+ * Output: out (B, H, W) int32: the skeleton as an id map again, -1 elsewhere.
+ *   status (B, 4) int32: [skeleton pixels, iterations that deleted something, deletions in iteration `rounds`, rounds].
+ *   A non-zero third entry says that `rounds` was too small; out is then still the defined result of exactly `rounds`
+ *   iterations.  A solid shape settles in about (its largest half-width + 1) iterations.
+ * per_launch: the iterations a launch runs on a tile held in LDS, 1, 2, 4 or 8; 0: the shipped default (4).  Every value
+ *   gives the same bits.
+ * Limits: H, W <= 16384, B <= 32, N <= 4096, else WM2F_EUNSUPPORTED, reported before a pointer is looked at; a size
+ *   below 1, rounds outside [1, 1024], another per_launch, a null pointer or another dtype: WM2F_EINVAL.  out must not
+ *   overlap map.  workspace: wm2f_labelmap_skeleton_workspace(B, H, W) bytes (-1 for a bad size), 16-byte aligned, no
+ *   clearing needed: one int32 plane and 8 KiB of counters per image.
+ * Kernels: init (counters); ceil(rounds / per_launch) launches of thin; status.  A thin workgroup owns a 64 x 64 tile:
+ *   it loads the tile and a halo of 2 per_launch pixels into LDS as int16 cells, runs its sub-iterations there
+ *   (decisions into registers, a barrier, the writes, a barrier) and stores the owned tile; after sub-iteration t the
+ *   cells at least t inside the loaded region are exact; after two sub-iterations in a row in which the workgroup
+ *   deleted nothing its image is final and it goes on to the store.  The launches ping-pong between out and the workspace plane so
+ *   that the last one writes out; the first decodes the map; the last runs only the iterations that remain.  From the
+ *   third on, a launch returns at once when the launch before it deleted nothing in its image (that launch copied one
+ *   plane to the other, so both hold the result).  Integer add atomics only, one per workgroup and counter:
+ *   bit-identical from run to run.  No call allocates, keeps state, reads anything back or waits for the device.
+ *
+ * wm2f_labelmap_skeleton_stats: skel (B, H, W) int32, what wm2f_labelmap_skeleton wrote; d2 (B, H, W) int32, optional:
+ *   wm2f_labelmap_distance of the ORIGINAL map; ids / n_ids / N as wm2f_labelmap_shape_stats takes them.  For a skeleton
+ *   pixel p of id k, pi as above on skel, b = the number of pi that are 1, and X = the crossing number: the sum of
+ *   !pi & p(i+1) around the cycle p2, p3, ..., p9, p2.  stats (B, N, 8) int64 per id:
+ *   [0] skeleton pixels
+ *   [1] orthogonal links: pairs of 4-adjacent skeleton pixels of the id, each pair once
+ *   [2] diagonal links: pairs of diagonally adjacent skeleton pixels of the id, counted only when neither of the two
+ *       pixels 4-adjacent to both is a skeleton pixel of that id (a staircase does not count its triangles twice)
+ *   [3] tips: X = 1 and b <= 2      [4] junction pixels: X >= 3      [5] isolated pixels: b = 0
+ *   [6] the sum of d2 over the skeleton pixels      [7] the largest d2 among them      (both 0 without d2)
+ *   The skeleton's length is [1] + sqrt(2) [2]; 2 sqrt(d2) - 1 is the width of the part a skeleton pixel runs through.
+ *   (Guo and Hall's C is 0 at the centre of a 4-connected "+", which is why junctions use X.)  An id without a skeleton
+ *   pixel has an all-zero row.  Two launches (clear; one read of the map, a one-pixel stencil around skeleton pixels,
+ *   one lane adding for its wave when the wave's skeleton pixels share an id).
+ *   Limits as above with N >= 1; ids without n_ids: WM2F_EINVAL.  Integer add and max atomics: bit-identical. */
+int64_t wm2f_labelmap_skeleton_workspace(int B, int H, int W);
+int wm2f_labelmap_skeleton(const void* map, int dtype, int32_t* out, int32_t* status, void* workspace, int B, int H, int W,
+                           int N, int rounds, int per_launch, void* stream);
+int wm2f_labelmap_skeleton_stats(const int32_t* skel, const int32_t* d2, const int32_t* ids, const int32_t* n_ids,
+                                 int64_t* stats, int B, int H, int W, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
