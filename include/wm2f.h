@@ -605,6 +605,47 @@ int wm2f_conv3x3_split_stats_fwd_p(const void* x, const void* w_split, void* out
 int wm2f_stem7x7_pool_fwd_p(const void* x, const void* w_split, const void* bias, void* out, int B, int Cin, int N, int Hi,
                             int Wi, int grid, int pieces, void* stream);
 
+/* wm2f_swin_linear_split_fwd_p: the Linears of a Swin block and of patch merging (inference), all fp32, row-major
+ *                        and token-major, W as nn.Linear stores it, at `pieces` of the split arithmetic above:
+ *                            out (M, N) = epilogue(x (M, K) . W (N, K)^T + bias[N]).
+ *                        Weights: w_split is exactly what wm2f_token_linear_split_weight(W, N, K) writes, the three-piece
+ *                        split in fragment order [k-step][row tile][piece][lane][8 bf16], N * K * 6 bytes; there is no
+ *                        second format.  A (feature tile, k-step) panel of any tile width that is a multiple of 16 is
+ *                        contiguous in that order.  pieces in {1, 2, 3} reads the first `pieces` pieces of each row tile and
+ *                        splits x into `pieces` pieces.
+ *                        Shapes: K % 32 == 0, N % 16 == 0, M >= 1; x, every out and residual below 2 GiB each (32-bit
+ *                        buffer offsets), N * K * 6 < 2 GiB.  M needs no alignment: the last token tile is partial, its
+ *                        loads and stores are bounded.  N need not be a multiple of the workgroup's feature-tile width:
+ *                        the last feature tile is partial in whole 16-row tiles.  Every pointer is 16-byte aligned.
+ *                        epilogue = 0: + bias (bias may be NULL: patch merging's reduction has none);
+ *                                   1: + bias, then exact GELU 0.5 v (1 + erf(v / sqrt 2)) on the fp32 value (F.gelu's default);
+ *                                   2: + bias, then + residual[M, N]; residual is required (and NULL otherwise), and out0 may
+ *                                      not alias it.
+ *                        n_out = 1: out0 is (M, N), out1 and out2 are not looked at.
+ *                                3: feature n goes to out{n / (N / 3)} at column n % (N / 3), each buffer (M, N / 3) and
+ *                                   contiguous -- the merged q | k | v projection written as the three image-order tensors
+ *                                   wm2f_swin_window_attn_fwd reads.  Needs (N / 3) % 16 == 0 and epilogue == 0.
+ *                        config = -1: the host's choice from (M, N, pieces, CUs), wm2f_swin_linear_split_config;
+ *                                 0 .. wm2f_swin_linear_split_configs() - 1: that entry of the tile table (tests, tuning).
+ *                        Accumulation: as the token kernel, the products are chained into the accumulator -- every MFMA of
+ *                        every k-step takes the running sum as its C operand, from +0 at k = 0 -- and the bias is added to
+ *                        the finished sum, then the GELU or the residual.
+ *                        Determinism: no split-K, no atomics.  Every output has one MFMA sequence, the same under every
+ *                        config, every M, every position of the token in M and every way of cutting rows into calls: the
+ *                        outputs are bit-identical across configs and across runs.
+ *                        Non-finite: an inf or a NaN in x makes every output of its token non-finite and touches no other
+ *                        token; finite values up to FLT_MAX stay finite where the result is representable.
+ *                        Refusals: anything outside the above returns WM2F_EINVAL with nothing launched and the outputs
+ *                        untouched; sizes (pieces, M, K, N, epilogue, n_out, config, the 2 GiB limits, a residual that does
+ *                        not match the epilogue) are checked before a pointer is looked at.
+ * wm2f_swin_linear_split_config: the host's choice for (M, N, pieces) on n_cu CUs, an index into the tile table; -1 for
+ *                        sizes the kernel refuses.  wm2f_swin_linear_split_configs: how many entries the table has. */
+int wm2f_swin_linear_split_fwd_p(const void* x, const void* w_split, const void* bias, const void* residual, void* out0,
+                                 void* out1, void* out2, int64_t M, int K, int N, int epilogue, int n_out, int config,
+                                 int pieces, void* stream);
+int wm2f_swin_linear_split_config(int64_t M, int N, int pieces, int n_cu);
+int wm2f_swin_linear_split_configs(void);
+
 /* wm2f_token_wgrad_bf16: the weight / bias gradient of such a Linear (the backward autograd derives for nn.Linear; train
  *                        step of HF:1036-1103 under bf16 autocast):  dw (N, K) fp32 = dy (M, N)^T . x (M, K),
  *                        db (N) fp32 = column sums of dy (NULL: skipped); dy, x bf16 row-major, fp32 accumulation on the bf16

@@ -131,6 +131,9 @@ SIGNATURES = {
     "wm2f_conv3x3_split_fwd_p": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_conv3x3_split_stats_fwd_p": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_stem7x7_pool_fwd_p": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "wm2f_swin_linear_split_fwd_p": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int64, _I, _I, _I, _I, _I, _I, _P]),
+    "wm2f_swin_linear_split_config": (c_int, [c_int64, _I, _I, _I]),
+    "wm2f_swin_linear_split_configs": (c_int, []),
     "wm2f_token_wgrad_workspace": (c_int64, [c_int64, _I, _I]),
     "wm2f_token_wgrad_bf16": (c_int, [_P, _P, _P, _P, _P, c_int64, _I, _I, _P]),
     "wm2f_token_wgrad_f32": (c_int, [_P, _P, _P, _P, _P, c_int64, _I, _I, _P]),

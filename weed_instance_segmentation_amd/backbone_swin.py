@@ -1,6 +1,7 @@
 """Swin Transformer backbone.  On a GPU each layer's shifted-window attention is one launch: ops.swin_window_attention
 when autograd records nothing, ops.swin_window_attention_train (one more launch in the backward) when it does (DESIGN.md
-section 19); CPU tensors and shapes those kernels are not built for run stock PyTorch-ROCm ops.
+section 19); CPU tensors and shapes those kernels are not built for run stock PyTorch-ROCm ops.  In the fp32 inference
+forward the layer's Linears and MLP and patch merging's reduction run on ops.swin_linear (section 45, ops.SWIN_LINEAR_SPLIT).
 
 Needed because the reference's own checkpoint is Swin-Large (config.py:4) and BASELINE.json's configs 4 / 5
 are Swin-T / Swin-B.  Restates transformers' SwinBackbone (models/swin/modeling_swin.py:1070-1150 of
@@ -19,10 +20,36 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import ops
+from .derived import derived
 
 # A/B switch for tools/ (a module attribute, never an environment variable): False sends every layer
 # through the stock route below.
 FUSED_WINDOW_ATTENTION = True
+
+
+def _records(x, module):
+    """Autograd would record a forward of `module` on x."""
+    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters()))
+
+
+def _split_level_on():
+    """ops.SWIN_LINEAR_SPLIT at the level of this call: True / False, or the collection of levels that take the route."""
+    flag = ops.SWIN_LINEAR_SPLIT
+    return flag if isinstance(flag, bool) else (ops.SPLIT_PRECISION or "highest") in flag
+
+
+def _split_linears_apply(x, module, weights):
+    """The Linears around x go through ops.swin_linear: inference on fp32 GPU tokens without
+    autocast, the flag on, and every weight inside swin_linear_applies."""
+    if not (x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled("cuda") and _split_level_on()):
+        return False
+    if _records(x, module):
+        return False
+    return all(ops.swin_linear_applies(t, w, n) for t, w, n in weights)
+
+
+def _split(lin):
+    return ops.split_weight_cached(lin, "swin_linear", lin.weight)
 
 
 def _window_partition(x, ws):  # (B,H,W,C) -> (B*nW, ws, ws, C)            modeling_swin.py:486-495
@@ -123,7 +150,41 @@ class Layer(nn.Module):  # modeling_swin.py:508-626
         dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
         return ops.swin_window_attention_applies(self.ws, self.attention.head_dim, dtype, x.device)
 
+    def _qkv(self):
+        """The merged (3C, C) weight and (3C,) bias (None without qkv_bias) of q | k | v, and the weight's split."""
+        at = self.attention
+        lins = (at.q_proj, at.k_proj, at.v_proj)
+        w = derived(at, "swin_qkv_weight", tuple(l.weight for l in lins), lambda: torch.cat([l.weight for l in lins], 0).contiguous())
+        b = None
+        if at.q_proj.bias is not None:
+            b = derived(at, "swin_qkv_bias", tuple(l.bias for l in lins), lambda: torch.cat([l.bias for l in lins], 0).contiguous())
+        return w, b, ops.split_weight_cached(at, "swin_qkv_split", w)
+
+    def _forward_split(self, x, dims):
+        """_forward_fused's inference branch with the Linears and the MLP on ops.swin_linear: five launches and two stock
+        LayerNorms per layer."""
+        at, mlp = self.attention, self.mlp
+        w, b, ws = self._qkv()
+        q, k, v = ops.swin_linear(self.layernorm_before(x), w, b, n_out=3, w_split=ws)
+        pad = lambda lin: None if lin.bias is None else lin.bias.detach()
+        a = ops.swin_window_attention(q, k, v, at.relative_position_bias.relative_position_bias_table.detach().float(), dims,
+                                      at.heads, self.ws, self.shift, pad(at.k_proj), pad(at.v_proj))
+        x = ops.swin_linear(a, at.o_proj.weight, at.o_proj.bias, residual=x, w_split=_split(at.o_proj))
+        h = ops.swin_linear(self.layernorm_after(x), mlp.fc1.weight, mlp.fc1.bias, gelu=True, w_split=_split(mlp.fc1))
+        return ops.swin_linear(h, mlp.fc2.weight, mlp.fc2.bias, residual=x, w_split=_split(mlp.fc2))
+
+    def _split_applies(self, x):
+        at, mlp = self.attention, self.mlp
+        if self.training and self.drop_path > 0.0:  # stochastic depth sits between o_proj and the residual
+            return False
+        hid = x[..., :1].expand(*x.shape[:-1], mlp.fc1.weight.shape[0])  # the shape of fc2's input, no memory
+        # q_proj inside swin_linear_applies puts the merged (3C, C) weight inside it with n_out = 3: C is a multiple of 32
+        return _split_linears_apply(x, self, ((x, at.q_proj.weight, 1), (x, at.o_proj.weight, 1), (x, mlp.fc1.weight, 1),
+                                              (hid, mlp.fc2.weight, 1)))
+
     def _forward_fused(self, x, dims):
+        if self._split_applies(x):
+            return self._forward_split(x, dims)
         at = self.attention
         h = self.layernorm_before(x)  # image-order tokens: no pad, no roll, no partition, no pad rows in the GEMMs
         q, k, v = at.q_proj(h), at.k_proj(h), at.v_proj(h)
@@ -176,7 +237,10 @@ class PatchMerging(nn.Module):  # modeling_swin.py:289-326
         if H % 2 or W % 2:
             x = F.pad(x, (0, 0, 0, W % 2, 0, H % 2))
         x = torch.cat([x[:, r::2, c::2, :] for c in range(2) for r in range(2)], dim=-1)
-        return self.reduction(self.norm(x.view(B, -1, 4 * C)))
+        h = self.norm(x.view(B, -1, 4 * C))
+        if _split_linears_apply(h, self, ((h, self.reduction.weight, 1),)):
+            return ops.swin_linear(h, self.reduction.weight, None, w_split=_split(self.reduction))
+        return self.reduction(h)
 
 
 class Stage(nn.Module):

@@ -37,6 +37,12 @@ SHORTCUT_FOLD = True
 # token_linear launches (the reference of the tests: the fused kernel gives their bits).
 TOKEN_FFN_FUSED = True
 
+# The inference forward of a Swin layer runs its Linears and MLP (merged q | k | v, o_proj + residual, fc1 + GELU, fc2 +
+# residual) and patch merging's reduction on swin_linear while this is on and swin_linear_applies.  True: at
+# every level of SPLIT_PRECISION; False: never, the stock F.linear route (the reference of the tests and of tools/);
+# a tuple of level names: at those levels only -- the default, set by §45's measurements level by level.
+SWIN_LINEAR_SPLIT: bool | tuple = ("highest", "high", "medium")
+
 # The precision of the split-bf16 GEMMs and convolutions (token_linear, conv1x1, conv1x1_gn, conv3x3, conv3x3_stats,
 # stem_conv_pool on their split kernels), read at every call: "highest" (or None) = three bf16 pieces per operand
 # and six products, fp32 accuracy; "high" = two pieces, three products (error floor 2^-14 of sum |x w|); "medium" = one
@@ -57,7 +63,8 @@ from .fused import (add_broadcast, bias_act_, bias_relu_maxpool, group_norm_act_
 from .gemm import (conv1x1, conv1x1_applies, conv1x1_dual, conv1x1_dual_applies, conv1x1_gn, conv3x3, conv3x3_applies, conv3x3_stats, conv_group_stats_applies,
                    ROWS_FFN, ROWS_NATURAL, ffn_row_order, linear_tokens, split_weight, split_weight_3x3,
                    split_weight_cached, split_weight_rows, split_weight_rows_cached, split_weight_stem, stem_conv_pool,
-                   stem_conv_pool_applies, stem_weight_columns, stem_weight_matrix, token_ffn, token_ffn_applies,
+                   stem_conv_pool_applies, stem_weight_columns, stem_weight_matrix, swin_linear, swin_linear_applies,
+                   token_ffn, token_ffn_applies,
                    token_linear, token_linear_applies, token_wgrad, token_wgrad_applies)
 from .k1 import (k1_bwd_deterministic, k1_lane_order, k1_lane_rows, k1_lanes_applies, k1_rows_applies, ms_deform_attn,
                  ms_deform_attn_bwd, ms_deform_attn_fused, ms_deform_attn_fused_lanes, ms_deform_attn_fused_packed,

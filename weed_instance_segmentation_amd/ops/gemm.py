@@ -4,7 +4,7 @@ from __future__ import annotations
 import torch
 
 from .. import ops as _flags  # the package itself: SPLIT_PRECISION is assigned on it and read when a split kernel is called
-from .._lib import load
+from .._lib import Wm2fError, load
 from ..derived import derived
 from ._core import _launch, _p, _req
 from .fused import bias_act_, bias_relu_maxpool
@@ -200,6 +200,81 @@ def token_ffn(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Ten
     _launch("wm2f_token_ffn_split_fwd_p", x, _p(x), _p(w1_split), _p(b1), _p(w2_split), _p(b2), _p(residual), _p(gamma), _p(beta),
             _p(pos), _p(out), _p(out_pos), M, K, F_, N, pos_rows, eps, pieces, tag=f"token_ffn_K{K}_F{F_}_split" + lvl)
     return (out, out_pos) if pos is not None else out
+
+
+_SWIN_LINEAR_LIMIT = 1 << 31  # bytes of x, of an output and of the residual in one call (32-bit buffer offsets)
+
+
+def swin_linear_applies(x: torch.Tensor, weight: torch.Tensor, n_out: int = 1) -> bool:
+    """Shapes swin_linear is built for: fp32 on a GPU, weight (N, K) with K a multiple of 32 and N of 16 (n_out = 3: N / 3 a
+    multiple of 16), x (..., K) with at least one row, the split weight below 2 GiB.  Any M: rows are cut into calls."""
+    if not isinstance(weight, torch.Tensor) or weight.dim() != 2 or x.dim() < 1 or n_out not in (1, 3):
+        return False
+    N, K = int(weight.shape[0]), int(weight.shape[1])
+    return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and K > 0 and K % 32 == 0
+            and N > 0 and N % 16 == 0 and x.shape[-1] == K and x.numel() >= K and N * K * 6 < (1 << 31)
+            and (n_out == 1 or (N % 3 == 0 and (N // 3) % 16 == 0)))
+
+
+def _aligned16(t):
+    """A view into a flat parameter bucket, or a row range of a larger tensor, may start anywhere: the kernel reads 16-byte
+    pieces, so such a tensor is copied."""
+    return t.clone() if t is not None and t.data_ptr() % 16 else t
+
+
+def swin_linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None, *, gelu: bool = False,
+                residual: torch.Tensor | None = None, n_out: int = 1, w_split: torch.Tensor | None = None, config: int = -1):
+    """A Linear of the Swin backbone with its epilogue fused (inference, no autograd; wm2f_swin_linear_split_fwd_p, DESIGN
+    §45): x (..., K) @ weight (N, K)^T + bias (None: no bias), then one of: nothing; gelu=True, the exact GELU; residual
+    (..., N), added.  fp32 accuracy on the bf16 matrix cores at ops.SPLIT_PRECISION "highest", the lower levels as the other
+    split kernels.  n_out = 3 (bias epilogue only) returns the three N / 3-wide column blocks as three contiguous tensors:
+    the merged q | k | v projection.  `w_split` = split_weight(weight) if the caller keeps one.  config >= 0 forces an entry
+    of the kernel's tile table (tests, tuning; the same bits), -1 lets the host choose.  Rows are cut into several calls
+    when x, an output or the residual reaches 2 GiB.  A strided or 16-byte-unaligned tensor is copied first (as _req does
+    for strides).  The shapes of swin_linear_applies."""
+    ts = {"x": x, "weight": weight, "bias": bias, "residual": residual}
+    for name, t in ts.items():
+        if t is not None and not isinstance(t, torch.Tensor):
+            raise TypeError(f"swin_linear: {name}: expected a tensor")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts.values()):
+        raise Wm2fError("swin_linear has no backward: call it under no_grad or on tensors that do not require grad")
+    x, weight = _aligned16(_req(x, "x")), _req(weight, "weight")
+    if weight.dim() != 2 or x.dim() < 1:
+        raise ValueError(f"swin_linear: x {tuple(x.shape)} weight {tuple(weight.shape)}")
+    N, K = int(weight.shape[0]), int(weight.shape[1])
+    if gelu and residual is not None:
+        raise ValueError("swin_linear: one epilogue: gelu or residual")
+    if n_out not in (1, 3) or (n_out == 3 and (gelu or residual is not None)):
+        raise ValueError("swin_linear: n_out is 1, or 3 with the bias epilogue")
+    if not swin_linear_applies(x, weight, n_out):
+        raise ValueError(f"swin_linear: x {tuple(x.shape)} weight {tuple(weight.shape)} n_out {n_out} outside swin_linear_applies")
+    M = x.numel() // K
+    if bias is not None:
+        bias = _aligned16(_req(bias, "bias"))
+        if bias.shape != (N,):
+            raise ValueError(f"swin_linear: bias {tuple(bias.shape)} for {N} features")
+    if residual is not None:
+        residual = _aligned16(_req(residual, "residual"))
+        if residual.numel() != M * N:
+            raise ValueError("swin_linear: residual shape")
+    if w_split is None:
+        w_split = split_weight(weight)
+    else:
+        _check_split(w_split, N * K * 6, x, "swin_linear: w_split is not split_weight(weight)")
+    n3 = N // n_out
+    outs = [torch.empty(*x.shape[:-1], n3, device=x.device, dtype=torch.float32) for _ in range(n_out)]
+    pieces, lvl = _split_pieces()
+    epilogue = 1 if gelu else (2 if residual is not None else 0)
+    tag = f"swin_linear_K{K}_N{N}" + ("_gelu" if gelu else "") + ("_res" if residual is not None else "") + \
+        ("_qkv" if n_out == 3 else "") + lvl
+    rows = max(1, (_SWIN_LINEAR_LIMIT - 1) // (4 * max(K, N)))  # whole rows per call; a row is a multiple of 64 bytes
+    x2, r2, o2 = x.view(M, K), None if residual is None else residual.view(M, N), [o.view(M, n3) for o in outs]
+    for m0 in range(0, M, rows):
+        m1 = min(M, m0 + rows)
+        oc = [o[m0:m1] for o in o2] + [None] * (3 - n_out)
+        _launch("wm2f_swin_linear_split_fwd_p", x, _p(x2[m0:m1]), _p(w_split), _p(bias), _p(None if r2 is None else r2[m0:m1]),
+                _p(oc[0]), _p(oc[1]), _p(oc[2]), m1 - m0, K, N, epilogue, int(n_out), int(config), pieces, tag=tag)
+    return outs[0] if n_out == 1 else tuple(outs)
 
 
 def conv1x1_applies(x: torch.Tensor, weight: torch.Tensor, stride: int = 1) -> bool:
