@@ -1831,6 +1831,69 @@ int wm2f_labelmap_skeleton(const void* map, int dtype, int32_t* out, int32_t* st
 int wm2f_labelmap_skeleton_stats(const int32_t* skel, const int32_t* d2, const int32_t* ids, const int32_t* n_ids,
                                  int64_t* stats, int B, int H, int W, int N, void* stream);
 
+/* ---- skeleton graphs: spur pruning, branches and node clusters, per-instance graph sums ----------
+ * A raw skeleton grows a side branch for every bump of a mask's boundary, and it has no structure.  These two calls
+ * decompose a skeleton into branches and node clusters, delete the branches that are boundary noise, and sum the graph
+ * per id.  tests/skeleton_graph_reference.py restates every rule in numpy (array passes, scipy.ndimage.label per key).
+ *
+ * Input: skel (B, H, W) int32, a skeleton map: an id in [0, N), anything else is dead (-1 after decoding).  Normally what
+ *   wm2f_labelmap_skeleton wrote, but any int32 map is defined input.  d2 (B, H, W) int32: wm2f_labelmap_distance of the
+ *   ORIGINAL map; a negative value counts as 0.
+ * Pixel classes, for a live pixel p of id k, p2 .. p9 as above (same-id live neighbours inside the image):
+ *   b = the number of pi that are 1;  X = the crossing number, the sum of !pi & p(i+1) around the ring p2 .. p9, p2.
+ *   node pixel: b >= 3.   path pixel: b <= 2.
+ *   free end: a path pixel with b <= 1, or with b = 2 and X = 1 (its two neighbours are adjacent to each other).
+ *   Nodes go by b, not by X: with X >= 3 the path pixels around a T-junction stay 8-connected through their diagonals
+ *   and the branches do not come apart.  With b >= 3 every component of path pixels is a chain or a closed ring.
+ * Components: key = 2 k + [node].  A component is an 8-connected set of pixels of equal key: a BRANCH when its pixels are
+ *   path pixels, a NODE CLUSTER when they are node pixels.  Its label is the smallest linear index y W + x among its
+ *   pixels.
+ * Branch record: P = its pixels; T = its free ends; a contact is a pair (path pixel of the branch, 8-adjacent node pixel
+ *   of the same id); cmin / cmax = the smallest / largest label among the clusters of contacted node pixels; D = the
+ *   largest d2 among contacted node pixels.
+ * Spur: a branch with T >= 1, a contact, cmin = cmax, and P <= min_pixels or 256 P'^2 <= ratio_q^2 D in int64 with
+ *   P' = min(P, 2^20).  ratio_q = round(16 ratio): "the branch is no longer than `ratio` times the half-width of the
+ *   part it grows out of", which is how long a boundary-noise spur is; a leaf is many half-widths long.  Because
+ *   cmin = cmax, everything adjacent to a deleted branch lies in one connected cluster, and a cluster is never deleted:
+ *   the 8-connected pieces of every id survive, under simultaneous deletions too.  An isolated line (no contact) and a
+ *   ring (T = 0) are never touched.  min_pixels = 0 and ratio_q = 0 delete no spur.
+ *
+ * wm2f_labelmap_skeleton_prune
+ * One round: all spurs of the image are deleted at once, decided on the state at the round's start; then `rethin`
+ *   iterations of wm2f_labelmap_skeleton's rule run on the result (they remove what is left of a node cluster, so the
+ *   former junction becomes a thin pass-through).  The result is the state after `rounds` rounds, per image,
+ *   unconditionally.  A round that changes nothing in an image leaves a fixed point of both steps.
+ * Output: out (B, H, W) int32, the pruned skeleton as an id map, -1 elsewhere.  status (B, 4) int32:
+ *   [pixels left, rounds that removed something, pixels removed in round `rounds`, pixels removed in all]; a non-zero
+ *   third entry says that `rounds` was too few, and out is then still the defined result of exactly `rounds` rounds.
+ * Limits: those of wm2f_labelmap_skeleton (WM2F_EUNSUPPORTED); a size below 1, min_pixels outside [0, 2^20], ratio_q
+ *   outside [0, 1024], rounds outside [1, 64], rethin outside [1, 16] or a null pointer: WM2F_EINVAL; sizes before
+ *   pointers, and all of them before a pointer is looked at.  out must not overlap skel or d2.  workspace:
+ *   wm2f_labelmap_skeleton_prune_workspace(B, H, W) bytes (-1 for a bad size), 16-byte aligned, no clearing needed.
+ * Kernels: per round local (classify and label inside 32 x 32 tiles), merge (tile borders), flatten, record (the branch
+ *   records at the roots: integer add / min / max atomics, the counts once per wave where a wave's pixels share a root),
+ *   delete, and the launches of wm2f_labelmap_skeleton; one clear before and a status kernel after: a fixed number of
+ *   launches whatever the content.  The kernels of a round return at once for an image in which the round before
+ *   removed nothing (per-image live counts in device memory; nothing is read back).  Bit-identical from run to run.
+ *
+ * wm2f_labelmap_skeleton_graph: one decomposition, nothing deleted.  ids / n_ids / N as wm2f_labelmap_skeleton_stats
+ *   takes them; with a list, row r of image b is the raw id ids[b][r] and a pixel whose value is not listed is dead.
+ *   labels (B, H, W) int32: -1 for a dead pixel, a path pixel's branch label, -2 - (cluster label) for a node pixel.
+ *   sums (B, N, 8) int64 per id:
+ *   [0] branches      [1] end branches (T >= 1 and a contact)      [2] node clusters      [3] node pixels
+ *   [4] free ends     [5] P of the longest end branch              [6] P of the longest branch
+ *   [7] closed branches (T = 0 and at most one contacted cluster)
+ *   An id without a skeleton pixel has an all-zero row.  Limits as above with N >= 0 (sums may be null when N = 0); ids
+ *   without n_ids: WM2F_EINVAL.  labels must not overlap skel.  workspace: wm2f_labelmap_skeleton_graph_workspace bytes,
+ *   16-byte aligned.  Six launches: clear, the four of the decomposition, labels (one add per root). */
+int64_t wm2f_labelmap_skeleton_prune_workspace(int B, int H, int W);
+int wm2f_labelmap_skeleton_prune(const int32_t* skel, const int32_t* d2, int32_t* out, int32_t* status, void* workspace,
+                                 int B, int H, int W, int N, int min_pixels, int ratio_q, int rounds, int rethin,
+                                 void* stream);
+int64_t wm2f_labelmap_skeleton_graph_workspace(int B, int H, int W);
+int wm2f_labelmap_skeleton_graph(const int32_t* skel, const int32_t* ids, const int32_t* n_ids, int32_t* labels,
+                                 int64_t* sums, void* workspace, int B, int H, int W, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

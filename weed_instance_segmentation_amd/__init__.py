@@ -17,7 +17,8 @@ from .instances import (CleanOptions, SplitOptions, aim_points, boundary_dilatio
                         shape_from_sums, shape_statistics, split_label_maps)
 from .treatment import TreatmentOptions, load_treatment_grid, save_treatment_grid, treatment_grid  # noqa: F401
 from .rows import RowOptions, annotate_rows, crop_rows  # noqa: F401
-from .skeleton import (SKELETON_TRAITS, SkeletonOptions, annotate_skeletons, skeleton_from_sums,  # noqa: F401
+from .skeleton import (SKELETON_GRAPH_TRAITS, SKELETON_TRAITS, PruneOptions, SkeletonOptions, annotate_skeletons,  # noqa: F401
+                       prune_skeleton_maps, skeleton_branch_maps, skeleton_from_sums, skeleton_graph_statistics,
                        skeleton_maps, skeleton_statistics)
 from .rle import (coco_results, decode_rle, encode_label_maps, rle_from_string, rle_to_string,  # noqa: F401
                   save_coco_results)

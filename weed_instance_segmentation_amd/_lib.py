@@ -217,6 +217,10 @@ SIGNATURES = {
     "wm2f_labelmap_skeleton_workspace": (c_int64, [_I, _I, _I]),
     "wm2f_labelmap_skeleton": (c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_labelmap_skeleton_stats": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "wm2f_labelmap_skeleton_prune_workspace": (c_int64, [_I, _I, _I]),
+    "wm2f_labelmap_skeleton_prune": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "wm2f_labelmap_skeleton_graph_workspace": (c_int64, [_I, _I, _I]),
+    "wm2f_labelmap_skeleton_graph": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
 }
 
 # additions of the profiling library (include/wm2f_prof.h)

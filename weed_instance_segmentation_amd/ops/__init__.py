@@ -85,7 +85,7 @@ from .postprocess import (_GRID, instance_any, instance_maps, instance_scores, i
                           panoptic_relabel_, panoptic_segments, semantic_resize_argmax, semantic_scores)
 from .rle import labelmap_toggle_counts, labelmap_toggles, rle_paint_
 from .rows import labelmap_row_bands, labelmap_row_votes, row_angle_table, row_bins, row_offset
-from .skeleton import labelmap_skeleton, labelmap_skeleton_stats
+from .skeleton import labelmap_skeleton, labelmap_skeleton_graph, labelmap_skeleton_prune, labelmap_skeleton_stats
 from .split import labelmap_split
 from .trace import labelmap_trace
 from .tiles import tile_blend, tile_compose, tile_link, tile_owned_counts, tile_pair_counts
