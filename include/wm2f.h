@@ -605,6 +605,20 @@ int wm2f_conv3x3_split_stats_fwd_p(const void* x, const void* w_split, void* out
 int wm2f_stem7x7_pool_fwd_p(const void* x, const void* w_split, const void* bias, void* out, int B, int Cin, int N, int Hi,
                             int Wi, int grid, int pieces, void* stream);
 
+/* The 3x3 entry points with the route of the launch: 0 the direct kernel, which loads and splits x once per tap;
+ * 1 the staged kernel, which splits an 8 x 32 pixel tile plus its halo once per channel block into LDS and reads the nine
+ * taps from there -- the same MFMAs in the same order, so the same bits in `out`; -1 the host's rule, which is what every
+ * entry point above means.  The staged kernel is built for stride 1 and the WN = 1 entries of the tile table, within the
+ * device's LDS per workgroup; route = 1 anywhere else returns WM2F_EINVAL, launches nothing and leaves out and stats_out
+ * untouched.  config keeps meaning the tile-table entry.
+ * wm2f_conv3x3_split_route: pure host function, the route (0 / 1) and in *entry the tile-table entry the rule takes on a
+ *                        device of n_cu CUs with 160 KiB of LDS per workgroup; -1 for arguments no launch accepts. */
+int wm2f_conv3x3_split_fwd_r(const void* x, const void* w_split, const void* bias, void* out, int B, int Cin, int N, int Hi,
+                             int Wi, int stride, int relu, int config, int pieces, int route, void* stream);
+int wm2f_conv3x3_split_stats_fwd_r(const void* x, const void* w_split, void* out, void* stats_out, int G_out, int B, int Cin,
+                                   int N, int Hi, int Wi, int stride, int config, int pieces, int route, void* stream);
+int wm2f_conv3x3_split_route(int N, int Hi, int Wi, int stride, int B, int n_cu, int pieces, int* entry);
+
 /* wm2f_swin_linear_split_fwd_p: the Linears of a Swin block and of patch merging (inference), all fp32, row-major
  *                        and token-major, W as nn.Linear stores it, at `pieces` of the split arithmetic above:
  *                            out (M, N) = epilogue(x (M, K) . W (N, K)^T + bias[N]).

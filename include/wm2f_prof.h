@@ -27,6 +27,10 @@
  *                     (valid outputs, the same bits as the shipped kernel); 1 or unset: the shipped kernel
  *   - wm2f_token_ffn_split_fwd reads on every launch   (tools/kbench.py --prof --only ffn)
  *       WM2F_FFN_ABL  timing ablations whose OUTPUTS ARE NOT VALID: 1 no epilogue stores, 4 no MFMAs; any other value is refused
+ *   - wm2f_conv3x3_split_fwd / _fwd_p read on every launch   (tools/conv3x3_configs.py --ablation)
+ *       WM2F_C3_ABL   timing ablations whose OUTPUTS ARE NOT VALID (three pieces, no statistics): 1 splits x at tap 0 of
+ *                     each channel block only and feeds those pieces to taps 1 .. 8, 2 also drops the x loads of taps
+ *                     1 .. 8; any other value is refused
  *   - the stamp buffer below: a __device__ global, i.e. the global mutable state the production library forbids.
  */
 #ifndef WM2F_PROF_H

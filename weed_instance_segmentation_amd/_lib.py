@@ -131,6 +131,10 @@ SIGNATURES = {
     "wm2f_conv3x3_split_fwd_p": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_conv3x3_split_stats_fwd_p": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_stem7x7_pool_fwd_p": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    # the 3x3 entry points with `route` before the stream, and the host's rule
+    "wm2f_conv3x3_split_fwd_r": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "wm2f_conv3x3_split_stats_fwd_r": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "wm2f_conv3x3_split_route": (c_int, [_I, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_swin_linear_split_fwd_p": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int64, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_swin_linear_split_config": (c_int, [c_int64, _I, _I, _I]),
     "wm2f_swin_linear_split_configs": (c_int, []),

@@ -22,6 +22,10 @@ CONV1X1_SPLIT = True
 # reference of the tests).
 CONV3X3_SPLIT = True
 
+# The split 3x3 kernel's route: True lets the host's rule send a launch to the staged kernel (the x tile split
+# once per channel block in LDS) where it measured faster; False keeps every launch on the direct kernel.  The same bits.
+CONV3X3_STAGED = True
+
 # The pixel decoder's inference forward folds GroupNorm into the convolutions around it while this is True: the
 # group statistics come out of the convolution epilogues (conv1x1_gn, conv3x3_stats) and mask_projection normalises
 # layer_1's raw output in its operand load.  False keeps the separate statistics and apply passes (the reference of the tests).
@@ -60,7 +64,7 @@ from .clean import labelmap_clean
 from .copy_paste import copy_paste
 from .fused import (add_broadcast, bias_act_, bias_relu_maxpool, group_norm_act_, group_norm_act_from_stats_, group_norm_tokens_,
                     group_norm_tokens_from_stats_, resize_bilinear, resize_pyramid, tokens_to_nchw)
-from .gemm import (conv1x1, conv1x1_applies, conv1x1_dual, conv1x1_dual_applies, conv1x1_gn, conv3x3, conv3x3_applies, conv3x3_stats, conv_group_stats_applies,
+from .gemm import (conv1x1, conv1x1_applies, conv1x1_dual, conv1x1_dual_applies, conv1x1_gn, conv3x3, conv3x3_applies, conv3x3_route, conv3x3_stats, conv3x3_stats_route, conv_group_stats_applies,
                    ROWS_FFN, ROWS_NATURAL, ffn_row_order, linear_tokens, split_weight, split_weight_3x3,
                    split_weight_cached, split_weight_rows, split_weight_rows_cached, split_weight_stem, stem_conv_pool,
                    stem_conv_pool_applies, stem_weight_columns, stem_weight_matrix, swin_linear, swin_linear_applies,

@@ -438,11 +438,31 @@ def conv1x1_gn(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None 
     return out if norm is not None else (out, stats)
 
 
+def _conv3x3_route(route: int | None) -> int:
+    """The `route` argument of the wm2f_conv3x3_split_*_r entry points: an explicit 0 (direct kernel) or 1 (staged kernel,
+    refused where it is not built), else the host's rule (-1) while ops.CONV3X3_STAGED is True and the direct kernel while
+    it is False."""
+    if route is None:
+        return -1 if _flags.CONV3X3_STAGED else 0
+    if route not in (-1, 0, 1):
+        raise ValueError(f"conv3x3: route = {route!r}: None, -1 (the host's rule), 0 (direct) or 1 (staged)")
+    return int(route)
+
+
 def conv3x3_stats(x: torch.Tensor, weight: torch.Tensor, groups: int, stride: int = 1, w_split: torch.Tensor | None = None,
                   config: int = -1):
     """conv3x3 on the split kernel without bias (the shapes of conv3x3_applies), plus the GroupNorm statistics of its output
     from the epilogue: returns (out, stats), stats (B, groups, 2) fp64 as conv1x1_gn's.  `out` is bit for bit conv3x3's.
-    Needs conv_group_stats_applies(N, groups).  Inference, no autograd."""
+    Needs conv_group_stats_applies(N, groups).  The route of the launch follows ops.CONV3X3_STAGED (conv3x3_stats_route
+    forces one).  Inference, no autograd."""
+    return conv3x3_stats_route(x, weight, groups, None, stride, w_split, config)
+
+
+def conv3x3_stats_route(x: torch.Tensor, weight: torch.Tensor, groups: int, route: int | None, stride: int = 1,
+                        w_split: torch.Tensor | None = None, config: int = -1):
+    """conv3x3_stats with the `route` argument of conv3x3_route: 0 the direct kernel, 1 the staged kernel (refused where it is
+    not built), None as ops.CONV3X3_STAGED says.  `out` has the same bits on both routes; the statistics are the same fp32
+    partials where the map width is a multiple of 32, and within the same bound elsewhere."""
     if not conv3x3_applies(x, weight, stride):
         raise ValueError("conv3x3_stats: shapes outside conv3x3_applies take conv3x3 and the separate GroupNorm passes")
     x = _req(x, "x")
@@ -456,8 +476,8 @@ def conv3x3_stats(x: torch.Tensor, weight: torch.Tensor, groups: int, stride: in
     out = torch.empty(B, N, Ho, Wo, device=x.device, dtype=torch.float32)
     stats = torch.empty(B, int(groups), 2, device=x.device, dtype=torch.float64)
     pieces, lvl = _split_pieces()
-    _launch("wm2f_conv3x3_split_stats_fwd_p", x, _p(x), _p(w_split), _p(out), _p(stats), int(groups), B, Cin, N, H, W,
-            int(stride), int(config), pieces, tag=f"conv3x3_C{Cin}_N{N}_P{Ho * Wo}{lvl}")
+    _launch("wm2f_conv3x3_split_stats_fwd_r", x, _p(x), _p(w_split), _p(out), _p(stats), int(groups), B, Cin, N, H, W,
+            int(stride), int(config), pieces, _conv3x3_route(route), tag=f"conv3x3_C{Cin}_N{N}_P{Ho * Wo}{lvl}")
     return out, stats
 
 
@@ -481,8 +501,21 @@ def conv3x3(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = N
     x (B, Cin, H, W) fp32, weight (N, Cin, 3, 3).  The ReLU epilogue needs a bias.
     split=True: wm2f_conv3x3_split_fwd (fp32 accuracy on the bf16 matrix cores), with `w_split` = split_weight_3x3(weight)
     if the caller keeps one; shapes outside conv3x3_applies take the split=False path.  config >= 0 forces an entry of the
-    kernel's tile table (tests, tuning; the same bits), -1 lets the kernel choose.
+    kernel's tile table (tests, tuning; the same bits), -1 lets the kernel choose.  The route of the launch
+    (direct or staged kernel, the same bits: DESIGN §15) follows ops.CONV3X3_STAGED; conv3x3_route forces one.
     split=False: F.conv2d, then bias_act_ (or the same in torch ops when Ho * Wo is not a multiple of 4)."""
+    return _conv3x3(x, weight, bias, relu, stride, split, w_split, config, None)
+
+
+def conv3x3_route(x: torch.Tensor, weight: torch.Tensor, route: int | None, bias: torch.Tensor | None = None, relu: bool = False,
+                  stride: int = 1, w_split: torch.Tensor | None = None, config: int = -1) -> torch.Tensor:
+    """conv3x3 on the split kernel with the route of the launch: 0 the direct kernel, 1 the staged kernel (the
+    x tile split once per channel block in LDS; stride 1 and the WN = 1 entries, refused with Wm2fError elsewhere), the
+    same bits; None follows ops.CONV3X3_STAGED (True: the host's rule, False: direct)."""
+    return _conv3x3(x, weight, bias, relu, stride, True, w_split, config, route)
+
+
+def _conv3x3(x, weight, bias, relu, stride, split, w_split, config, route):
     if relu and bias is None:
         raise ValueError("conv3x3: the ReLU epilogue carries a bias")
     if not split or not conv3x3_applies(x, weight, stride):
@@ -507,8 +540,8 @@ def conv3x3(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = N
         _check_split(w_split, N * 9 * Cin * 6, x, "conv3x3: w_split is not split_weight_3x3(weight)")
     out = torch.empty(B, N, Ho, Wo, device=x.device, dtype=torch.float32)
     pieces, lvl = _split_pieces()
-    _launch("wm2f_conv3x3_split_fwd_p", x, _p(x), _p(w_split), _p(bias), _p(out), B, Cin, N, H, W, int(stride),
-            1 if relu else 0, int(config), pieces, tag=f"conv3x3_C{Cin}_N{N}_P{Ho * Wo}{lvl}")
+    _launch("wm2f_conv3x3_split_fwd_r", x, _p(x), _p(w_split), _p(bias), _p(out), B, Cin, N, H, W, int(stride),
+            1 if relu else 0, int(config), pieces, _conv3x3_route(route), tag=f"conv3x3_C{Cin}_N{N}_P{Ho * Wo}{lvl}")
     return out
 
 
