@@ -1908,6 +1908,42 @@ int64_t wm2f_labelmap_skeleton_graph_workspace(int B, int H, int W);
 int wm2f_labelmap_skeleton_graph(const int32_t* skel, const int32_t* ids, const int32_t* n_ids, int32_t* labels,
                                  int64_t* sums, void* workspace, int B, int H, int W, int N, void* stream);
 
+/* ---- colour: per-instance sums of the picture under an id map, vegetation-index histogram and mask
+ * A picture is (B, H, W, 3) uint8, packed, R G B per pixel, at any byte address.  An INDEX is I = a R + b G + c B with
+ * integer coefficients, not all zero, |a| + |b| + |c| <= 32.  Its smallest value is Imin = -255 x (the sum of the
+ * negative coefficients' magnitudes); it takes bins = 255 (|a| + |b| + |c|) + 1 values (at most 8161); a pixel's bin is
+ * I - Imin.  The NORMALISED index of a pixel is q = floor(4096 I / (R + G + B)), 0 where R + G + B = 0: Q12 on the
+ * chromatic coordinates, FLOOR division ((200, 1, 0) under (-1, 2, -1) gives -4035).  tests/color_reference.py restates
+ * every rule in numpy with Python's //.
+ *
+ * wm2f_labelmap_color_stats: maps, ids / n_ids / N and "a value that is no listed id belongs to nothing" are
+ *   wm2f_labelmap_instance_stats'.  thresholds (B) int32 on the device.  sums (B, N, 14) int64 per instance, over the
+ *   pixels that carry its id:
+ *   [0] area   [1..3] sum R, G, B   [4..6] sum R^2, G^2, B^2   [7..9] sum RG, RB, GB
+ *   [10] n_on: pixels with I > thresholds[b]   [11] sum q (signed)
+ *   [12] n_dark: pixels with max(R, G, B) < dark   [13] n_bright: pixels with max(R, G, B) >= bright
+ *   An id without a pixel has an all-zero row.  At the limits (area <= 2^28) every sum stays below 2^45.
+ *   hue (B, N, K) int64, or null (then K and min_chroma are not looked at): hue[b][r][k] counts the instance's pixels with
+ *   chroma cr = mx - mn >= min_chroma whose integer hue h falls in bin h / (360 / K), mx and mn the largest and smallest
+ *   of R, G, B.  h in [0, 360), with floor division, the cases in this order:
+ *     mx == R: h = floor(60 (G - B) / cr), plus 360 when negative;   else mx == G: h = 120 + floor(60 (B - R) / cr);
+ *     else: h = 240 + floor(60 (R - G) / cr).          (255, 0, 1) gives 359.
+ *   This is the project's own integer hue; it is NOT Pillow's float HSV of wm2f_photometric_u8.
+ *   Both results are cleared inside the call.  A memset per result and one launch whatever N.
+ * wm2f_image_index_hist: hist (B, bins) int64, cleared inside the call: the count of every value of I over the picture.
+ * wm2f_image_index_mask: mask (B, H, W) uint8 <- 1 where I > thresholds[b], else 0; counts (B) int64, cleared inside the
+ *   call, <- the on-pixels.  One launch; 3 bytes read and 1 written per pixel.
+ * Limits: H, W <= 16384, B <= 32, N <= 4096, else WM2F_EUNSUPPORTED; a size below 1, coefficients outside the rule above,
+ *   dark or bright outside [0, 255], with hue K outside [1, 36] or not a divisor of 360 or min_chroma outside [1, 255],
+ *   another map dtype, a null pointer, ids without n_ids: WM2F_EINVAL; sizes and scalars before pointers.  No float
+ *   instruction, integer atomics only: bit-identical from run to run.  No call allocates, keeps state or waits. */
+int wm2f_labelmap_color_stats(const uint8_t* image, const void* map, int dtype, const int32_t* ids, const int32_t* n_ids,
+                              int ca, int cb, int cc, const int32_t* thresholds, int dark, int bright, int K,
+                              int min_chroma, int64_t* sums, int64_t* hue, int B, int H, int W, int N, void* stream);
+int wm2f_image_index_hist(const uint8_t* image, int ca, int cb, int cc, int64_t* hist, int B, int H, int W, void* stream);
+int wm2f_image_index_mask(const uint8_t* image, int ca, int cb, int cc, const int32_t* thresholds, uint8_t* mask,
+                          int64_t* counts, int B, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,8 @@ from .rows import RowOptions, annotate_rows, crop_rows  # noqa: F401
 from .skeleton import (SKELETON_GRAPH_TRAITS, SKELETON_TRAITS, PruneOptions, SkeletonOptions, annotate_skeletons,  # noqa: F401
                        prune_skeleton_maps, skeleton_branch_maps, skeleton_from_sums, skeleton_graph_statistics,
                        skeleton_maps, skeleton_statistics)
+from .color import (COLOR_TRAITS, ColorOptions, annotate_colors, color_from_sums, color_statistics,  # noqa: F401
+                    otsu_threshold, vegetation_masks, vegetation_threshold)
 from .rle import (coco_results, decode_rle, encode_label_maps, rle_from_string, rle_to_string,  # noqa: F401
                   save_coco_results)
 from .contours import (instance_polygons, save_via_annotations, trace_label_maps, via_annotations)  # noqa: F401

@@ -20,7 +20,7 @@ LIB = os.path.join(HERE, "libwm2f.so")
 # environment knobs of K2 / K3 (include/wm2f_prof.h).  tools/ load it; the product never does.
 OBJ_PROF = os.path.join(CSRC, "build_prof")
 LIB_PROF = os.path.join(HERE, "libwm2f_prof.so")
-SOURCES = ["api.hip", "msdeform.hip", "msdeform_tiled.hip", "msdeform_quad.hip", "msdeform_tiled_bwd.hip", "mask_einsum.hip", "mask_einsum_bf16.hip", "token_gemm.hip", "token_gemm_split.hip", "swin_linear_split.hip", "conv1x1_split.hip", "conv3x3_split.hip", "stem_split.hip", "token_wgrad.hip", "layernorm_train.hip", "attn_mask.hip", "masked_xattn.hip", "swin_attn.hip", "swin_attn_bwd.hip", "matcher.hip", "lsa.hip", "fused_elementwise.hip", "postprocess.hip", "postprocess_sp.hip", "mask_loss.hip", "coco_eval.hip", "instance_stats.hip", "boundary.hip", "distance.hip", "nearest.hip", "panoptic_eval.hip", "overlay.hip", "preprocess.hip", "augment.hip", "photometric.hip", "orient.hip", "copy_paste.hip", "ccl.hip", "polygon.hip", "rle.hip", "trace.hip", "tiles.hip", "clean.hip", "tile_blend.hip", "split.hip", "shape.hip", "rows.hip", "skeleton.hip", "skeleton_graph.hip"]
+SOURCES = ["api.hip", "msdeform.hip", "msdeform_tiled.hip", "msdeform_quad.hip", "msdeform_tiled_bwd.hip", "mask_einsum.hip", "mask_einsum_bf16.hip", "token_gemm.hip", "token_gemm_split.hip", "swin_linear_split.hip", "conv1x1_split.hip", "conv3x3_split.hip", "stem_split.hip", "token_wgrad.hip", "layernorm_train.hip", "attn_mask.hip", "masked_xattn.hip", "swin_attn.hip", "swin_attn_bwd.hip", "matcher.hip", "lsa.hip", "fused_elementwise.hip", "postprocess.hip", "postprocess_sp.hip", "mask_loss.hip", "coco_eval.hip", "instance_stats.hip", "boundary.hip", "distance.hip", "nearest.hip", "panoptic_eval.hip", "overlay.hip", "preprocess.hip", "augment.hip", "photometric.hip", "orient.hip", "copy_paste.hip", "ccl.hip", "polygon.hip", "rle.hip", "trace.hip", "tiles.hip", "clean.hip", "tile_blend.hip", "split.hip", "shape.hip", "rows.hip", "skeleton.hip", "skeleton_graph.hip", "color.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "group_norm.h"), os.path.join(CSRC, "labelling.h"), os.path.join(CSRC, "labelmap.h"),
            os.path.join(CSRC, "msdeform_tiled.h"), os.path.join(CSRC, "postprocess_grid.h"),
            os.path.join(os.path.dirname(HERE), "include", "wm2f.h"),

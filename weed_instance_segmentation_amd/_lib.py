@@ -35,6 +35,7 @@ WM2F_COPY_PASTE_DESC_LEN = 5
 WM2F_CLEAN_KEEP_ALL, WM2F_CLEAN_KEEP_LARGEST = 0, 1
 WM2F_CLEAN_ALL, WM2F_CLEAN_PIECES, WM2F_CLEAN_CHOOSE, WM2F_CLEAN_HOLES, WM2F_CLEAN_PAINT = range(5)
 WM2F_PRE_MAX_IMAGES, WM2F_PRE_MAX_SIDE = 32, 16384
+WM2F_COLOR_COLUMNS, WM2F_COLOR_MAX_WEIGHT, WM2F_COLOR_MAX_HUE_BINS = 14, 32, 36
 # route[0] of wm2f_masked_xattn_route
 (WM2F_K2_UNSUPPORTED, WM2F_K2_FWD_GENERAL, WM2F_K2_FWD_FULL, WM2F_K2_BF16_FWD, WM2F_K2_BWD_GENERAL, WM2F_K2_BWD_FULL,
  WM2F_K2_BF16_BWD) = range(7)
@@ -225,6 +226,9 @@ SIGNATURES = {
     "wm2f_labelmap_skeleton_prune": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "wm2f_labelmap_skeleton_graph_workspace": (c_int64, [_I, _I, _I]),
     "wm2f_labelmap_skeleton_graph": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "wm2f_labelmap_color_stats": (c_int, [_P, _P, _I, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P]),
+    "wm2f_image_index_hist": (c_int, [_P, _I, _I, _I, _P, _I, _I, _I, _P]),
+    "wm2f_image_index_mask": (c_int, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
 }
 
 # additions of the profiling library (include/wm2f_prof.h)

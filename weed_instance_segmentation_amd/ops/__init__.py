@@ -61,6 +61,7 @@ from .._lib import check
 from ._core import KernelTimer, _p, _stream, set_kernel_timer
 from .ccl import label_components, resize_nearest_tables
 from .clean import labelmap_clean
+from .color import image_index_hist, image_index_mask, index_coefficients, index_range, labelmap_color_stats
 from .copy_paste import copy_paste
 from .fused import (add_broadcast, bias_act_, bias_relu_maxpool, group_norm_act_, group_norm_act_from_stats_, group_norm_tokens_,
                     group_norm_tokens_from_stats_, resize_bilinear, resize_pyramid, tokens_to_nchw)

@@ -287,7 +287,7 @@ def _device_image(image) -> torch.Tensor:
 def segment_tiled(image, model, processor, tile: int = 1024, overlap: int = 256, batch_size: int = 4,
                   threshold: float = 0.5, mask_threshold: float = 0.5, overlap_mask_area_threshold: float = 0.8,
                   merge_threshold=(1, 2), return_instance_stats: bool = False, clean=None,
-                  return_aim_points: bool = False, split=None, return_shape_stats: bool = False) -> dict:
+                  return_aim_points: bool = False, split=None, *, colors=None, return_shape_stats: bool = False) -> dict:
     """Instance segmentation of an image of any size at native resolution: overlapping tiles (`tile_windows`), `batch_size`
     of them at a time through `processor(images=...)`, `model(pixel_values=...)` under no_grad and
     `processor.post_process_instance_segmentation(target_sizes=tile size)`, then `merge_tile_results`.  The image (PIL
@@ -297,10 +297,17 @@ def segment_tiled(image, model, processor, tile: int = 1024, overlap: int = 256,
     called with `images=` alone, so its own size settings decide how a tile is fed.  `clean=CleanOptions(...)` repairs
     the merged map (`merge_tile_results`); the tiles themselves are merged as predicted; `return_aim_points=True` adds the
     merged map's aim points and clearances there; `split=SplitOptions(...)` parts touching plants of the merged map
-    there; `return_shape_stats=True` adds the merged map's shape traits there.  Returns `merge_tile_results`'s dictionary."""
+    there; `return_shape_stats=True` adds the merged map's shape traits there.  Returns `merge_tile_results`'s dictionary.
+    `colors=ColorOptions(...)` adds the colour traits of the merged map's instances under the full-size picture, which is
+    on the device already (`annotate_colors`); None: the result is what it is without.  `colors` and
+    `return_shape_stats` are keyword-only: a further option can join them without moving anyone's positional slot."""
     batch_size = int(batch_size)
     if batch_size < 1:
         raise ValueError(f"segment_tiled: batch_size must be at least 1, got {batch_size}")
+    if colors is not None:
+        from .color import ColorOptions, annotate_colors
+        if not isinstance(colors, ColorOptions):
+            raise TypeError(f"segment_tiled: colors must be a ColorOptions or None, got {type(colors).__name__}")
     img = _device_image(image)
     grid = tile_windows(int(img.shape[0]), int(img.shape[1]), tile, overlap)
     crops = [img[y0:y1, x0:x1] for y0, x0, y1, x1 in grid.windows]
@@ -313,9 +320,10 @@ def segment_tiled(image, model, processor, tile: int = 1024, overlap: int = 256,
             results += processor.post_process_instance_segmentation(
                 outputs, threshold=threshold, mask_threshold=mask_threshold,
                 overlap_mask_area_threshold=overlap_mask_area_threshold, target_sizes=[(grid.th, grid.tw)] * len(batch))
-    return merge_tile_results(results, grid, merge_threshold=merge_threshold, return_instance_stats=return_instance_stats,
-                              clean=clean, return_aim_points=return_aim_points, split=split,
-                              return_shape_stats=return_shape_stats)
+    merged = merge_tile_results(results, grid, merge_threshold=merge_threshold, return_instance_stats=return_instance_stats,
+                                clean=clean, return_aim_points=return_aim_points, split=split,
+                                return_shape_stats=return_shape_stats)
+    return merged if colors is None else annotate_colors(merged, img, colors)
 
 
 # ---------------------------------------------------------------------------------------------- the semantic route
